@@ -241,6 +241,53 @@ def parity_check(cfg, model, pairs, out, which, parity_mode=False):
                 what='outputs of the last timed step; random-init weights', seconds=round(time.perf_counter() - t0, 2))
 
 
+DUMP_BUDGET_BYTES = 64 * 10**6      # --dump-outputs: every file together, headers included
+_NPY_HEADER_BYTES = 256
+
+
+def dump_outputs(out_dir, outs):
+    """--dump-outputs DIR: what the last timed step handed its caller -- the output dicts of its forwards (the reference's keys,
+    regtr.py:218-235) -- as DIR/<key>.npy in float32 (float64 stays float64).  Per-pair lists are concatenated over the pairs in batch order
+    along their point axis, `pose` (layers, pairs, 3, 4) along its pair axis.  At most DUMP_BUDGET_BYTES in all: smallest array first, each
+    gets an equal share of what is left; an array larger than its share keeps a fixed sample of its rows along that axis (seeded by the key
+    and the row count, ascending), so two builds run with the same arguments write the same rows.
+    -> {key: {'shape': full shape, 'axis': a, 'rows_kept': k}}"""
+    import zlib
+    parts = {}
+    for key in outs[0]:
+        vals = [o[key] for o in outs]
+        if isinstance(vals[0], torch.Tensor):
+            parts[key] = (vals, 1)
+        else:
+            vals = [t for v in vals for t in v]
+            parts[key] = (vals, 1 if vals[0].dim() == 3 else 0)
+    info = {}
+    for key, (vals, axis) in parts.items():
+        shape = list(vals[0].shape)
+        shape[axis] = sum(int(t.shape[axis]) for t in vals)
+        item = 8 if vals[0].dtype == torch.float64 else 4
+        info[key] = {'shape': shape, 'axis': axis, 'bytes': int(np.prod(shape)) * item}
+    left, n_left = DUMP_BUDGET_BYTES, len(info)
+    os.makedirs(out_dir, exist_ok=True)
+    for key in sorted(info, key=lambda k: (info[k]['bytes'], k)):
+        d = info.pop(key)
+        rows = d['shape'][d['axis']]
+        share = left // n_left - _NPY_HEADER_BYTES
+        keep = rows if d['bytes'] <= share else share // max(1, d['bytes'] // max(rows, 1))
+        vals, axis = parts[key]
+        t = torch.cat([v.detach() for v in vals], axis)
+        t = t if t.dtype == torch.float64 else t.float()
+        if keep < rows:
+            idx = np.sort(np.random.default_rng([zlib.crc32(key.encode()), rows]).choice(rows, keep, replace=False))
+            t = t.index_select(axis, torch.from_numpy(idx).to(t.device))
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, f'{key}.npy'), a)
+        left -= a.nbytes + _NPY_HEADER_BYTES
+        n_left -= 1
+        info[key] = {'shape': d['shape'], 'axis': axis, 'rows_kept': int(keep)}
+    return info
+
+
 def plan_pairs(args, rank, world, device):
     """Which pairs this rank runs and how they are cut into forwards.  Weak scaling (default): `--pairs` pairs per rank and step, ids
     rank * pairs + i.  --config lomatch (configs[3], strong scaling): a fixed set of --total-pairs pairs, pair i -> rank i % world
@@ -397,7 +444,12 @@ def main():
     ap.add_argument('--cpu-baseline-only', action='store_true',
                     help='no GPU needed: time only the CPU baseline leg on the synthetic workload and print it (where /root/reference '
                          'exists this times the REAL reference module, kind "reference")')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help="after the timed steps, write the outputs of the last timed step (rank 0's forwards) as DIR/<key>.npy, float32, at most "
+                         '64 MB in all (larger outputs: a fixed, seeded sample of their rows); same arguments, same inputs: two builds compare file for file')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be >= 1')
     if args.collect_pmc:
         return collect_pmc(args)
     if args.cpu_baseline_only:
@@ -467,18 +519,23 @@ def main():
     n_rep = min(args.replicas, len(chunks))
     runner = ReplicaRunner(replicate(model, cfg, n_rep, dev), batch, chunks, dev)
 
+    keep = slice(None) if args.dump_outputs else slice(-1, None)      # the step's outputs held past it: every forward's only when they are dumped
+
     def step():
         outs = runner.run(1)
-        return runner.poses(outs), outs[-1]
+        return runner.poses(outs), outs[keep]
 
     def many(n):
         outs = runner.run(n)
-        return runner.poses(outs), outs[-1]
+        return runner.poses(outs), outs[keep]
     if n_rep > 1:
         step.many = many
     settle = settle_device(step, args.settle_s)
-    elapsed, all_poses, all_ids, last_out, per_rank = timed_passes(args, dist, lomatch, pair_ids, step, torch.cuda.synchronize, dev)
+    elapsed, all_poses, all_ids, last_outs, per_rank = timed_passes(args, dist, lomatch, pair_ids, step, torch.cuda.synchronize, dev)
     peak_gb = torch.cuda.max_memory_allocated(dev) / 2**30       # inputs, weights and every buffer of the forwards so far
+    dumped = dump_outputs(args.dump_outputs, last_outs) if args.dump_outputs and rank == 0 else None
+    last_out = last_outs[-1]
+    del last_outs
     assert all_poses.shape[0] == pairs_per_step and torch.isfinite(all_poses).all()
     ranks_seen = count_ranks(all_ids, lomatch, n_local, world)                                      # who entered the all_gather
     assert ranks_seen == world, (ranks_seen, world)
@@ -527,6 +584,8 @@ def main():
                                       'bf16x2': 'bf16 three-term split in the cross-encoder Linears, bf16x3 elsewhere',
                                       'bf16': 'plain bf16 operands in the cross-encoder Linears and attention core, float32-grade elsewhere'}[dtype]},
         }
+        if dumped is not None:
+            res['dump_outputs'] = {'dir': args.dump_outputs, 'what': "the last timed step's outputs (bench.dump_outputs)", 'arrays': dumped}
         if args.emulate_rank_of:
             W = args.emulate_rank_of
             res['predicted'] = {

@@ -202,3 +202,64 @@ def test_forward_compulsory_bytes_matches_survey_appendix_b():
                       + sum(p.numel() * 4 for n, p in m.named_parameters() if not n.startswith('kpf_encoder')))
     assert abs(blocks / 1e6 - 119.0) < 1.5, blocks / 1e6
     assert 145e6 < total < 153e6
+
+
+def test_timed_region_runs_exactly_the_requested_steps():
+    """--steps K: bench.timed_passes runs W warm-up steps and then exactly K timed ones -- one step() per step, or one step.many(K) when
+    forwards run in flight -- and returns the last timed step's outputs; --steps 0 is refused."""
+    import argparse
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    ids = torch.arange(4, dtype=torch.int32)
+    for K, W in ((1, 0), (7, 3)):
+        calls = []
+
+        def step():
+            calls.append(1)
+            return torch.zeros(4, 3, 4), len(calls)
+        args = argparse.Namespace(warmup=W, steps=K)
+        _, poses, _, last, _ = bench.timed_passes(args, None, False, ids, step, lambda: None, 'cpu')
+        assert len(calls) == W + K and last == W + K and poses.shape == (4, 12)
+        many = []
+        step.many = lambda n: (many.append(n), (torch.zeros(4, 3, 4), 'last'))[1]
+        calls.clear()
+        _, _, _, last, _ = bench.timed_passes(args, None, False, ids, step, lambda: None, 'cpu')
+        assert many == [K] and len(calls) == W and last == 'last'
+    r = _run(['--gpus', '1', '--stub-backend', 'gloo', '--steps', '0'])
+    assert r.returncode != 0 and '--steps' in r.stderr
+
+
+def test_dump_outputs_budget_sampling_and_layout(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): per-pair lists concatenated over the forwards' pairs in batch order, pose along its pair axis,
+    float32 files; beyond the 64 MB budget the largest arrays keep a seeded sample of rows, the same rows on every run."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+
+    def fwd(lens):
+        B = len(lens)
+        return {'src_feat': [torch.randn(6, n, 256, generator=g) for n in lens], 'src_kp': tuple(torch.randn(n, 3, generator=g) for n in lens),
+                'src_overlap': [torch.randn(6, n, 1, generator=g) for n in lens], 'pose': torch.randn(6, B, 3, 4, generator=g),
+                'tgt_feat_un': tuple(torch.randn(n, 256, generator=g).double() for n in lens)}
+    outs = [fwd([4000, 3000, 5000]), fwd([6000, 2000])]                    # two forwards of the step: 20 000 points, feat 123 MB
+    a = bench.dump_outputs(str(tmp_path / 'a'), outs)
+    b = bench.dump_outputs(str(tmp_path / 'b'), outs)
+    assert a == b
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == ['pose.npy', 'src_feat.npy', 'src_kp.npy', 'src_overlap.npy', 'tgt_feat_un.npy']
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) <= 64 * 10**6
+    for f in files:
+        x, y = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
+        assert np.array_equal(x, y) and x.dtype == (np.float64 if f == 'tgt_feat_un.npy' else np.float32)
+    kp = np.load(tmp_path / 'a' / 'src_kp.npy')
+    assert np.array_equal(kp, torch.cat([t for o in outs for t in o['src_kp']]).numpy())          # small: whole, pairs in batch order
+    pose = np.load(tmp_path / 'a' / 'pose.npy')
+    assert np.array_equal(pose, torch.cat([o['pose'] for o in outs], 1).numpy()) and pose.shape == (6, 5, 3, 4)
+    assert a['src_feat']['shape'] == [6, 20000, 256] and a['src_feat']['axis'] == 1 and 0 < a['src_feat']['rows_kept'] < 20000
+    feat = np.load(tmp_path / 'a' / 'src_feat.npy')
+    full = torch.cat([t for o in outs for t in o['src_feat']], 1).numpy()
+    assert feat.shape == (6, a['src_feat']['rows_kept'], 256)
+    assert any(np.array_equal(feat[:, 0], full[:, i]) for i in range(full.shape[1]))             # rows of the real output

@@ -1,6 +1,7 @@
 """CPU: the reference-order emulation the parity-mode HIP kernels run (regtr_amd/csrc/ref_umap.h + ref_kdtree.h, compiled for the host
 by oracle/Makefile) against the real things: libstdc++'s std::unordered_map iteration order and std::sort, and the
-unmodified reference C++ (nanoflann KD-tree visiting order + std::sort) through oracle/_ref."""
+unmodified reference C++ (nanoflann KD-tree visiting order + std::sort) through oracle/_ref, or where that was not built through
+its recorded outputs (tests/golden/ref_cpp_outputs.json, oracle/native.py: ref_available)."""
 import ctypes
 import os
 
@@ -99,7 +100,7 @@ def test_neighbour_order_vs_reference_fixture(host, case):
     assert np.array_equal(_emul_query(host, g['sub_pts'], pts, g['sub_lens'], lens, r), g['pools'])
 
 
-@pytest.mark.skipif(not native.have_ref(), reason='oracle/_ref not built (needs /root/reference)')
+@pytest.mark.skipif(not native.ref_available(), reason='neither oracle/_ref nor the recorded reference outputs')
 def test_neighbour_order_vs_unmodified_reference_cpp(host):
     rng = np.random.default_rng(11)
     clouds = [synth_cloud(rng, n, lattice=lat) for n, lat in ((3000, 0.006), (1, 0.0), (9, 0.0), (11, 0.006), (2500, 0.0), (800, 0.02))]
@@ -112,7 +113,7 @@ def test_neighbour_order_vs_unmodified_reference_cpp(host):
     assert np.array_equal(_emul_query(host, sub, pts, sl, lens, 0.0625), native.ref_batch_query(sub, pts, sl, lens, 0.0625))
 
 
-@pytest.mark.skipif(not native.have_ref(), reason='oracle/_ref not built (needs /root/reference)')
+@pytest.mark.skipif(not native.ref_available(), reason='neither oracle/_ref nor the recorded reference outputs')
 @pytest.mark.parametrize('case', ['3dmatch_kitchen', '3dmatch_home_at'])
 def test_neighbour_order_kitchen_pyramid(host, case):
     """Every table of the real red-kitchen / home_at pairs' pyramids (reference row order at every level; home_at is the dense one:
