@@ -1,4 +1,4 @@
-"""Builds regtr_amd/libregtr_hip.so (gfx950) in-tree with hipcc.  `python -m regtr_amd.build [--force] [--experimental]`.
+"""Builds regtr_amd/libregtr_hip.so (gfx950) in-tree with hipcc.  `python -m regtr_amd.build [--force] [--experimental] [--dispatch]`.
 --experimental additionally builds libregtr_hip.experimental.so (-DREGTR_EXPERIMENTAL: the measured-slower experiment kernels of
 include/regtr_hip_experimental.h, which the shipped library does not contain; regtr_amd/experimental.py)."""
 import os
@@ -126,8 +126,17 @@ def build_experimental(force=False, verbose=False):
     return build(force, verbose, variant='experimental', variant_flags=['-DREGTR_EXPERIMENTAL=1'])
 
 
+def build_dispatch(force=False, verbose=False):
+    """libregtr_hip.dispatch.so (tests only): the product sources with the tile planner's development switches read from the environment
+    (-DREGTR_DEV_ENV=1) and eight-wave attention from the first workgroup on (-DMHA_WIDE_MIN_WG=1), so tests/test_gpu_dispatch.py can force
+    every launch branch at small shapes (REGTR_DEV=1 REGTR_VARIANT=dispatch)."""
+    return build(force, verbose, variant='dispatch', variant_flags=['-DREGTR_DEV_ENV=1', '-DMHA_WIDE_MIN_WG=1'])
+
+
 if __name__ == '__main__':
     print(build(force='--force' in sys.argv, verbose=True))
     print(build_parity(force='--force' in sys.argv, verbose=True))
     if '--experimental' in sys.argv:
         print(build_experimental(force='--force' in sys.argv, verbose=True))
+    if '--dispatch' in sys.argv:
+        print(build_dispatch(force='--force' in sys.argv, verbose=True))

@@ -1,0 +1,179 @@
+"""Which kernel instantiation the three host-side dispatchers launch for a shape: a restatement of the C++ policy, for the tests.
+
+route_x3 mirrors csrc/gemm_x3.hip (x3_plan, x3_plan_f16 and the launch ladder at the end of regtr_gemm_x3) as regtr_amd/ops.py:gemm
+drives it, route_stream csrc/gemm_stream.hip (sg_cols_per_wg, the SG_L2 / SG_L3 ladder), route_mha csrc/attention.hip (regtr_mha_fwd).
+tests/test_dispatch_routes.py checks the mirror against the host-only plan queries of the library and asserts that the GPU cases
+(tests/test_gpu_dispatch.py, tests/test_gpu_ops.py) reach every instantiation listed in X3_KERNELS / STREAM_KERNELS / MHA_KERNELS.
+
+A route is '+'-joined kernel names: the product kernel, then for split-K its reduction ('reduce', 'reduce_stats/vec' or
+'reduce_stats/novec'), then 'stats_pass' when ops.gemm hands C to regtr_instnorm_stats for the statistics instead (split-K with N / 4 not a power of
+two <= 256, where that pass refuses the width as well: tests/test_gpu_dispatch.py asserts the error)."""
+
+XBK = 32
+
+
+def cdiv(a, b):
+    return -(-a // b)
+
+
+def x3_supported(M, N, K):                                              # regtr_gemm_x3_supported
+    if M < 0:
+        return False
+    if N == 32:
+        return K >= 64 and K % XBK == 0
+    return N >= 64 and N % 64 == 0 and K >= 16 and K % 4 == 0
+
+
+def x3_rs_ok(N):                                                        # x3_rs_ok: N / 4 a power of two <= 256
+    c4 = N >> 2
+    return N % 4 == 0 and 1 <= c4 <= 256 and c4 & (c4 - 1) == 0
+
+
+def x3_rs_rows(N):
+    return 1 if N >= 1024 else 1024 // N
+
+
+def x3_plan(M, N, K, dev_env={}):
+    """x3_plan -> (tile, splits, k_chunk, strip); tile 0 = 128 x 128, 1 = 128 x 64, 2 = 64 x 64."""
+    if N == 32:
+        return 1, 1, K, True                                            # the thin strip form
+    strip_on = int(dev_env.get('REGTR_X3_STRIP', 1))
+    forced = int(dev_env.get('REGTR_X3_TILE', -1))
+    forced_s = int(dev_env.get('REGTR_X3_SPLITS', 0))
+    if 0 <= forced <= 2 and (forced != 0 or N % 128 == 0):             # development: forced tile (and split count)
+        splits, k_chunk = 1, K
+        if forced_s >= 2 and K // forced_s >= 64:
+            k_chunk = cdiv(cdiv(K, forced_s), XBK) * XBK
+            splits = cdiv(K, k_chunk)
+        return forced, splits, k_chunk, bool(strip_on) and forced != 2
+
+    def tiles(bm, bn):
+        return cdiv(M, bm) * (N // bn)
+    tile = 2
+    if tiles(128, 64) >= 512 and (K >= 960 or tiles(128, 64) >= 2048):
+        tile = 1
+    if N % 128 == 0 and tiles(128, 128) >= 1536:
+        tile = 0
+    if strip_on and N % 128 == 0 and K >= 1536 and K % XBK == 0 and tiles(128, 128) >= 512:
+        tile = 0
+    tl = tiles(128, 128) if tile == 0 else tiles(128, 64) if tile == 1 else tiles(64, 64)
+    splits, k_chunk = 1, K
+    if tl < 384 and K >= 512:
+        s = min(cdiv(768, tl), K // 256, 8)
+        if s >= 2:
+            k_chunk = cdiv(cdiv(K, s), XBK) * XBK
+            splits = cdiv(K, k_chunk)
+    return tile, splits, k_chunk, bool(strip_on) and tile != 2
+
+
+def x3_stat_tile_rows(M, N, K, dev_env={}):                             # regtr_gemm_x3_stat_tile_rows
+    if not x3_supported(M, N, K) or M < 1:
+        return 0
+    tile, splits, _, _ = x3_plan(M, N, K, dev_env)
+    if splits > 1:
+        return x3_rs_rows(N) if x3_rs_ok(N) else 0
+    return 64 if tile == 2 else 128
+
+
+def x3_f16_supported(M, N, K, with_stats, dev_env={}):                 # regtr_gemm_x3_f16_supported (the plan always exists)
+    return x3_supported(M, N, K)
+
+
+def route_x3(M, N, K, planes=3, a_stats=False, want_stats=False, dev_env={}, ldc=None):
+    """The kernels ops.gemm(a, SplitWeight, planes=.., a_stats=.., want_stats=..) launches on the split kernel (force_x3_gemm; planes 4 =
+    inside `with ops.f16_pair(True)`).  ldc: the leading dimension of C (default N; only the split-K statistics reduction cares)."""
+    assert x3_supported(M, N, K) and M > 0 and planes in (1, 2, 3, 4)
+    if planes in (1, 2):
+        assert not a_stats and not want_stats, 'regtr_gemm_x3 refuses statistics / a folded operand with 1 or 2 planes'
+    assert not (N == 32 and a_stats)
+    stat = bool(want_stats) and x3_stat_tile_rows(M, N, K, dev_env) > 0   # ops.gemm: R > 0 -> stat_partial, else a pass over C
+    tile, splits, k_chunk, strip = x3_plan(M, N, K, dev_env)
+    if planes == 4:                                                     # x3_plan_f16: keep_rows = stat_partial | a_stats | tile_info
+        if not strip and not (stat or a_stats) and splits == 1 and K % XBK == 0 and cdiv(M, 128) * (N // 64) >= 512:
+            tile, strip = 1, True
+        if tile == 0 and not int(dev_env.get('REGTR_F16_CW4', 1)):
+            tile = 1
+        if tile == 0 and (not strip or a_stats or K % XBK or k_chunk % XBK):
+            tile = 1                                                    # the 8-wave tiled kernel has no f16 pair form
+    sout = stat and splits == 1                                         # split-K: the statistics come from the reduction
+    strip = strip and not a_stats and K % XBK == 0 and k_chunk % XBK == 0
+    p = f'/p{planes}'
+    st = '/stat' if sout else ''
+    if strip:                                                           # X3D_LAUNCH(MW, CW, AR): planes != 3 take AR = 2
+        cw = 4 if tile == 0 else 2
+        if planes != 3:
+            ar = 2
+        elif tile == 0:
+            ar = 4 if int(dev_env.get('REGTR_X3_IL', 1)) else 2
+        else:
+            ar = 3 if int(dev_env.get('REGTR_X3_ARING', 3)) == 3 else 2
+        k = f'x3d<4,{cw},{ar}>{p}{st}'
+    elif (int(dev_env.get('REGTR_X3_DEEP', 1)) and tile == 2 and not a_stats and planes in (3, 4) and K % XBK == 0 and k_chunk % XBK == 0
+          and cdiv(M, 64) * (N // 64) * splits <= 512):
+        k = f'x3q{p}{st}'
+    elif planes == 4 and tile == 0:
+        k = 'none'                                                      # X3_LAUNCH(2, 4, ..) has no f16 pair form: nothing runs
+    else:
+        k = f'x3/tile{tile}{p}' + ('/astats' if a_stats else '') + st
+    if splits > 1:
+        vec = (N if ldc is None else ldc) % 4 == 0
+        k += ('+reduce_stats/' + ('vec' if vec else 'novec')) if stat else '+reduce'
+    if want_stats and not stat:
+        k += '+stats_pass'
+    return k
+
+
+def route_stream(M, N, K, a_stats=False):
+    """regtr_gemm_stream: k_gemm_strip<K / 16, columns per workgroup / 32, fold>."""
+    nb = sg_cols_per_wg(N, K)
+    assert M >= 0 and K in (32, 64, 128) and 32 <= N <= 512 and N % 32 == 0 and nb > 0 and not (a_stats and K > 64)
+    kt = K // 16
+    return f'strip<{kt},{nb // 32},{int(bool(a_stats) and kt <= 4)}>'
+
+
+def sg_cols_per_wg(N, K):
+    for nb in (128, 64, 32):
+        if nb <= N and N % nb == 0 and nb * K * 6 + 8 * nb * 16 <= 64 * 1024:
+            return nb
+    return 0
+
+
+def route_mha(lens, precision, min_wg=4096, heads=8):
+    """regtr_mha_fwd: the exact-f32 kernel k_mha_fwd<1 | 4> or k_mha_fwd_bf16 with 4 or 8 waves (BW / BW8); min_wg = MHA_WIDE_MIN_WG."""
+    TQ, TK, BW, BW8 = 32, 32, 4, 8
+    n, max_len = len(lens), max(lens)
+    if max_len == 0:
+        return 'none'
+    small = cdiv(max_len, BW * TQ) * heads * n < 512
+    if precision == 2 or (precision in (0, 3) and small):
+        return 'mha_f32<4>' if cdiv(max_len, TQ) * heads * n <= 1024 and max_len > 4 * TK else 'mha_f32<1>'
+    wide = max_len > BW * TQ and cdiv(max_len, BW8 * TQ) * heads * n >= min_wg
+    return f"mha_bf16<{'BW8' if wide else 'BW4'}>/p{precision}"
+
+
+def kernels(route):
+    return set(route.split('+'))
+
+
+def _x3_kernels():
+    ks = set()
+    for planes in (1, 2, 3, 4):
+        sts = ('', '/stat') if planes >= 3 else ('',)
+        for st in sts:
+            for cw, ars in ((4, (4, 2)), (2, (3, 2))):
+                for ar in (ars if planes == 3 else (2,)):
+                    ks.add(f'x3d<4,{cw},{ar}>/p{planes}{st}')
+            if planes >= 3:
+                ks.add(f'x3q/p{planes}{st}')
+        for tile in ((0, 1, 2) if planes != 4 else (1, 2)):
+            for fold in (('', '/astats') if planes >= 3 else ('',)):
+                for st in sts:
+                    ks.add(f'x3/tile{tile}/p{planes}{fold}{st}')
+    return ks | {'reduce', 'reduce_stats/vec', 'reduce_stats/novec', 'stats_pass'}
+
+
+# every instantiation the launch ladders can reach (the 'none' of an f16 pair launch on the 8-wave tiled kernel is not one of them)
+X3_KERNELS = _x3_kernels()
+STREAM_KERNELS = {f'strip<{K // 16},{nb // 32},{fold}>' for K in (32, 64, 128) for nb in (32, 64, 128) for fold in ((0, 1) if K <= 64 else (0,))
+                  if sg_cols_per_wg(nb, K) == nb}
+MHA_KERNELS = {'mha_f32<1>', 'mha_f32<4>'} | {f'mha_bf16<{w}>/p{p}' for w in ('BW4', 'BW8') for p in (0, 1, 3)}
