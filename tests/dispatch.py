@@ -1,9 +1,11 @@
-"""Which kernel instantiation the three host-side dispatchers launch for a shape: a restatement of the C++ policy, for the tests.
+"""Which kernel instantiation the host-side dispatchers launch for a shape: a restatement of the C++ policy, for the tests.
 
 route_x3 mirrors csrc/gemm_x3.hip (x3_plan, x3_plan_f16 and the launch ladder at the end of regtr_gemm_x3) as regtr_amd/ops.py:gemm
 drives it, route_stream csrc/gemm_stream.hip (sg_cols_per_wg, the SG_L2 / SG_L3 ladder), route_mha csrc/attention.hip (regtr_mha_fwd).
 tests/test_dispatch_routes.py checks the mirror against the host-only plan queries of the library and asserts that the GPU cases
-(tests/test_gpu_dispatch.py, tests/test_gpu_ops.py) reach every instantiation listed in X3_KERNELS / STREAM_KERNELS / MHA_KERNELS.
+(tests/test_gpu_dispatch.py, tests/test_gpu_ops.py) reach every instantiation listed in X3_KERNELS / STREAM_KERNELS / MHA_KERNELS.  route_gather / route_maxpool mirror csrc/kpconv.hip
+(regtr_kpconv_gather with the flag decision of ops.kpconv, regtr_maxpool_gather); their cases are in tests/test_gpu_gather.py and their
+universes GATHER_KERNELS / MAXPOOL_KERNELS.
 
 A route is '+'-joined kernel names: the product kernel, then for split-K its reduction ('reduce', 'reduce_stats/vec' or
 'reduce_stats/novec'), then 'stats_pass' when ops.gemm hands C to regtr_instnorm_stats for the statistics instead (split-K with N / 4 not a power of
@@ -152,7 +154,8 @@ def route_mha(lens, precision, min_wg=4096, heads=8):
 
 
 def kernels(route):
-    return set(route.split('+'))
+    """The instantiations of a route: a gather kernel's '/qpw<n>' or '/g<n>' suffix (queries or groups per wave) is a launch argument."""
+    return {k.split('/')[0] if k.startswith(('mfma<', 'c1p<')) else k for k in route.split('+')}
 
 
 def _x3_kernels():
@@ -177,3 +180,80 @@ X3_KERNELS = _x3_kernels()
 STREAM_KERNELS = {f'strip<{K // 16},{nb // 32},{fold}>' for K in (32, 64, 128) for nb in (32, 64, 128) for fold in ((0, 1) if K <= 64 else (0,))
                   if sg_cols_per_wg(nb, K) == nb}
 MHA_KERNELS = {'mha_f32<1>', 'mha_f32<4>'} | {f'mha_bf16<{w}>/p{p}' for w in ('BW4', 'BW8') for p in (0, 1, 3)}
+
+
+# ------------------------------------------------------------------------------------------------ KPConv gather, max-pool (csrc/kpconv.hip)
+GATHER_WAVES, KP_PAD, MG_QPW = 4, 16, 8
+LDS_LIMIT = 160 * 1024
+
+
+def gather_computes_flag(Cin, H):                                       # regtr_kpconv_gather_computes_flag
+    return Cin == 1 or (Cin % 32 == 0 and H <= 64)
+
+
+def ops_flag_pass(ns, Cin, H, x_aligned=True, stats_aligned=True):
+    """ops.kpconv runs regtr_rowsum_positive (and hands the gather a flag) unless the gather derives the flags itself."""
+    return not (gather_computes_flag(Cin, H) and x_aligned and ns > 0 and ns * Cin < (1 << 29) and stats_aligned)
+
+
+def generic_lds(Cin, H):
+    """Dynamic LDS of k_kpconv_gather<LQ>: GATHER_WAVES tiles of QW queries x H neighbours x (KP_PAD + 6) floats."""
+    LQ = 16 if Cin <= 16 else (32 if Cin <= 32 else 64)
+    QW = 64 // LQ
+    return LQ, GATHER_WAVES * ((QW * H * (KP_PAD + 6) + 3) & ~3) * 4
+
+
+def mfma_qpw(nq):
+    return min(max(cdiv(nq, 256 * 12), 1), MG_QPW)
+
+
+def c1p_groups(nq):
+    return min(max(cdiv(nq, 256 * 8 * GATHER_WAVES * 4), 1), 8)
+
+
+def route_gather(nq, ns, Cin, H, KP=15, flag_given=False, xyzf=False, x_stats=False, aligned16=True, ld_wf=0):
+    """regtr_kpconv_gather's launch for these arguments, after the flag pass 'rowsum' (or 'rowsum/stats' with x_stats) when the caller
+    hands it a flag: 'c1', 'c1p<NS>/g<groups per wave>', 'mfma<J,V[,pre]>/qpw<queries per wave>', 'lq<LQ>' (the generic LDS-tile kernel),
+    or 'refused' (RG_ERR_ARG).  aligned16: x, wf and x_stats 16-byte aligned; xyzf: packed support records given (assumed aligned)."""
+    assert nq > 0
+    if ld_wf and ld_wf != KP * Cin and not (Cin == 1 and ld_wf == KP_PAD):
+        return 'refused'
+    if ns < 0 or H < 1 or Cin < 1 or not 1 <= KP <= KP_PAD or (xyzf and (x_stats or ns * 16 >= 1 << 31)):
+        return 'refused'
+    if not flag_given and not gather_computes_flag(Cin, H):
+        return 'refused'
+    pre = ['rowsum/stats' if x_stats else 'rowsum'] if flag_given else []
+    if Cin == 1:
+        if x_stats:
+            return 'refused'
+        HP1 = (H + 1) & ~1
+        groups = c1p_groups(nq)
+        if xyzf and 4 * HP1 <= 4 * 64 and ns > 0 and groups >= 2:
+            NS = 2 if 4 * HP1 <= 128 else (3 if 4 * HP1 <= 192 else 4)
+            return '+'.join(pre + [f'c1p<{NS}>/g{groups}'])
+        return '+'.join(pre + ['c1'])
+    fits = aligned16 and ns > 0 and ns * Cin < (1 << 29)
+    if not flag_given and not fits:
+        return 'refused'
+    if gather_computes_flag(Cin, H) and fits:
+        J = 10 if H <= 40 else (13 if H <= 52 else 16)
+        V = 4 if Cin % 64 == 0 else 2
+        return '+'.join(pre + [f"mfma<{J},{V}{',pre' if xyzf else ''}>/qpw{mfma_qpw(nq)}"])
+    LQ, lds = generic_lds(Cin, H)
+    if lds > LDS_LIMIT:
+        return 'refused'
+    return '+'.join(pre + [f'lq<{LQ}>'])
+
+
+def route_maxpool(ns, C, aligned16=True):
+    """regtr_maxpool_gather: the branch-free k_maxpool_gather_buf<QW, 8> while the table fits 32-bit byte offsets (and x is 16-byte
+    aligned), else the predicated k_maxpool_gather<QW>; QW queries per wave."""
+    assert C >= 4 and C % 4 == 0 and ns >= 0
+    QW = 4 if C <= 64 else (2 if C <= 128 else 1)
+    buf = ns > 0 and ns * C * 4 < 0xffffff00 and aligned16
+    return f"{'mp_buf' if buf else 'mp'}<{QW}>"
+
+
+GATHER_KERNELS = ({'c1', 'c1p<2>', 'c1p<3>', 'c1p<4>', 'lq<16>', 'lq<32>', 'lq<64>', 'rowsum', 'rowsum/stats'}
+                  | {f"mfma<{J},{V}{p}>" for J in (10, 13, 16) for V in (2, 4) for p in ('', ',pre')})
+MAXPOOL_KERNELS = {f'{k}<{qw}>' for k in ('mp_buf', 'mp') for qw in (4, 2, 1)}

@@ -1,13 +1,17 @@
-"""CPU: tests/dispatch.py restates the GEMM / attention dispatchers faithfully, and the GPU cases reach every instantiation they can launch.
+"""CPU: tests/dispatch.py restates the GEMM / attention / KPConv gather / max-pool dispatchers faithfully, and the GPU cases reach every
+instantiation they can launch.
 
 The mirror is checked against the plan queries libregtr_hip.so exports (host-only: no GPU needed); the coverage gate lists every
-instantiation of the launch ladders (dispatch.X3_KERNELS / STREAM_KERNELS / MHA_KERNELS) and fails when no parametrized GPU case of
-tests/test_gpu_dispatch.py or tests/test_gpu_ops.py routes to one -- e.g. after a planner retune moved a case off its branch."""
+instantiation of the launch ladders (dispatch.X3_KERNELS / STREAM_KERNELS / MHA_KERNELS / GATHER_KERNELS / MAXPOOL_KERNELS) and fails when
+no parametrized GPU case of tests/test_gpu_dispatch.py, tests/test_gpu_ops.py or tests/test_gpu_gather.py routes to one -- e.g. after a
+planner retune moved a case off its branch.  The gather mirror is checked against the library's regtr_kpconv_gather_computes_flag only:
+a refusal is never probed by calling a launcher with stand-in pointers (a mirror wrong about it would launch on garbage)."""
 import itertools
 
 from tests import dispatch
 from tests import dispatch_worker as dw
 from tests import test_gpu_dispatch as gd
+from tests import test_gpu_gather as gg
 
 MS = [1, 2, 63, 64, 65, 127, 128, 129, 130, 300, 751, 1000, 2000, 2753, 6000, 9381, 12000, 20000, 38061, 50443, 70000, 100000,
       150000, 300000, 600000, 2400000]
@@ -94,3 +98,112 @@ def test_every_mha_instantiation_is_reached():
         routes.append(route)
     routes += [dispatch.route_mha(gd.MHA_8V4_LENS, p, min_wg=1) for p in (0, 1, 3)]     # the dispatch variant's side of the bit-identity test
     _gate(dispatch.MHA_KERNELS, routes)
+
+
+def test_gather_flag_mirror_matches_library():
+    """Which (Cin, H) regtr_kpconv_gather derives the neighbour flags for (Cin 1, or a multiple of 32 with H <= 64) -- the decision behind
+    ops.kpconv's flag pass and the matrix-core route."""
+    from regtr_amd import _lib
+    L = _lib.lib()
+    n = 0
+    for Cin, H in itertools.product(list(range(1, 70)) + [94, 95, 96, 97, 127, 128, 160, 192, 256, 320, 512, 1024], list(range(1, 131))):
+        assert bool(L.regtr_kpconv_gather_computes_flag(Cin, H)) == dispatch.gather_computes_flag(Cin, H), (Cin, H)
+        n += dispatch.gather_computes_flag(Cin, H)
+    assert n > 700
+
+
+def test_gather_mirror_refusals_and_hand_off():
+    """The host-side refusals the mirror restates (never probed on the library with stand-in pointers) and the ns * Cin = 2^29 hand-off."""
+    assert dispatch.generic_lds(16, 56) == (16, 78848) and dispatch.generic_lds(16, 116) == (16, 163328)
+    assert dispatch.route_gather(64, 64, 16, 116, flag_given=True) == 'rowsum+lq<16>'
+    assert dispatch.route_gather(64, 64, 16, 117, flag_given=True) == 'refused'
+    assert dispatch.route_gather(64, 64, 16, 40) == 'refused'                              # no flag where the gather cannot derive it
+    assert dispatch.route_gather(64, 64, 64, 65) == 'refused'
+    assert dispatch.route_gather(64, 64, 1, 40, x_stats=True) == 'refused'
+    assert dispatch.route_gather(64, 64, 64, 40, xyzf=True, x_stats=True) == 'refused'
+    assert dispatch.route_gather(64, 64, 64, 40, ld_wf=16) == 'refused'
+    assert dispatch.route_gather(64, 64, 1, 40, ld_wf=16) == 'c1'
+    assert dispatch.route_gather(64, 64, 64, 40, aligned16=False) == 'refused'
+    assert dispatch.route_gather(64, 64, 64, 40, flag_given=True, aligned16=False) == 'rowsum+lq<64>'
+    assert dispatch.route_gather(4096, 2 ** 21 - 1, 256, 40) == 'mfma<10,4>/qpw2'
+    assert dispatch.route_gather(4096, 2 ** 21, 256, 40) == 'refused'
+    assert not dispatch.ops_flag_pass(2 ** 21 - 1, 256, 40) and dispatch.ops_flag_pass(2 ** 21, 256, 40)
+    assert dispatch.route_maxpool(2 ** 24 - 2, 64) == 'mp_buf<4>' and dispatch.route_maxpool(2 ** 24 - 1, 64) == 'mp<4>'
+    assert dispatch.route_maxpool(100, 128, aligned16=False) == 'mp<2>'
+
+
+def _gather_cases():
+    """(route, nq, J/V/PRE kernel, lens or None) of every parametrized gather case in tests/test_gpu_gather.py, each route re-derived."""
+    out = []
+    for Cin, H, nq, mode, route in _params(gg.test_mfma_gather_vs_fp64, 'Cin H nq mode route'.split()):
+        assert dispatch.route_gather(nq, nq, Cin, H, gg.KP, dispatch.ops_flag_pass(nq, Cin, H), mode == 'pre', mode == 'stats') == route
+        out.append((route, nq, mode))
+    for Cin, H, nq, mode, mis, route in _params(gg.test_generic_gather_vs_fp64, 'Cin H nq mode misalign route'.split()):
+        assert dispatch.route_gather(nq, nq, Cin, H, gg.KP, True, False, mode == 'stats', mis % 4 == 0) == route
+        out.append((route, nq, mode))
+    for H, nq, mode, route in _params(gg.test_c1_gather_vs_fp64, 'H nq mode route'.split()):
+        for ld_wf in (0, 16):
+            assert dispatch.route_gather(nq, nq, 1, H, gg.KP, mode == 'flag', mode == 'records', ld_wf=ld_wf) == route
+        out.append((route, nq, mode))
+    for ns, route in _params(gg.test_gather_handoff_at_2_29_feature_elements, ['ns', 'route']):
+        assert dispatch.route_gather(4096, ns, 256, 40, gg.KP, dispatch.ops_flag_pass(ns, 256, 40)) == route
+        out.append((route, 4096, 'plain'))
+    return out
+
+
+def test_every_gather_instantiation_is_reached():
+    _gate(dispatch.GATHER_KERNELS, [r for r, _, _ in _gather_cases()])
+
+
+def test_gather_pipelines_are_reached():
+    """The software pipelines see every regime: each k_kpconv_gather_mfma<J, V, PRE> at one query per wave, at some count in 2-7 and at 8,
+    the multi-query regimes with a last wave that holds fewer queries than the others; the folded InstanceNorm at 8 per wave on clouds
+    whose boundaries fall inside a wave's run (and empty clouds); k_kpconv_gather_c1p<NS> at 2 and at 8 groups per wave."""
+    mfma, c1p, stats8 = {}, {}, set()
+    for route, nq, mode in _gather_cases():
+        for part in route.split('+'):
+            if part.startswith('mfma<'):
+                k, qpw = part.split('/qpw')
+                qpw = int(qpw)
+                tail = nq % qpw != 0
+                mfma.setdefault(k, set()).add('1' if qpw == 1 else ('2-7' if qpw < 8 else '8') if tail else f'{qpw}/no-tail')
+                if mode == 'stats' and qpw == 8:
+                    lens = gg._lens(nq)
+                    off = list(itertools.accumulate(lens, initial=0))
+                    assert 0 in lens and any(o % 8 for o in off[1:-1]), lens
+                    stats8.add(k)
+            elif part.startswith('c1p<'):
+                k, g = part.split('/g')
+                c1p.setdefault(k, set()).add(int(g))
+    for k in sorted(x for x in dispatch.GATHER_KERNELS if x.startswith('mfma<')):
+        assert {'1', '2-7', '8'} <= mfma.get(k, set()), (k, mfma.get(k))
+    assert stats8 == {k for k in dispatch.GATHER_KERNELS if k.startswith('mfma<') and not k.endswith(',pre>')}, sorted(stats8)
+    for k in ('c1p<2>', 'c1p<3>', 'c1p<4>'):
+        assert {2, 8} <= c1p.get(k, set()), (k, c1p.get(k))
+
+
+def test_every_maxpool_instantiation_is_reached():
+    routes = [dispatch.route_maxpool(3001, C) for (C,) in _params(gg.test_maxpool_vs_ref, ['C'])]
+    routes += [dispatch.route_maxpool(ns, C) for C, ns in _params(gg.test_maxpool_predicated_at_4_gib, ['C', 'ns'])]
+    _gate(dispatch.MAXPOOL_KERNELS, routes)
+
+
+def test_gather_and_maxpool_edges_are_reached():
+    """The regimes around the instantiations: the generic kernel above 64 KiB of dynamic LDS, at the largest tile the launcher accepts, at
+    H > 64 with Cin % 32 == 0 and on an unaligned WF, each LQ with and without the folded statistics; both sides of the ns * Cin = 2^29
+    hand-off; the Cin = 1 kernel with a derived flag, a given flag and records, at an odd H; max-pool rows of one float4, of a partial
+    float4 group per lane and of many, and 4 GiB tables for every predicated QW."""
+    gen = [(Cin, H, mode, mis) for Cin, H, _, mode, mis, _ in _params(gg.test_generic_gather_vs_fp64, 'Cin H nq mode misalign route'.split())]
+    lds = {dispatch.generic_lds(Cin, H)[1] for Cin, H, _, _ in gen}
+    assert max(lds) > 64 * 1024 and any(64 * 1024 < b < dispatch.LDS_LIMIT // 2 for b in lds)
+    assert any(dispatch.generic_lds(Cin, H + 1)[1] > dispatch.LDS_LIMIT for Cin, H, _, _ in gen)
+    assert {m for Cin, H, m, _ in gen if Cin % 32 == 0 and H > 64} == {'plain', 'stats'}
+    assert any(mis % 4 and dispatch.gather_computes_flag(Cin, H) for Cin, H, _, mis in gen)
+    assert {(dispatch.generic_lds(Cin, H)[0], m) for Cin, H, m, _ in gen} == {(lq, m) for lq in (16, 32, 64) for m in ('plain', 'stats')}
+    assert {ns * 256 - (1 << 29) for ns, _ in _params(gg.test_gather_handoff_at_2_29_feature_elements, ['ns', 'route'])} == {-256, 0}
+    c1 = _params(gg.test_c1_gather_vs_fp64, 'H nq mode route'.split())
+    assert {m for H, nq, m, r in c1 if r.endswith('c1')} == {'derived', 'flag', 'records'} and any(H % 2 for H, _, _, _ in c1)
+    Cs = [C for (C,) in _params(gg.test_maxpool_vs_ref, ['C'])]
+    assert 4 in Cs and max(Cs) >= 1024 and {dispatch.route_maxpool(3001, C) for C in Cs if C % 16} == {'mp_buf<4>', 'mp_buf<2>', 'mp_buf<1>'}
+    big = _params(gg.test_maxpool_predicated_at_4_gib, ['C', 'ns'])
+    assert all(ns * C * 4 == 1 << 32 for C, ns in big) and {dispatch.route_maxpool(ns, C) for C, ns in big} == {'mp<4>', 'mp<2>', 'mp<1>'}
