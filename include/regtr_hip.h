@@ -35,6 +35,9 @@
  *   regtr_mha_fwd             nn.MultiheadAttention core          transformers.py:197-226
  *   regtr_attn_xyz            CorrespondenceDecoder.simple_attention   models/regtr.py:316-351
  *   regtr_weighted_procrustes pose assembly + compute_rigid_transform   regtr.py:185-203, utils/se3_torch.py:108-154
+ *   regtr_infonce             InfoNCELossFull.compute_infonce     models/losses/feature_loss.py:281-314
+ *   regtr_se3_transform       se3_transform (GT overlap masks)    data_loaders/threedmatch.py:78-84
+ *   regtr_loss_terms          overlap BCE + CorrCriterion sums    models/regtr.py:250-285, models/losses/corr_loss.py:18-40
  */
 #ifndef REGTR_HIP_H
 #define REGTR_HIP_H
@@ -355,6 +358,43 @@ int regtr_attn_xyz(const float* q, const float* k, const float* xyz, float* out,
  * status word, REGTR_STATUS_NONFINITE_POSE when an R|t came out non-finite */
 int regtr_weighted_procrustes(const float* kp, const float* corr, const float* logit, const int* seg_off, int n_pairs,
                               int n_total, int n_layers, float* pose, int* status, void* stream);
+
+
+/* ---- validation / test losses (models/regtr.py:237-294 compute_loss; inference only, no gradients) ----------------------------- */
+
+/* InfoNCE feature loss (models/losses/feature_loss.py:246-314) over packed, ragged pairs.  Pair b's anchors are rows
+ * [anc_seg_off[b], anc_seg_off[b+1]) of anc [n_anc, D] (row stride ld_anc), its targets rows [pos_seg_off[b], pos_seg_off[b+1]) of
+ * pos [n_pos, D] (row stride ld_pos), which hold the TRANSFORMED positives P' = G W_sym.  Per anchor row i, over the pair's targets j:
+ *   l_ij = A_i . P'_j (exact f32 MFMA), d_ij = sqrt_rn((dx^2 + dy^2) + dz^2) in float32 without contraction,
+ *   j* = argmin_j d_ij -- on exact ties the LOWEST j --, mask_i = d_ij* < r_p, ignore_ij = d_ij < r_n && j != j*,
+ *   loss_i = -l_ij* + logsumexp over the j not ignored.
+ * anc_pose: NULL, or [n_pairs, 12] row-major 3x4 poses applied to the anchor coordinates first (x' = ((R0 x + R1 y) + R2 z) + t,
+ * rounded per operation).  pair_out [n_pairs, 2]: (sum of loss_i over masked rows, number of masked rows) -- reduced in a fixed
+ * order, bit-reproducible.  row_loss / row_mask [n_anc]: optional (NULL) per-row loss_i and mask_i (1 / 0); a row of a pair without
+ * targets gets NaN / 0.  max_anc >= every pair's anchor count (a pair with more, or with offsets outside the arrays, gives NaN).
+ * Refused (REGTR_ERR_ARG, nothing launched): D not a multiple of 64 or above 512, a negative count, a NULL pointer with a non-zero
+ * count, ld < D, rows of anc / pos not 16-byte aligned.  ws: regtr_infonce_ws_bytes(n_pairs, max_anc) bytes. */
+size_t regtr_infonce_ws_bytes(int n_pairs, int max_anc);
+int regtr_infonce(const float* anc, int ld_anc, const float* pos, int ld_pos, const float* anc_xyz, const float* pos_xyz,
+                  const int* anc_seg_off, const int* pos_seg_off, int n_pairs, int n_anc, int n_pos, int max_anc, int D,
+                  float r_p, float r_n, const float* anc_pose, float* pair_out, float* row_loss, float* row_mask, void* ws,
+                  size_t ws_bytes, void* stream);
+
+/* The O(N) loss terms of one decoder layer, per pair b of the packed coarsest-level tokens (seg_off [2 n_pairs + 1]: the src clouds,
+ * then the tgt clouds, as RegTR.forward packs them), into out [n_pairs, 5]:
+ *   0: sum of BCE-with-logits(logit, gt_overlap) over the pair's src and tgt tokens, max(x,0) - x y + log1p(exp(-|x|)) in float64;
+ *   1, 2: sum of w |warped - T kp|_1 and sum of w over the src tokens (T = pose b, w = gt_overlap)   models/losses/corr_loss.py:18-40;
+ *   3, 4: the same over the tgt tokens with T^-1 = [R^T | -R^T t].
+ * pose: [n_pairs] poses of pose_stride floats (12: 3x4, 16: 4x4), rows 0-2 read.  Transforms and L1 errors in float32 rounded per
+ * operation, sums in float64, fixed-order reductions.  Refused like regtr_infonce (negative counts, NULLs with a non-zero count,
+ * pose_stride not 12 or 16). */
+/* x' = ((R0 x + R1 y) + R2 z) + t, rounded per operation, for every point of packed clouds: point i of cloud c (seg_off[c] <= i <
+ * seg_off[c + 1], n_clouds + 1 entries, seg_off[0] = 0, seg_off[n_clouds] = n) takes pose c (pose_stride 12: 3x4, 16: 4x4).  out [n, 3]. */
+int regtr_se3_transform(const float* xyz, const int* seg_off, int n_clouds, int n, const float* pose, int pose_stride, float* out,
+                        void* stream);
+
+int regtr_loss_terms(const float* logit, const float* gt_overlap, const float* kp, const float* warped, const int* seg_off,
+                     int n_pairs, int n_total, const float* pose, int pose_stride, float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -4,7 +4,9 @@ Replaces, for inference only, the reference's Trainer.test loop (/root/reference
 GenericRegModel.test_step / _save_3DMatch_log (models/generic_reg_model.py:130-158, 260-281):
   * B pairs per forward instead of one (conf test_batch_size: 1), next batch loaded by a worker thread into pinned
     memory and copied to the GPU on a side stream while the current batch computes;
-  * no compute_loss, no tensorboard, no per-pair host synchronisation: poses stay on the device until the end of the set;
+  * no tensorboard, no per-pair host synchronisation: poses stay on the device until the end of the set;
+  * optionally (losses=True, test.py --losses) the reference's test losses: RegTR.compute_loss per pair on GT masks from
+    overlap.compute_overlap_masks, kept on the device and reduced once at the end (the `[Losses]` line of test_epoch_end);
   * pairs sharded over ranks (one process per GPU) with a single RCCL gather of the poses; rank 0 writes the logs;
   * `est.log` blocks / `pred_transforms.npy` in the reference's exact formats, so the reference's own evaluation scripts
     (benchmark_predator / RPMNet eval) read them unchanged.
@@ -288,7 +290,8 @@ _POOL_IDS = [0]
 def _pool_fill(task):
     """Runs in a loader process: loads the pairs `idxs` (one PART of a batch) and packs them into its region [lo, lo + cap) of slab
     `slab_id` as [src clouds ..., tgt clouds ...].  -> (b, part, lens_src, lens_tgt, ids, None) or, when the part does not fit its
-    region, (b, part, None, None, ids, (src arrays, tgt arrays)) with the clouds pickled back (correct, slower)."""
+    region, (b, part, None, None, ids, (src arrays, tgt arrays)) with the clouds pickled back (correct, slower).  Last element: the
+    pairs' GT poses (3, 4) (None where the source has none), which RegTR.compute_loss needs (run_test(losses=True))."""
     b, part, idxs, slab_id, lo, cap, pool_id, source_file = task
     source = _POOL_SOURCES.get(source_file)
     if source is None:        # first task of this worker (or of a re-spawned one): the pair source arrives by file, not by fork
@@ -301,14 +304,15 @@ def _pool_fill(task):
     src, tgt = [it['src_xyz'] for it in items], [it['tgt_xyz'] for it in items]
     ls, lt = [int(c.shape[0]) for c in src], [int(c.shape[0]) for c in tgt]
     ids = [int(it['idx']) for it in items]
+    poses = [np.asarray(it['pose'], dtype=np.float32)[:3] if 'pose' in it else None for it in items]       # (GT poses: 48 B per pair)
     if sum(ls) + sum(lt) > cap:
-        return b, part, None, None, ids, ([np.ascontiguousarray(c, dtype=np.float32) for c in src], [np.ascontiguousarray(c, dtype=np.float32) for c in tgt])
+        return b, part, None, None, ids, ([np.ascontiguousarray(c, dtype=np.float32) for c in src], [np.ascontiguousarray(c, dtype=np.float32) for c in tgt]), poses
     slab = _POOL_SLABS[pool_id][slab_id]
     o = lo
     for c, n in zip(src + tgt, ls + lt):
         slab[o:o + n] = c
         o += n
-    return b, part, ls, lt, ids, None
+    return b, part, ls, lt, ids, None, poses
 
 
 def _unlink_quiet(path):
@@ -438,9 +442,10 @@ class LoaderPool:
                     t1 = time.perf_counter()
                     timing['wait_worker_s'] += t1 - t0
                     # pieces in the forward's order: every part's src clouds, then every part's tgt clouds
-                    pieces, lens_s, lens_t, ids = [[], []], [], [], []
-                    for (b, part, ls, lt, pid, arrays), t in zip(done, [a_ for a_ in range(len(done))]):
+                    pieces, lens_s, lens_t, ids, gt = [[], []], [], [], [], []
+                    for (b, part, ls, lt, pid, arrays, pp), t in zip(done, [a_ for a_ in range(len(done))]):
                         ids += pid
+                        gt += pp
                         if arrays is not None:              # oversize part: the clouds came back by value
                             ls, lt = [int(a.shape[0]) for a in arrays[0]], [int(a.shape[0]) for a in arrays[1]]
                             pieces[0] += [torch.from_numpy(a) for a in arrays[0]]
@@ -454,7 +459,7 @@ class LoaderPool:
                     n = sum(lens)
                     B = len(ids)
                     off = np.concatenate([[0], np.cumsum(lens)])
-                    item = {'ids': ids}
+                    item = {'ids': ids, 'gt_pose': gt}
                     if self.cuda:
                         if n <= self.cap:
                             if staged[k] is not None:
@@ -576,13 +581,16 @@ def pose_errors(pred, gt):
 
 
 # ------------------------------------------------------------------------------------------------------ the test loop
-def run_test(model, pairs, batch, device, logger=None, max_pairs=None, num_workers=0, loader_pool=None):
+def run_test(model, pairs, batch, device, logger=None, max_pairs=None, num_workers=0, loader_pool=None, losses=False):
     """Runs every pair of `pairs` (this rank's shard) through the model, B at a time.  loader_pool: a LoaderPool over `pairs` (loader
     processes forked by the caller, e.g. before the GPU was initialised); else num_workers > 0: a pool forked here for this pass;
     0: one loader thread (Prefetcher).
     model: one RegTR module, or a LIST of replicas with the same weights (regtr_amd.workload.replicate): R host threads then take batches off the
     one loader in turn and run them on R HIP streams -- forwards in flight fill each other's host waits and heads (round 6; bench.py measures
     +6 % for three 64-pair forwards in flight); the poses come back in pair-id order either way, bit-identical to the one-replica run.
+    losses: also RegTR.compute_loss(per_pair=True) of every pair (3DMatch-style pair sources: GT pose per pair, level-0 masks from
+    overlap.compute_overlap_masks at cfg.overlap_radius); the means over all pairs of all ranks (one extra all-reduce) are returned in
+    timing['losses'].  Without it the launches and outputs are those of a plain run.
     Returns, on every rank, (poses (n_total, 3, 4) float32 numpy ordered by pair id, pair ids, timing dict)."""
     import contextlib
     import itertools
@@ -604,7 +612,11 @@ def run_test(model, pairs, batch, device, logger=None, max_pairs=None, num_worke
     R = len(models)
     streams = [torch.cuda.Stream(device) for _ in range(R)] if (cuda and R > 1) else [None] * R
     it, turn, counter = iter(loader), threading.Lock(), itertools.count()
-    done, errs, fwd_ms = [], [], []
+    done, errs, fwd_ms, loss_done = [], [], [], []
+    if losses:
+        if any(m.cfg.get('dataset', '3dmatch') != '3dmatch' for m in models):
+            raise NotImplementedError('run_test(losses=True): ModelNet losses are not implemented (3DMatch-style pair sources only)')
+        from .overlap import compute_overlap_masks
 
     def work(r):
         try:
@@ -619,8 +631,18 @@ def run_test(model, pairs, batch, device, logger=None, max_pairs=None, num_worke
                             return
                         k = next(counter)
                     t_f = time.perf_counter()
-                    out = models[r]({'src_xyz': b['src_xyz'], 'tgt_xyz': b['tgt_xyz']})
+                    fb = {'src_xyz': b['src_xyz'], 'tgt_xyz': b['tgt_xyz']}
+                    out = models[r](fb)
                     fwd_ms.append(round((time.perf_counter() - t_f) * 1e3, 1))
+                    if losses:
+                        gp = b['gt_pose'] if 'gt_pose' in b else [i_['pose'] for i_ in b['items']]
+                        if any(g_ is None for g_ in gp):
+                            raise RuntimeError('run_test(losses=True): the pair source gives no ground-truth pose')
+                        pose = torch.from_numpy(np.stack([np.asarray(g_, dtype=np.float32)[:3] for g_ in gp])).to(device, non_blocking=True)
+                        sm, tm = compute_overlap_masks(b['src_xyz'], b['tgt_xyz'], pose, models[r].cfg.overlap_radius)
+                        lo = models[r].compute_loss(out, {'kpconv_meta': fb['kpconv_meta'], 'pose': pose, 'src_overlap': sm,
+                                                          'tgt_overlap': tm}, per_pair=True)
+                        loss_done.append((k, list(lo), torch.stack([v_.to(torch.float64) for v_ in lo.values()])))     # (keys, B)
                     done.append((k, out['pose'][-1], b['ids'] if 'ids' in b else [i_['idx'] for i_ in b['items']]))      # (B, 3, 4), stays on the device
         except BaseException as e:      # noqa: BLE001  (re-raised on the caller)
             errs.append(e)
@@ -647,6 +669,16 @@ def run_test(model, pairs, batch, device, logger=None, max_pairs=None, num_worke
     pose_t = torch.cat(poses).reshape(-1, 12) if poses else torch.zeros((0, 12), dtype=torch.float32, device=device)
     id_t = torch.tensor(ids, dtype=torch.int32, device=device)
     all_poses, all_ids = gather_poses(pose_t, id_t, n)
+    loss_means = None
+    if losses:
+        loss_done.sort(key=lambda d: d[0])
+        keys = loss_done[0][1] if loss_done else models[0].loss_keys()
+        per = torch.cat([d[2] for d in loss_done], dim=1) if loss_done else torch.zeros((len(keys), 0), dtype=torch.float64, device=device)
+        red = torch.cat([per.sum(dim=1), torch.tensor([float(per.shape[1])], dtype=torch.float64).to(device, non_blocking=True)])
+        if world > 1:
+            dist.all_reduce(red)                   # per-term sums and the pair count of every rank
+        red = red.cpu().numpy()
+        loss_means = {k_: float(red[j] / red[-1]) if red[-1] > 0 else float('nan') for j, k_ in enumerate(keys)}
     if device.type == 'cuda':
         torch.cuda.synchronize(device)
     elapsed = time.perf_counter() - t0
@@ -659,5 +691,7 @@ def run_test(model, pairs, batch, device, logger=None, max_pairs=None, num_worke
                            "(An f16 pair operand beyond 65504 is not the cause unless cfg.f16_range_check was switched off: RegTR.forward detects that "
                            "and re-runs the forward in fp32x3 arithmetic; compute_dtype: 'fp32x3' avoids the format altogether.)  Check the inputs "
                            'and the checkpoint for non-finite values.')
-    return poses_np, all_ids.cpu().numpy(), {'elapsed_s': elapsed, 'pairs': n, 'world': world,
-                                             'loader': getattr(loader_pool, 'last_timing', None), 'forward_ms': fwd_ms}
+    timing = {'elapsed_s': elapsed, 'pairs': n, 'world': world, 'loader': getattr(loader_pool, 'last_timing', None), 'forward_ms': fwd_ms}
+    if losses:
+        timing['losses'] = loss_means
+    return poses_np, all_ids.cpu().numpy(), timing

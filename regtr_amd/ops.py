@@ -595,3 +595,53 @@ def weighted_procrustes(kp, corr, logit, seg_off, n_pairs):
     check(_lib.lib().regtr_weighted_procrustes(ptr(kp), ptr(corr), ptr(logit), iptr(seg_off), n_pairs, N, Lyr, ptr(pose),
                                                context.current().status_ptr(), stream()), 'regtr_weighted_procrustes')
     return pose
+
+
+# ------------------------------------------------------------------------------------------------ losses (validation / test)
+def infonce(anc, pos_t, anc_xyz, pos_xyz, anc_seg_off, pos_seg_off, max_anc, r_p, r_n, anc_pose=None, rows=False):
+    """InfoNCE feature loss of packed, ragged pairs (regtr_infonce).  anc (N_anc, D) and pos_t (N_pos, D) row-strided views (pos_t: the
+    TRANSFORMED positives G W_sym), xyz (N, 3), seg_off (B+1,) int32 on the device, max_anc >= every pair's anchor count.
+    anc_pose (B, 12) float32 or None: applied to anc_xyz first.  Returns pair_out (B, 2) = (masked loss sum, mask count); with rows=True
+    also (row_loss, row_mask) (N_anc,).  Nothing here synchronises."""
+    L = _lib.lib()
+    n_anc, D = anc.shape
+    n_pos = pos_t.shape[0]
+    B = anc_seg_off.numel() - 1
+    dev = anc.device
+    out = torch.empty((B, 2), dtype=torch.float32, device=dev)
+    rl = torch.empty(n_anc, dtype=torch.float32, device=dev) if rows else None
+    rm = torch.empty(n_anc, dtype=torch.float32, device=dev) if rows else None
+    nb = L.regtr_infonce_ws_bytes(B, int(max_anc))
+    ws = _ws(max(nb, 1), dev)
+    lda = anc.stride(0) if n_anc > 1 else D
+    ldp = pos_t.stride(0) if n_pos > 1 else D
+    assert anc.stride(1) == 1 and pos_t.stride(1) == 1
+    check(L.regtr_infonce(raw(anc) if n_anc else None, lda, raw(pos_t) if n_pos else None, ldp, ptr(anc_xyz) if n_anc else None,
+                          ptr(pos_xyz) if n_pos else None, iptr(anc_seg_off), iptr(pos_seg_off), B, n_anc, n_pos, int(max_anc), D,
+                          float(r_p), float(r_n), ptr(anc_pose), ptr(out), ptr(rl), ptr(rm), bptr(ws), nb, stream()), 'regtr_infonce')
+    return (out, rl, rm) if rows else out
+
+
+def loss_terms(logit, gt_overlap, kp, warped, seg_off, pose):
+    """The O(N) loss terms of one layer (regtr_loss_terms): logit / gt_overlap (N,), kp / warped (N, 3) packed like RegTR.forward's
+    coarsest level (seg_off (2B+1,) int32: src clouds, then tgt clouds), pose (B, 3, 4) or (B, 4, 4) float32.  Returns (B, 5): BCE sum,
+    src sum w|err|_1, src sum w, tgt sum w|err|_1, tgt sum w."""
+    B = seg_off.numel() // 2
+    N = logit.shape[0]
+    pose = pose.contiguous()
+    out = torch.empty((B, 5), dtype=torch.float32, device=logit.device)
+    check(_lib.lib().regtr_loss_terms(ptr(logit) if N else None, ptr(gt_overlap) if N else None, ptr(kp) if N else None,
+                                      ptr(warped) if N else None, iptr(seg_off), B, N, ptr(pose), pose.shape[-2] * pose.shape[-1],
+                                      ptr(out), stream()), 'regtr_loss_terms')
+    return out
+
+
+def se3_transform(xyz, seg_off, pose):
+    """xyz (N, 3) packed clouds (seg_off (C+1,) int32), pose (C, 3, 4) or (C, 4, 4) float32 -> (N, 3): cloud c's points x' = R_c x + t_c,
+    rounded per operation (regtr_se3_transform)."""
+    n = xyz.shape[0]
+    pose = pose.contiguous()
+    out = torch.empty((n, 3), dtype=torch.float32, device=xyz.device)
+    check(_lib.lib().regtr_se3_transform(ptr(xyz) if n else None, iptr(seg_off), seg_off.numel() - 1, n, ptr(pose),
+                                         pose.shape[-2] * pose.shape[-1], ptr(out) if n else None, stream()), 'regtr_se3_transform')
+    return out

@@ -2,6 +2,7 @@
 
     compute_overlap(src, tgt, search_voxel_size)   /root/reference/src/utils/pointcloud.py:8-65
     compute_overlaps(batch)                        /root/reference/src/models/backbone_kpconv/kpconv.py:540-566
+    compute_overlap_masks(src, tgt, poses, r)      the level-0 masks of data_loaders/threedmatch.py:78-84, batched on the device
 
 Same signatures and return values as the reference functions; the radius matching runs on the cell-grid kernels of
 csrc/preprocess.hip (float64 distances over float32 coordinates, like open3d's KDTreeFlann on the widened points) and the
@@ -45,6 +46,32 @@ def compute_overlap(src, tgt, search_voxel_size, device=None):
     src_corr_is_mutual = np.logical_and(tgt_corr[src_corr] == np.arange(len(src_corr)), src_corr > 0)                    # :58-59
     src_tgt_corr = np.stack([np.nonzero(src_corr_is_mutual)[0], src_corr[src_corr_is_mutual]])
     return src_corr >= 0, tgt_corr >= 0, src_tgt_corr
+
+
+def _offsets(clouds, device):
+    off = [0]
+    for c in clouds:
+        off.append(off[-1] + int(c.shape[0]))
+    return torch.tensor(off, dtype=torch.int32).to(device, non_blocking=True)
+
+
+def compute_overlap_masks(src_list, tgt_list, poses, radius):
+    """Level-0 ground-truth masks of a batch, as ThreeDMatchDataset derives them per pair (threedmatch.py:78-84): has_corr_src /
+    has_corr_tgt of compute_overlap(se3_transform(pose, src), tgt, radius).  src_list / tgt_list: (B) float32 (N, 3) device clouds,
+    poses (B, 3, 4) or (B, 4, 4).  The src clouds are transformed on the device (ops.se3_transform) and one regtr_nearest_in_radius
+    runs each way over the packed clouds; no host round trip.  Returns (src_masks, tgt_masks): lists (B) of bool views."""
+    dev = src_list[0].device
+    with _lib.on_device(dev):
+        src = torch.cat([_dev_cloud(s, dev) for s in src_list], dim=0)
+        tgt = torch.cat([_dev_cloud(t, dev) for t in tgt_list], dim=0)
+        s_off, t_off = _offsets(src_list, dev), _offsets(tgt_list, dev)
+        poses = poses.to(device=dev, dtype=torch.float32, non_blocking=True)
+        src_w = ops.se3_transform(src, s_off, poses)
+        tgt_corr = nearest_in_radius(tgt, t_off, src_w, s_off, radius)         # pointcloud.py:44-49
+        src_corr = nearest_in_radius(src_w, s_off, tgt, t_off, radius)         # :50-55
+        src_mask, tgt_mask = src_corr >= 0, tgt_corr >= 0
+    split = lambda m, cl: list(torch.split(m, [int(c.shape[0]) for c in cl]))
+    return split(src_mask, src_list), split(tgt_mask, tgt_list)
 
 
 def compute_overlaps(batch):

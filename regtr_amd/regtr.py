@@ -3,8 +3,9 @@
 Drop-in for the reference's `RegTR` (/root/reference/src/models/regtr.py:22-235): same constructor (`RegTR(cfg)`),
 same `forward(batch) -> dict` contract (input lists batch['src_xyz'] / batch['tgt_xyz'], side effect
 batch['kpconv_meta'], output keys of regtr.py:218-235), same `state_dict` names and shapes, so a reference checkpoint
-loads with `load_state_dict(state['state_dict'])` (demo.py:165).  Training-only members (compute_loss, criteria) are
-not implemented; their parameters (`feature_criterion.W`, feature_loss.py:261) are kept so strict loading works.
+loads with `load_state_dict(state['state_dict'])` (demo.py:165).  `compute_loss(pred, batch)` gives the reference's validation /
+test losses (regtr.py:237-294) without gradients: the InfoNCE feature terms on regtr_infonce, the overlap and correspondence terms on
+regtr_loss_terms.  Training (autograd, optimiser) is not implemented.
 
 The forward enqueues every stage on the current HIP stream with ONE host synchronisation (the data-dependent level
 sizes after preprocessing): preprocess -> KPConv encoder -> feat_proj -> 6 cross-encoder layers on packed tokens ->
@@ -16,7 +17,7 @@ import threading
 import torch
 import torch.nn as nn
 
-from . import _lib, context, devflags, ops
+from . import _lib, context, devflags, ops, overlap
 from .config import as_config
 from .kpconv import KPFEncoder, PreprocessorGPU, _prepared
 from .transformer import TransformerCrossEncoder, TransformerCrossEncoderLayer
@@ -99,11 +100,41 @@ def _throttled(n):
 
 
 class _LossParams(nn.Module):
-    """Holds InfoNCELossFull.W (feature_loss.py:261) so reference checkpoints load strictly; never used at inference."""
+    """Holds InfoNCELossFull.W (feature_loss.py:261): loaded strictly from reference checkpoints, read by RegTR.compute_loss."""
 
     def __init__(self, d_embed):
         super().__init__()
         self.W = nn.Parameter(torch.zeros(d_embed, d_embed), requires_grad=False)
+
+
+def loss_weight_dict(cfg):
+    """regtr.py:90-95: {'overlap_i', 'feature_i', 'corr_i', 'feature_un'} -> weight."""
+    wd = {}
+    for k in ['overlap', 'feature', 'corr']:
+        for i in cfg.get(f'{k}_loss_on', [cfg.num_encoder_layers - 1]):
+            wd[f'{k}_{i}'] = cfg.get(f'wt_{k}')
+    wd['feature_un'] = cfg.wt_feature_un
+    return wd
+
+
+def _packed_rows(views):
+    """Row views (n_k, ...) of one tensor, one per cloud, as ONE (sum n_k, ...) tensor: a view when they lie back to back in memory
+    (what RegTR.forward returns), else a copy."""
+    v0 = views[0]
+    n = sum(int(v.shape[0]) for v in views)
+    row = v0.stride(0) if v0.dim() else 1
+    at = v0.data_ptr()
+    base = v0.untyped_storage().data_ptr()
+    adjacent = all(v.stride() == v0.stride() and v.dtype == v0.dtype and v.untyped_storage().data_ptr() == base for v in views)
+    for v in views:
+        if not adjacent:
+            break
+        if v.shape[0] and v.data_ptr() != at:
+            adjacent = False
+        at += int(v.shape[0]) * row * v.element_size()
+    if adjacent:
+        return v0.as_strided((n,) + tuple(v0.shape[1:]), v0.stride(), v0.storage_offset())
+    return torch.cat([v.contiguous() for v in views], dim=0)
 
 
 class RegTR(nn.Module):
@@ -156,6 +187,7 @@ class RegTR(nn.Module):
         if cfg.get('feature_loss_type', 'infonce') == 'infonce':                  # :79-81
             self.feature_criterion = _LossParams(cfg.d_embed)
             self.feature_criterion_un = _LossParams(cfg.d_embed)
+        self.weight_dict = loss_weight_dict(cfg) if 'wt_feature_un' in cfg else None        # :90-95 (configs with a losses section)
         self._cache = {}
         self.last_timings = None
         self._params_checked = False
@@ -362,3 +394,79 @@ class RegTR(nn.Module):
             'pose': pose,
         }
         return outputs
+
+    # ------------------------------------------------------------------------------------------ losses (validation / test, no gradients)
+    def _w_sym(self, crit):
+        """InfoNCELossFull's W_sym = triu(W) + triu(W)^T (feature_loss.py:295-296; the diagonal counts twice), once per weight version."""
+        return _prepared(self._cache, ('w_sym', id(crit)), crit.W, lambda w: (torch.triu(w) + torch.triu(w).t()).contiguous())
+
+    def _infonce(self, crit, feats, xyz, seg_c, lens, B, pose12, r_p, r_n):
+        """Per-pair (masked loss sum, mask count) of InfoNCELossFull.forward on packed tokens (src clouds, then tgt clouds):
+        anchors = the src tokens with the GT pose applied to their coordinates, positives = the tgt tokens."""
+        n_src = sum(lens[:B])
+        pos_t = torch.empty_like(feats)                 # rows [n_src, N) get G W_sym; the src rows are never read
+        ops.gemm(feats[n_src:], self._w_sym(crit), out=pos_t[n_src:])                         # exact-f32 MFMA GEMM
+        return ops.infonce(feats, pos_t, xyz, xyz, seg_c[:B + 1], seg_c[B:], max(lens[:B], default=0), r_p, r_n, anc_pose=pose12)
+
+    def loss_keys(self):
+        """The keys of compute_loss's result, in its order."""
+        cfg = self.cfg
+        return ([f'overlap_{i}' for i in cfg.overlap_loss_on] + [f'feature_{i}' for i in cfg.feature_loss_on] + ['feature_un'] +
+                [f'corr_{i}' for i in cfg.corr_loss_on] + ['total'])
+
+    @torch.no_grad()
+    def compute_loss(self, pred, batch, per_pair=False):
+        """regtr.py:237-294 without gradients: {'overlap_i', 'feature_i', 'feature_un', 'corr_i', 'total'} -> 0-dim device tensors,
+        or (B,) tensors of every term per pair with per_pair=True (what the reference computes with one pair per batch).
+        batch: 'pose' (B, 3, 4) or (B, 4, 4), 'src_overlap' / 'tgt_overlap' level-0 masks, 'kpconv_meta' from the preceding forward
+        (batch['overlap_pyr'] is set as the reference does).  Reference semantics kept, NaN included: a pair without an anchor inside
+        r_p gives 0 / 0 in its feature term, and the total is then NaN.  Float32-grade whatever cfg.compute_dtype; no host wait."""
+        cfg = self.cfg
+        if cfg.get('feature_loss_type', 'infonce') != 'infonce':
+            raise NotImplementedError(f"compute_loss: feature_loss_type {cfg.feature_loss_type!r} (CircleLossFull) is not implemented")
+        missing = [k for k in ('r_p', 'r_n', 'wt_overlap', 'wt_feature', 'wt_feature_un', 'wt_corr') if k not in cfg]
+        if missing:
+            raise KeyError(f'compute_loss needs the losses section of the config (regtr_amd/conf/*.yaml); missing: {missing}')
+        meta = batch['kpconv_meta']
+        B = len(pred['src_kp'])
+        dev = pred['src_kp'][0].device
+        lens = [int(n) for n in meta['_lens_host'][-1]]
+        N = sum(lens)
+        seg_c = meta['_seg_off'][-1]
+        wd = loss_weight_dict(cfg)
+        with context.forward(dev, f16_pair=False, status=None):
+            pose = batch['pose']
+            if isinstance(pose, (list, tuple)):
+                pose = torch.stack(list(pose))
+            pose = pose.to(device=dev, dtype=torch.float32).contiguous()
+            pose12 = pose[:, :3, :].reshape(B, 12).contiguous()
+            batch['overlap_pyr'] = overlap.compute_overlaps(batch)                               # :242-245
+            gt_c = batch['overlap_pyr'][f'pyr_{len(meta["points"]) - 1}']
+            xyz = _packed_rows(list(pred['src_kp']) + list(pred['tgt_kp']))
+            terms = {}
+            for i in sorted(set(cfg.overlap_loss_on) | set(cfg.corr_loss_on)):
+                logit = _packed_rows([o[i] for o in pred['src_overlap']] + [o[i] for o in pred['tgt_overlap']]).reshape(N)
+                warped = _packed_rows([w[i] for w in pred['src_kp_warped']] + [w[i] for w in pred['tgt_kp_warped']])
+                terms[i] = ops.loss_terms(logit.contiguous(), gt_c, xyz, warped.contiguous(), seg_c, pose)
+            n_pair = torch.tensor([lens[b] + lens[B + b] for b in range(B)], dtype=torch.float32).to(dev, non_blocking=True) \
+                if per_pair else None
+            losses = {}
+            for i in cfg.overlap_loss_on:                                                         # :252-255 (one mean over all points)
+                t = terms[i][:, 0]
+                losses[f'overlap_{i}'] = t / n_pair if per_pair else t.sum() / N
+            feat_sets = [(f'feature_{i}', self.feature_criterion,
+                          _packed_rows([f[i] for f in pred['src_feat']] + [f[i] for f in pred['tgt_feat']])) for i in cfg.feature_loss_on]
+            feat_sets.append(('feature_un', self.feature_criterion_un, _packed_rows(list(pred['src_feat_un']) + list(pred['tgt_feat_un']))))
+            for key, crit, feats in feat_sets:                                                    # :258-269, feature_loss.py:303-314
+                out = self._infonce(crit, feats, xyz, seg_c, lens, B, pose12, cfg.r_p, cfg.r_n)
+                per = out[:, 0] / out[:, 1]
+                losses[key] = per if per_pair else per.mean()
+            for i in cfg.corr_loss_on:                                                            # :271-285, corr_loss.py:18-40
+                t = terms[i]
+                if per_pair:
+                    losses[f'corr_{i}'] = t[:, 1] / t[:, 2].clamp_min(1e-6) + t[:, 3] / t[:, 4].clamp_min(1e-6)
+                else:
+                    s = t.sum(0)
+                    losses[f'corr_{i}'] = s[1] / s[2].clamp_min(1e-6) + s[3] / s[4].clamp_min(1e-6)
+            losses['total'] = torch.sum(torch.stack([losses[k] * wd[k] for k in losses]), dim=0)   # :292-293
+        return losses

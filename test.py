@@ -7,7 +7,7 @@
 Runs the MI355X-native RegTR inference path over the benchmark's pairs and writes `<log>/<benchmark>/<scene>/est.log`
 (3DMatch / 3DLoMatch) or `<log>/pred_transforms.npy` (ModelNet / ModelLoNet) in the reference's formats
 (models/generic_reg_model.py:194-195, 260-281), which the reference's evaluation scripts read unchanged.
-Inference only: no loss, no tensorboard.  Extra flags: --batch (pairs per forward), --data_root, --synthetic N
+Inference only: no training, no tensorboard; --losses adds the reference's test losses ([Losses] line).  Extra flags: --batch (pairs per forward), --data_root, --synthetic N
 (N deterministic synthetic pairs instead of the dataset files), --max_pairs, --preprocessor (cpu | gpu: which reference preprocessor's semantics;
 --neighbor_order / --voxel_key set its two rules one by one), --benchmark_dir (gt.log / gt.info folder: the
 Predator registration-recall table of benchmark/benchmark_predator.py is then printed, computed in process).
@@ -55,6 +55,9 @@ parser.add_argument('--materialize', type=str, default=None,
 parser.add_argument('--distinct', type=int, default=0, help='with --materialize: generate only this many different pairs (pair i = pair i %% distinct; one file pair per pair all the same)')
 parser.add_argument('--overlap', type=str, default=None, help="synthetic pairs: 'lomatch' = 10-30 %% overlap (3DLoMatch-like)")
 parser.add_argument('--max_pairs', type=int, default=None)
+parser.add_argument('--losses', action='store_true',
+                    help='also compute the reference\'s test losses (RegTR.compute_loss per pair on GT overlap masks) and log a [Losses] line; '
+                         '3DMatch-style pair sources only')
 parser.add_argument('--warmup_points', type=int, default=24000, help='points per cloud of the warm-up batch (larger than the data so that later batches fit the allocator\'s blocks)')
 parser.add_argument('--alloc_conf', type=str, default='', help='torch caching-allocator settings for the run (e.g. roundup_power2_divisions:8)')
 parser.add_argument('--reserve_gb', type=float, default=0, help='GiB reserved once and returned to the caching allocator\'s pool before the run (default 0 = off; measured: no effect on the forward-time spikes, which were GIL hand-offs, not hipMalloc)')
@@ -137,6 +140,10 @@ def main():
         assert opt.benchmark in ['ModelNet', 'ModelLoNet'], "Benchmark for modelnet dataset must be one of ['ModelNet', 'ModelLoNet']"
         cfg.partial = [0.7, 0.7] if opt.benchmark == 'ModelNet' else [0.5, 0.5]
 
+    if opt.losses and cfg.dataset != '3dmatch':
+        logger.error('--losses: ModelNet losses are not implemented (3DMatch-style pair sources only, synthetic included)')
+        sys.exit(-4)
+
     if not torch.cuda.is_available():
         logger.error('regtr_amd runs on an MI355X (HIP) device only; there is no CPU path')
         sys.exit(-3)
@@ -217,7 +224,8 @@ def main():
         del wb
         logger.info(f'warm-up forward ({opt.batch} synthetic pairs, untimed): {time.perf_counter() - t_w:.2f} s')
     t_run = time.perf_counter()
-    poses, ids, timing = harness.run_test(models if len(models) > 1 else model, pairs, opt.batch, device, logger, opt.max_pairs, loader_pool=pool)
+    poses, ids, timing = harness.run_test(models if len(models) > 1 else model, pairs, opt.batch, device, logger, opt.max_pairs, loader_pool=pool,
+                                         losses=opt.losses)
     if pool is not None:
         logger.info(f'loader: {timing["loader"]}; forward ms (host clock, incl. the end-of-forward status wait): {timing["forward_ms"]}')
         pool.close()
@@ -263,6 +271,9 @@ def main():
         ok = np.logical_and(rot < cfg.get('reg_success_thresh_rot', 10), trans < cfg.get('reg_success_thresh_trans', 0.1))
         logger.info(f'[Metrics] rot_err_deg_final: {rot.mean():.4f}, trans_err_final: {trans.mean():.4f}, reg_success_final: {ok.mean():.4f} '
                     f'({len(ids)} pairs, {timing["pairs"] / timing["elapsed_s"]:.1f} pairs/s on {timing["world"]} GPU(s))')
+        if opt.losses:
+            lm = timing['losses']
+            logger.info('[Losses] ' + ', '.join(f'{k}: {v:.6g}' for k, v in lm.items()) + f' (mean over {len(ids)} pairs)')
     if world > 1 or 'RANK' in os.environ:
         import torch.distributed as dist
         dist.barrier()
