@@ -246,7 +246,8 @@ int regtr_gemm_stream(const float* A, int lda, const void* planes, float* C, int
  *   K1 = 16, K2 = 0, N = 64: the first block (:590-646), A1 = the Cin = 1 gather's WF rows at ld_wf = 16, A1' = A1 / row_div1[row]
  *     (the neighbour count, :411), a1_stats / A2 / W2 NULL -- replaces contraction GEMM + statistics + regtr_instnorm_apply.
  * W1 [K1,N] / W2 [K2,N] float32 row-major, seg_off [n_clouds+1], max_len = longest cloud, tile_info = regtr_tile_segments(seg_off,
- * n_clouds, M, 256, ..).  out_stats (optional) [1 or 2,n_clouds,N,2] receives the (mean, rstd) of the products. */
+ * n_clouds, M, 256, ..).  out_stats (optional) [1 or 2,n_clouds,N,2] receives the (mean, rstd) of the products; an empty cloud gets
+ * (0, 0), as regtr_instnorm_stats reports it (M = 0 or max_len = 0 launches nothing and writes nothing). */
 int regtr_block_tail_supported(int M, int N, int K1, int K2);
 size_t regtr_block_tail_ws_bytes(int n_clouds, int max_len, int N, int K1, int K2);
 int regtr_block_tail(const float* A1, int lda1, const float* a1_stats, float a1_slope, const float* row_div1, const float* A2, int lda2,

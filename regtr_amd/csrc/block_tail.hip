@@ -274,7 +274,13 @@ __global__ void __launch_bounds__(256) k_tail_prepare(const double* __restrict__
     __shared__ double2 quad[256];
     const int cloud = blockIdx.x, col0 = blockIdx.y * 64;
     const int n = seg_off[cloud + 1] - seg_off[cloud];
-    if (n <= 0) return;                                              // no row of this cloud reaches k_tail_strip
+    if (n <= 0) {                                                    // no row of this cloud reaches k_tail_strip; its statistics are
+        if (out_stats && threadIdx.x < 64) {                         // (0, 0), as regtr_instnorm_stats reports an empty cloud
+            out_stats[(size_t)cloud * N + col0 + threadIdx.x] = make_float2(0.f, 0.f);
+            if (K2 > 0) out_stats[((size_t)n_clouds + cloud) * N + col0 + threadIdx.x] = make_float2(0.f, 0.f);
+        }
+        return;
+    }
     const int n_valid = (n + MO_ROWS_WG - 1) / MO_ROWS_WG;
     bt_prepare_source<K1>(part1, n_chunks, n_valid, n, cloud, W1, N, col0, eps, cov, quad, planes1, mean1, out_stats, pivot1);
     if constexpr (K2 > 0)
@@ -537,7 +543,7 @@ size_t regtr_block_tail_ws_bytes(int n_clouds, int max_len, int N, int K1, int K
 //   A1 [M, K1] (lda1); A1' = LeakyReLU_a1_slope(InstanceNorm(A1)) by a1_stats [n_clouds, K1, 2] when given, else A1 / row_div1[row]
 //   (row_div1 optional [M]);  A2 [M, K2] (lda2) and W2 only when K2 > 0;  W1 [K1, N], W2 [K2, N] float32 row-major (k, n)
 //   seg_off [n_clouds + 1] cloud offsets of the rows, max_len = longest cloud, tile_info = regtr_tile_segments(seg_off, .., M, 256, ..)
-//   out_stats (optional) [1 or 2, n_clouds, N, 2]: (mean, rstd) of the products, as InstanceNorm would report them
+//   out_stats (optional) [1 or 2, n_clouds, N, 2]: (mean, rstd) of the products, as InstanceNorm would report them ((0, 0) for an empty cloud)
 int regtr_block_tail(const float* A1, int lda1, const float* a1_stats, float a1_slope, const float* row_div1, const float* A2, int lda2,
                      const float* W1, const float* W2, const int* seg_off, int n_clouds, int max_len, const void* tile_info,
                      int M, int N, int K1, int K2, float eps, float slope, float* Y, int ldy, void* ws, size_t ws_bytes,

@@ -5,7 +5,9 @@ drives it, route_stream csrc/gemm_stream.hip (sg_cols_per_wg, the SG_L2 / SG_L3 
 tests/test_dispatch_routes.py checks the mirror against the host-only plan queries of the library and asserts that the GPU cases
 (tests/test_gpu_dispatch.py, tests/test_gpu_ops.py) reach every instantiation listed in X3_KERNELS / STREAM_KERNELS / MHA_KERNELS.  route_gather / route_maxpool mirror csrc/kpconv.hip
 (regtr_kpconv_gather with the flag decision of ops.kpconv, regtr_maxpool_gather); their cases are in tests/test_gpu_gather.py and their
-universes GATHER_KERNELS / MAXPOOL_KERNELS.
+universes GATHER_KERNELS / MAXPOOL_KERNELS.  route_instnorm / route_finalize_tiles mirror csrc/norm.hip (in_rows, the finalize split at
+n_clouds C = 4096) and route_block_tail csrc/block_tail.hip; their cases are in tests/test_gpu_norm.py and their universes NORM_KERNELS
+((C, rows) pairs), FINALIZE_KERNELS and TAIL_KERNELS.
 
 A route is '+'-joined kernel names: the product kernel, then for split-K its reduction ('reduce', 'reduce_stats/vec' or
 'reduce_stats/novec'), then 'stats_pass' when ops.gemm hands C to regtr_instnorm_stats for the statistics instead (split-K with N / 4 not a power of
@@ -257,3 +259,85 @@ def route_maxpool(ns, C, aligned16=True):
 GATHER_KERNELS = ({'c1', 'c1p<2>', 'c1p<3>', 'c1p<4>', 'lq<16>', 'lq<32>', 'lq<64>', 'rowsum', 'rowsum/stats'}
                   | {f"mfma<{J},{V}{p}>" for J in (10, 13, 16) for V in (2, 4) for p in ('', ',pre')})
 MAXPOOL_KERNELS = {f'{k}<{qw}>' for k in ('mp_buf', 'mp') for qw in (4, 2, 1)}
+
+
+# ------------------------------------------------------------------------------------------------ InstanceNorm, block tail (csrc/norm.hip, csrc/block_tail.hip)
+IN_ROWS = 128
+NORM_WIDTHS = (4, 8, 16, 32, 64, 128, 256, 512, 1024)                 # C / 4 float4 columns a power of two <= 256
+
+
+def in_rows(n_clouds, max_len, C):
+    """in_rows: rows of one cloud per workgroup of k_instnorm_partial / k_instnorm_apply, halved from 128 while the launch is small."""
+    TR = 256 // (C >> 2)
+    rows = IN_ROWS
+    while rows > 4 * TR and rows > 8 and cdiv(max(max_len, 1), rows) * n_clouds < 1024:
+        rows >>= 1
+    return rows
+
+
+def instnorm_ws_bytes(n_clouds, max_len, C):                            # regtr_instnorm_ws_bytes
+    if n_clouds < 1 or C not in NORM_WIDTHS:
+        return 256
+    return cdiv(max(max_len, 1), in_rows(n_clouds, max_len, C)) * n_clouds * C * 16 + 256
+
+
+def route_instnorm(n_clouds, max_len, C, apply=False):
+    """regtr_instnorm_stats ('in_partial/r<rows>+in_finalize') or regtr_instnorm_apply ('in_apply/r<rows>'); 'none' when max_len = 0
+    launches nothing, 'refused' for a width the kernels do not take.  The kernels are not templated: the rows are the launch regime."""
+    if n_clouds < 1 or C not in NORM_WIDTHS or max_len < 0:
+        return 'refused'
+    if max_len == 0:
+        return 'none'
+    r = in_rows(n_clouds, max_len, C)
+    return f'in_apply/r{r}' if apply else f'in_partial/r{r}+in_finalize'
+
+
+def route_finalize_tiles(n_clouds, C):
+    """regtr_instnorm_finalize_tiles: a wave per (cloud, channel) while n_clouds C <= 4096, else a thread per channel in blocks of 64 / 128 / 256."""
+    if n_clouds * C <= 4096:
+        return 'fin_wave'
+    return f"fin_thread<{256 if C >= 256 else (128 if C >= 128 else 64)}>"
+
+
+def _norm_kernels():
+    """Every reachable (C, rows): rows halves from 128 while rows > 4 TR and rows > 8 (and the launch is small), TR = 1024 / C."""
+    out = set()
+    for C in NORM_WIDTHS:
+        r = IN_ROWS
+        out.add((C, r))
+        while r > 4 * (1024 // C) and r > 8:
+            r >>= 1
+            out.add((C, r))
+    return out
+
+
+def block_tail_supported(M, N, K1, K2):                                 # regtr_block_tail_supported
+    return M >= 0 and ((K1, K2, N) in ((32, 64, 128), (16, 0, 64)))
+
+
+def block_tail_ws_bytes(n_clouds, max_len, N, K1, K2):                  # regtr_block_tail_ws_bytes
+    if n_clouds < 1 or not block_tail_supported(0, N, K1, K2):
+        return 0
+
+    def al(b):
+        return (b + 255) & ~255
+    nc = cdiv(max(max_len, 1), 2048)
+    return (al(n_clouds * nc * (K1 * K1 + K1) * 8) + al(n_clouds * nc * (K2 * K2 + K2) * 8) + al(n_clouds * 3 * N * K1 * 2)
+            + al(n_clouds * 3 * N * K2 * 2) + 2 * (al(n_clouds * K1 * 4) + al(n_clouds * K2 * 4)))
+
+
+def route_block_tail(M, N, K1, K2):
+    """regtr_block_tail's four launches: k_moments<KC, INFOLD, ROWDIV> per source, k_tail_prepare<K1, K2>, k_tail_strip<KT1, KT2, NT, NPASS,
+    FOLD1>; 'none' for M = 0, 'refused' for an unserved shape."""
+    if not block_tail_supported(M, N, K1, K2):
+        return 'refused'
+    if M == 0:
+        return 'none'
+    if K2:
+        return 'moments<1,1,0>+moments<2,0,0>+prepare<32,64>+tail_strip<2,4,2,2,1>'
+    return 'moments<1,0,1>+prepare<16,0>+tail_strip<1,0,2,1,0>'
+
+
+NORM_KERNELS = _norm_kernels()
+FINALIZE_KERNELS = {'fin_wave', 'fin_thread<64>', 'fin_thread<128>', 'fin_thread<256>'}
+TAIL_KERNELS = set().union(*(set(route_block_tail(1, N, K1, K2).split('+')) for N, K1, K2 in ((128, 32, 64), (64, 16, 0))))

@@ -1,5 +1,5 @@
-"""CPU: tests/dispatch.py restates the GEMM / attention / KPConv gather / max-pool dispatchers faithfully, and the GPU cases reach every
-instantiation they can launch.
+"""CPU: tests/dispatch.py restates the GEMM / attention / KPConv gather / max-pool / InstanceNorm / block-tail dispatchers faithfully, and
+the GPU cases reach every instantiation they can launch.
 
 The mirror is checked against the plan queries libregtr_hip.so exports (host-only: no GPU needed); the coverage gate lists every
 instantiation of the launch ladders (dispatch.X3_KERNELS / STREAM_KERNELS / MHA_KERNELS / GATHER_KERNELS / MAXPOOL_KERNELS) and fails when
@@ -207,3 +207,95 @@ def test_gather_and_maxpool_edges_are_reached():
     assert 4 in Cs and max(Cs) >= 1024 and {dispatch.route_maxpool(3001, C) for C in Cs if C % 16} == {'mp_buf<4>', 'mp_buf<2>', 'mp_buf<1>'}
     big = _params(gg.test_maxpool_predicated_at_4_gib, ['C', 'ns'])
     assert all(ns * C * 4 == 1 << 32 for C, ns in big) and {dispatch.route_maxpool(ns, C) for C, ns in big} == {'mp<4>', 'mp<2>', 'mp<1>'}
+
+
+# ------------------------------------------------------------------------------------------------ InstanceNorm, finalize, block tail, strip GEMM
+def test_instnorm_rows_mirror_matches_library():
+    """in_rows (the rows per workgroup of the InstanceNorm statistics and apply launches) through the library's host-only workspace query:
+    cdiv(max_len, rows) n_clouds C 16 + 256 bytes, and 256 for a width the kernels refuse."""
+    from regtr_amd import _lib
+    L = _lib.lib()
+    n = 0
+    for nc, ml, C in itertools.product([1, 2, 3, 8, 9, 70, 127, 128, 129, 384, 1023, 1024, 1025, 4000],
+                                       [0, 1, 7, 8, 9, 63, 64, 65, 127, 128, 129, 255, 256, 1000, 1024, 4097, 20000, 131072],
+                                       dispatch.NORM_WIDTHS + (12, 2048, 0)):
+        assert L.regtr_instnorm_ws_bytes(nc, ml, C) == dispatch.instnorm_ws_bytes(nc, ml, C), (nc, ml, C)
+        n += C in dispatch.NORM_WIDTHS
+    assert n > 2000
+    assert all(L.regtr_instnorm_ws_bytes(4, 100, C) == 256 for C in (12, 2048, 0, 6, 1028))
+    assert dispatch.route_instnorm(4, 100, 12) == 'refused' and dispatch.route_instnorm(4, 0, 64) == 'none'
+
+
+def test_block_tail_mirror_matches_library():
+    from regtr_amd import _lib
+    L = _lib.lib()
+    for M, N, K1, K2 in itertools.product([0, 1, 300, 131072], [32, 64, 128, 256], [0, 16, 32, 64], [0, 16, 32, 64]):
+        r = dispatch.route_block_tail(M, N, K1, K2)
+        assert bool(L.regtr_block_tail_supported(M, N, K1, K2)) == (r != 'refused'), (M, N, K1, K2)
+        for nc, ml in itertools.product([1, 2, 70, 384], [0, 1, 2047, 2048, 2049, 70000]):
+            assert L.regtr_block_tail_ws_bytes(nc, ml, N, K1, K2) == dispatch.block_tail_ws_bytes(nc, ml, N, K1, K2), (nc, ml, N, K1, K2)
+    assert dispatch.route_block_tail(5, 128, 32, 64).count('+') == 3 and dispatch.route_block_tail(5, 64, 16, 0).count('+') == 2
+
+
+def test_every_instnorm_regime_is_reached():
+    """The statistics cases reach every reachable (C, rows) pair of in_rows; the apply cases reach the refusal widths' neighbours (C = 512 /
+    1024) and the smallest rows of a small launch."""
+    from tests import test_gpu_norm as gn
+    reached = set()
+    for C, kind, rows in _params(gn.test_instnorm_stats_vs_fp64, 'C kind rows'.split()):
+        lens = gn.case_lens(C, kind, rows)
+        r = dispatch.in_rows(len(lens), max(lens), C)
+        assert r == rows and dispatch.route_instnorm(len(lens), max(lens), C) == f'in_partial/r{r}+in_finalize'
+        assert 0 in lens and 1 in lens, (C, kind, rows)
+        reached.add((C, r))
+    assert reached == dispatch.NORM_KERNELS, sorted(dispatch.NORM_KERNELS - reached)
+    many = {C for C, kind, _ in _params(gn.test_instnorm_stats_vs_fp64, 'C kind rows'.split()) if kind == 'many'}
+    assert many == set(dispatch.NORM_WIDTHS)
+    applied = {(C, dispatch.in_rows(len(lens), max(lens), C)) for C, lens in _params(gn.test_instnorm_apply_vs_fp64, ['C', 'lens'])}
+    assert {C for C, _ in applied} >= {4, 64, 256, 512, 1024} and (1024, 8) in applied
+    combos = {c for C, _ in _params(gn.test_instnorm_apply_vs_fp64, ['C', 'lens']) for c in gn.apply_combos(C)}
+    assert len(combos) == 2 * 3 * 2 * 2 * 3
+
+
+def test_every_finalize_form_is_reached():
+    """Both finalize kernels, on either side of n_clouds C = 4096 and at it, all three thread-form block sizes, tile_rows 1 / 64 / 128 / 256,
+    clouds over one to 300 tiles, starting mid-tile, and empty clouds."""
+    from tests import test_gpu_norm as gn
+    routes, sides, spans, mid, empty = set(), set(), set(), False, False
+    for C, T, lens in _params(gn.test_instnorm_finalize_tiles_vs_fp64, 'C tile_rows lens'.split()):
+        routes.add(dispatch.route_finalize_tiles(len(lens), C))
+        sides.add(len(lens) * C - 4096)
+        off = list(itertools.accumulate(lens, initial=0))
+        for b, n in enumerate(lens):
+            if n:
+                spans.add((off[b + 1] - 1) // T - off[b] // T + 1)
+                mid |= off[b] % T != 0
+            empty |= n == 0
+    assert routes == dispatch.FINALIZE_KERNELS
+    assert 0 in sides and any(s < 0 for s in sides) and any(s > 0 for s in sides)
+    assert {T for _, T, _ in _params(gn.test_instnorm_finalize_tiles_vs_fp64, 'C tile_rows lens'.split())} == {1, 64, 128, 256}
+    assert 1 in spans and max(spans) >= 300 and mid and empty
+
+
+def test_every_tail_instantiation_is_reached():
+    """Both block-tail forms, on clouds at the 512-row wave and 2048-row chunk edges of k_moments, one-row and empty clouds, many clouds per
+    256-row tile; and every strip GEMM instantiation from the float64 strip test as well."""
+    from tests import test_gpu_norm as gn
+    from tests import test_gpu_ops
+    routes = []
+    for (lens,) in _params(gn.test_block_tail_vs_fp64, ['lens']):
+        routes.append(dispatch.route_block_tail(sum(lens), 128, 32, 64))
+    for (lens,) in _params(gn.test_first_block_direct_vs_fp64, ['lens']):
+        routes.append(dispatch.route_block_tail(sum(lens), 64, 16, 0))
+    assert len(_params(gn.test_first_block_kpconv_vs_fp64, ['records'])) == 2
+    _gate(dispatch.TAIL_KERNELS, routes)
+    all_lens = [n for (lens,) in _params(gn.test_block_tail_vs_fp64, ['lens']) for n in lens]
+    assert {0, 1, 511, 512, 513, 2047, 2048, 2049} <= set(all_lens) and any(n > 4096 for n in all_lens)
+    assert any(len(lens) >= 64 and max(lens) <= 4 for (lens,) in _params(gn.test_block_tail_vs_fp64, ['lens']))
+    assert [1] in [lens for (lens,) in _params(gn.test_block_tail_vs_fp64, ['lens'])]
+    routes = []
+    for li, K, N in _params(gn.test_gemm_stream_vs_fp64, ['li', 'K', 'N']):
+        M = sum(test_gpu_ops.STREAM_LENS[li])
+        routes += [dispatch.route_stream(M, N, K, fold) for fold in ((False, True) if K <= 64 else (False,))]
+    _gate(dispatch.STREAM_KERNELS, routes)
+    assert {li for li, _, _ in _params(gn.test_gemm_stream_vs_fp64, ['li', 'K', 'N'])} == set(range(len(test_gpu_ops.STREAM_LENS)))
