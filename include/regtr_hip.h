@@ -38,6 +38,9 @@
  *   regtr_infonce             InfoNCELossFull.compute_infonce     models/losses/feature_loss.py:281-314
  *   regtr_se3_transform       se3_transform (GT overlap masks)    data_loaders/threedmatch.py:78-84
  *   regtr_loss_terms          overlap BCE + CorrCriterion sums    models/regtr.py:250-285, models/losses/corr_loss.py:18-40
+ *   regtr_infonce_rows / _bwd InfoNCELossFull forward + backward  models/losses/feature_loss.py:246-314
+ *   regtr_gemm_tn             dW of InfoNCELossFull (G^T dP')     models/losses/feature_loss.py:295-297
+ *   regtr_corr_l1_bwd         CorrCriterion('mae') backward       models/losses/corr_loss.py:24-37
  */
 #ifndef REGTR_HIP_H
 #define REGTR_HIP_H
@@ -396,6 +399,46 @@ int regtr_se3_transform(const float* xyz, const int* seg_off, int n_clouds, int 
 
 int regtr_loss_terms(const float* logit, const float* gt_overlap, const float* kp, const float* warped, const int* seg_off,
                      int n_pairs, int n_total, const float* pose, int pose_stride, float* out, void* stream);
+
+
+/* ---- training-loss backward (regtr_amd/losses.py: the InfoNCELossFull / CorrCriterion drop-ins) ------------------------------------ */
+
+/* regtr_infonce with the per-row decisions the backward reuses: besides regtr_infonce's outputs (row_loss may be NULL, row_mask may
+ * not), row_lse [n_anc] = the logsumexp over the allowed set and row_idx [n_anc] = j*_i, the packed positive index of the argmin
+ * (-1 and NaN when the pair has no targets).  pair_out, row_loss and row_mask are bit-identical to regtr_infonce's.  Refused like
+ * regtr_infonce, and when n_anc > 0 with row_mask, row_lse or row_idx NULL. */
+int regtr_infonce_rows(const float* anc, int ld_anc, const float* pos, int ld_pos, const float* anc_xyz, const float* pos_xyz,
+                       const int* anc_seg_off, const int* pos_seg_off, int n_pairs, int n_anc, int n_pos, int max_anc, int D,
+                       float r_p, float r_n, const float* anc_pose, float* pair_out, float* row_loss, float* row_mask, float* row_lse,
+                       int* row_idx, void* ws, size_t ws_bytes, void* stream);
+
+/* Backward of regtr_infonce_rows' mean over pairs, loss = (1 / mean_div) sum_b pair_out[b,0] / pair_out[b,1], from the forward's own
+ * decisions (row_lse, row_idx, row_mask, pair_out) and the same distance arithmetic / anchor pose.  grad: ONE float on the device (the
+ * upstream gradient g); s_b = (g / mean_div) / pair_out[b,1] is formed on the device.  Over the allowed set of masked rows,
+ *   dl_ij = s_b exp(l_ij - LSE_i) - s_b [j = j*_i],   d_anc_i = sum_j dl_ij P'_j,   d_pos_j = sum_i dl_ij A_i
+ * (d_pos is the gradient of the TRANSFORMED positives P'); unmasked rows and ignored entries contribute 0.  Every row of every pair
+ * is written (pairs without columns give 0 rows); rows outside every pair are not.  Exact-f32 MFMA, one owner per output row,
+ * bit-reproducible.  max_anc / max_pos >= every pair's anchor / positive count.  Refused like regtr_infonce (and mean_div <= 0,
+ * ld_danc / ld_dpos < D). */
+int regtr_infonce_bwd(const float* anc, int ld_anc, const float* pos, int ld_pos, const float* anc_xyz, const float* pos_xyz,
+                      const int* anc_seg_off, const int* pos_seg_off, int n_pairs, int n_anc, int n_pos, int max_anc, int max_pos,
+                      int D, float r_n, const float* anc_pose, const float* row_lse, const int* row_idx, const float* row_mask,
+                      const float* pair_out, const float* grad, float mean_div, float* d_anc, int ld_danc, float* d_pos, int ld_dpos,
+                      void* stream);
+
+/* out [N1, N2] (row stride ldo) = a^T b for a [M, N1] and b [M, N2] (row strides lda, ldb) over a tall M: exact-f32 MFMA, split-K
+ * with a fixed-order float64 second pass, bit-reproducible.  fold = 1 (N1 == N2) writes InfoNCELossFull's dW from dW_sym = a^T b
+ * instead: out_ij = dW_sym_ij + dW_sym_ji for i < j, 2 dW_sym_ii on the diagonal, 0 below.  Refused: N1 or N2 not a positive
+ * multiple of 64, a negative M, a stride below its width, NULLs.  ws: regtr_gemm_tn_ws_bytes(M, N1, N2) bytes. */
+size_t regtr_gemm_tn_ws_bytes(int M, int N1, int N2);
+int regtr_gemm_tn(const float* a, int lda, const float* b, int ldb, int M, int N1, int N2, int fold, float* out, int ldo, void* ws,
+                  size_t ws_bytes, void* stream);
+
+/* Backward of CorrCriterion('mae') (models/losses/corr_loss.py:24-37): d_warped [n, 3] = ((g / den) w_i) sgn(warped - T kp), sgn(0)
+ * = 0, with T kp rounded per operation as regtr_loss_terms rounds it.  Point i of cloud c (seg_off [n_clouds + 1]) takes pose c
+ * (pose_stride 12 or 16); grad and den (the clamped weight sum) are ONE float each on the device.  Refused like regtr_se3_transform. */
+int regtr_corr_l1_bwd(const float* kp, const float* warped, const float* w, const int* seg_off, int n_clouds, int n, const float* pose,
+                      int pose_stride, const float* grad, const float* den, float* d_warped, void* stream);
 
 #ifdef __cplusplus
 }

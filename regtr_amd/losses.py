@@ -1,0 +1,157 @@
+"""Differentiable drop-ins for the reference's training losses: InfoNCELossFull (models/losses/feature_loss.py:246-314) and
+CorrCriterion (models/losses/corr_loss.py:9-40), with the same constructors, parameter names and forward signatures, so that
+
+    model.feature_criterion = InfoNCELossFull(cfg.d_embed, cfg.r_p, cfg.r_n)
+    model.feature_criterion_un = InfoNCELossFull(cfg.d_embed, cfg.r_p, cfg.r_n)
+    model.corr_criterion = CorrCriterion(metric='mae')
+
+drop into the reference model's training step ("Training-loss drop-in").  Forward and backward run on the HIP kernels
+of csrc/losses.hip (regtr_infonce_rows / regtr_infonce_bwd / regtr_gemm_tn, regtr_loss_terms / regtr_corr_l1_bwd) and the exact-f32
+GEMM; torch only packs the per-pair lists and forms the scalar means.  Nothing here synchronises with the host.
+
+Reference semantics are kept: a pair without an anchor inside r_p gives NaN (0 / 0), and its gradient contributions are exactly 0.
+Refused: metric='mse', overlap_weights=None, coordinates / poses / weights that require grad, double backward, tensors off the GPU.
+"""
+import torch
+import torch.nn as nn
+from torch.autograd.function import once_differentiable
+
+from . import context, ops
+
+_EPS = 1e-6     # corr_loss.py:6
+
+
+def _on_gpu(name, ts):
+    for t in ts:
+        if not isinstance(t, torch.Tensor) or t.device.type != 'cuda':
+            raise RuntimeError(f'{name}: every tensor must be on the GPU (got {getattr(t, "device", type(t))})')
+
+
+def _no_grad_inputs(name, ts):
+    if any(t.requires_grad for t in ts):
+        raise RuntimeError(f'{name}: coordinates, poses and weights take no gradient here (only features, W and the warped points do)')
+
+
+def _offsets(lens, dev):
+    off = [0]
+    for n in lens:
+        off.append(off[-1] + n)
+    return torch.tensor(off, dtype=torch.int32).to(dev, non_blocking=True)
+
+
+class _InfoNCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, A, G, W, ax, px, a_off, p_off, max_anc, max_pos, r_p, r_n):
+        with context.forward(A.device, f16_pair=False, status=None):
+            Wt = torch.triu(W)
+            w_sym = (Wt + Wt.t()).contiguous()                                        # feature_loss.py:295-296
+            P = ops.gemm(G, w_sym)                                                    # P' = G W_sym, exact-f32 MFMA
+            saved = ops.infonce_rows(A, P, ax, px, a_off, p_off, max_anc, r_p, r_n)
+        out = saved[0]
+        ctx.save_for_backward(A, G, P, w_sym, ax, px, a_off, p_off, *saved)
+        ctx.meta = (max_anc, max_pos, r_n, out.shape[0])
+        return (out[:, 0] / out[:, 1]).mean()                                         # feature_loss.py:312-314
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        A, G, P, w_sym, ax, px, a_off, p_off, *saved = ctx.saved_tensors
+        max_anc, max_pos, r_n, B = ctx.meta
+        g = g.detach().to(torch.float32).contiguous()
+        with context.forward(A.device, f16_pair=False, status=None):
+            dA, dP = ops.infonce_bwd(A, P, ax, px, a_off, p_off, max_anc, max_pos, r_n, saved, g, float(B))
+            dG = ops.gemm(dP, w_sym) if ctx.needs_input_grad[1] else None            # W_sym is symmetric
+            dW = ops.gemm_tn(G, dP, fold=True) if ctx.needs_input_grad[2] else None   # G^T dP', folded onto triu(W)
+        return dA, dG, dW, None, None, None, None, None, None, None, None
+
+
+class InfoNCELossFull(nn.Module):
+    """feature_loss.py:246-314 on the HIP kernels.  Parameter `W` (d_embed x d_embed, N(0, 0.1) init) and `n_sample` as the reference,
+    so state_dict keys match.  forward(src_feat, tgt_feat, src_xyz, tgt_xyz): lists of per-pair (N, D) float32 features and (N, 3)
+    coordinates on the GPU (src_xyz already in the target frame, as RegTR.compute_loss passes them) -> the mean over pairs of the
+    masked mean InfoNCE loss.  Gradients go to the features and to W."""
+
+    def __init__(self, d_embed, r_p, r_n):
+        super().__init__()
+        self.r_p = r_p
+        self.r_n = r_n
+        self.n_sample = 256
+        self.W = nn.Parameter(torch.zeros(d_embed, d_embed), requires_grad=True)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        nn.init.normal_(self.W, std=0.1)
+
+    def forward(self, src_feat, tgt_feat, src_xyz, tgt_xyz):
+        B = len(src_feat)
+        if B == 0 or not (len(tgt_feat) == len(src_xyz) == len(tgt_xyz) == B):
+            raise RuntimeError(f'InfoNCELossFull: need the same number (>= 1) of src / tgt features and coordinates, got '
+                               f'{len(src_feat)}, {len(tgt_feat)}, {len(src_xyz)}, {len(tgt_xyz)}')
+        _no_grad_inputs('InfoNCELossFull', [*src_xyz, *tgt_xyz])
+        _on_gpu('InfoNCELossFull', [self.W, *src_feat, *tgt_feat, *src_xyz, *tgt_xyz])
+        if any(f.dtype != torch.float32 for f in [self.W, *src_feat, *tgt_feat, *src_xyz, *tgt_xyz]):
+            raise RuntimeError('InfoNCELossFull: float32 features, coordinates and W only')
+        n_src = [int(f.shape[0]) for f in src_feat]
+        n_tgt = [int(f.shape[0]) for f in tgt_feat]
+        if min(n_src) < 1 or min(n_tgt) < 1:
+            raise RuntimeError('InfoNCELossFull: every cloud needs at least one point (the reference\'s topk needs one too)')
+        dev = src_feat[0].device
+        A = torch.cat(list(src_feat)).contiguous()
+        G = torch.cat(list(tgt_feat)).contiguous()
+        ax = torch.cat(list(src_xyz)).contiguous()
+        px = torch.cat(list(tgt_xyz)).contiguous()
+        return _InfoNCE.apply(A, G, self.W, ax, px, _offsets(n_src, dev), _offsets(n_tgt, dev), max(n_src), max(n_tgt),
+                              float(self.r_p), float(self.r_n))
+
+
+class _CorrL1(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, warped, kp, w, seg, seg2, pose):
+        with context.forward(warped.device, f16_pair=False, status=None):
+            terms = ops.loss_terms(w, w, kp, warped, seg2, pose)                      # (B, 5): columns 1, 2 = sum w |e|_1, sum w
+        den = terms[:, 2].sum().clamp_min(_EPS)
+        ctx.save_for_backward(kp, warped, w, seg, pose, den)
+        return terms[:, 1].sum() / den
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        kp, warped, w, seg, pose, den = ctx.saved_tensors
+        g = g.detach().to(torch.float32).contiguous()
+        with context.forward(kp.device, f16_pair=False, status=None):
+            d = ops.corr_l1_bwd(kp, warped, w, seg, pose, g, den)
+        return d, None, None, None, None, None
+
+
+class CorrCriterion(nn.Module):
+    """corr_loss.py:9-40 with metric 'mae' on the HIP kernels.  forward(kp_before, kp_warped_pred, pose_gt, overlap_weights): lists of
+    per-pair (N, 3) points and (N,) weights, pose_gt (B, 3, 4) or (B, 4, 4) -> sum w |warped - T kp|_1 / max(sum w, 1e-6) over all
+    pairs.  Gradients go to kp_warped_pred."""
+
+    def __init__(self, metric='mae'):
+        super().__init__()
+        if metric != 'mae':
+            raise NotImplementedError(f"CorrCriterion: metric {metric!r} is not implemented (only 'mae', what RegTR uses)")
+        self.metric = metric
+
+    def forward(self, kp_before, kp_warped_pred, pose_gt, overlap_weights=None):
+        if overlap_weights is None:
+            raise NotImplementedError('CorrCriterion: overlap_weights=None (the per-point mean of corr_loss.py:37) is not implemented')
+        B = int(pose_gt.shape[0])
+        if not (len(kp_before) == len(kp_warped_pred) == len(overlap_weights) == B) or B == 0:
+            raise RuntimeError(f'CorrCriterion: need one key-point set, warped set and weight vector per pose, got {len(kp_before)}, '
+                               f'{len(kp_warped_pred)}, {len(overlap_weights)} for {B} poses')
+        _no_grad_inputs('CorrCriterion', [pose_gt, *kp_before, *overlap_weights])
+        _on_gpu('CorrCriterion', [pose_gt, *kp_before, *kp_warped_pred, *overlap_weights])
+        if any(t.dtype != torch.float32 for t in [pose_gt, *kp_before, *kp_warped_pred, *overlap_weights]):
+            raise RuntimeError('CorrCriterion: float32 points, weights and poses only')
+        if pose_gt.dim() != 3 or tuple(pose_gt.shape[1:]) not in ((3, 4), (4, 4)):
+            raise RuntimeError(f'CorrCriterion: pose_gt must be (B, 3, 4) or (B, 4, 4), got {tuple(pose_gt.shape)}')
+        lens = [int(k.shape[0]) for k in kp_before]
+        dev = pose_gt.device
+        seg2 = _offsets(lens + [0] * B, dev)          # regtr_loss_terms' (src clouds, tgt clouds) layout with empty tgt clouds
+        seg = seg2[:B + 1]
+        kp = torch.cat(list(kp_before)).contiguous()
+        warped = torch.cat(list(kp_warped_pred)).contiguous()
+        w = torch.cat([x.reshape(-1) for x in overlap_weights]).contiguous()
+        return _CorrL1.apply(warped, kp, w, seg, seg2, pose_gt.contiguous())

@@ -645,3 +645,74 @@ def se3_transform(xyz, seg_off, pose):
     check(_lib.lib().regtr_se3_transform(ptr(xyz) if n else None, iptr(seg_off), seg_off.numel() - 1, n, ptr(pose),
                                          pose.shape[-2] * pose.shape[-1], ptr(out) if n else None, stream()), 'regtr_se3_transform')
     return out
+
+
+# ------------------------------------------------------------------------------------------------ training-loss backward
+def infonce_rows(anc, pos_t, anc_xyz, pos_xyz, anc_seg_off, pos_seg_off, max_anc, r_p, r_n, anc_pose=None):
+    """ops.infonce with the decisions its backward reuses (regtr_infonce_rows): -> (pair_out (B, 2), row_lse (N_anc,), row_idx (N_anc,)
+    int32, row_mask (N_anc,)).  pair_out is bit-identical to ops.infonce's.  Nothing here synchronises."""
+    L = _lib.lib()
+    n_anc, D = anc.shape
+    n_pos = pos_t.shape[0]
+    B = anc_seg_off.numel() - 1
+    dev = anc.device
+    out = torch.empty((B, 2), dtype=torch.float32, device=dev)
+    lse = torch.empty(n_anc, dtype=torch.float32, device=dev)
+    idx = torch.empty(n_anc, dtype=torch.int32, device=dev)
+    rm = torch.empty(n_anc, dtype=torch.float32, device=dev)
+    nb = L.regtr_infonce_ws_bytes(B, int(max_anc))
+    ws = _ws(max(nb, 1), dev)
+    lda = anc.stride(0) if n_anc > 1 else D
+    ldp = pos_t.stride(0) if n_pos > 1 else D
+    assert anc.stride(1) == 1 and pos_t.stride(1) == 1
+    check(L.regtr_infonce_rows(raw(anc) if n_anc else None, lda, raw(pos_t) if n_pos else None, ldp, ptr(anc_xyz) if n_anc else None,
+                               ptr(pos_xyz) if n_pos else None, iptr(anc_seg_off), iptr(pos_seg_off), B, n_anc, n_pos, int(max_anc), D,
+                               float(r_p), float(r_n), ptr(anc_pose), ptr(out), None, ptr(rm) if n_anc else None,
+                               ptr(lse) if n_anc else None, iptr(idx) if n_anc else None, bptr(ws), nb, stream()), 'regtr_infonce_rows')
+    return out, lse, idx, rm
+
+
+def infonce_bwd(anc, pos_t, anc_xyz, pos_xyz, anc_seg_off, pos_seg_off, max_anc, max_pos, r_n, saved, grad, mean_div, anc_pose=None):
+    """Backward of (1 / mean_div) sum_b pair_out[b,0] / pair_out[b,1] (regtr_infonce_bwd): saved = infonce_rows' result, grad a 0-dim
+    float32 device tensor.  -> (d_anc (N_anc, D), d_pos_t (N_pos, D)), d_pos_t the gradient of the TRANSFORMED positives.  anc / pos_t
+    contiguous.  Nothing here synchronises."""
+    out, lse, idx, rm = saved
+    n_anc, D = anc.shape
+    n_pos = pos_t.shape[0]
+    B = anc_seg_off.numel() - 1
+    d_anc = torch.empty((n_anc, D), dtype=torch.float32, device=anc.device)
+    d_pos = torch.empty((n_pos, D), dtype=torch.float32, device=anc.device)
+    check(_lib.lib().regtr_infonce_bwd(ptr(anc) if n_anc else None, D, ptr(pos_t) if n_pos else None, D,
+                                       ptr(anc_xyz) if n_anc else None, ptr(pos_xyz) if n_pos else None, iptr(anc_seg_off),
+                                       iptr(pos_seg_off), B, n_anc, n_pos, int(max_anc), int(max_pos), D, float(r_n), ptr(anc_pose),
+                                       ptr(lse) if n_anc else None, iptr(idx) if n_anc else None, ptr(rm) if n_anc else None, ptr(out),
+                                       ptr(grad.reshape(1)), float(mean_div), ptr(d_anc) if n_anc else None, D,
+                                       ptr(d_pos) if n_pos else None, D, stream()), 'regtr_infonce_bwd')
+    return d_anc, d_pos
+
+
+def gemm_tn(a, b, fold=False):
+    """a (M, N1)^T @ b (M, N2) -> (N1, N2) over a tall M (regtr_gemm_tn: split-K, fixed-order second pass, bit-reproducible); N1, N2
+    multiples of 64.  fold=True (N1 == N2): InfoNCELossFull's dW from dW_sym = a^T b (upper triangle dW_sym + dW_sym^T, diagonal
+    doubled, zero below)."""
+    L = _lib.lib()
+    M, N1 = a.shape
+    N2 = b.shape[1]
+    out = torch.empty((N1, N2), dtype=torch.float32, device=a.device)
+    nb = L.regtr_gemm_tn_ws_bytes(M, N1, N2)
+    ws = _ws(max(nb, 1), a.device)
+    check(L.regtr_gemm_tn(ptr(a) if M else None, N1, ptr(b) if M else None, N2, M, N1, N2, int(bool(fold)), ptr(out), N2, bptr(ws), nb,
+                          stream()), 'regtr_gemm_tn')
+    return out
+
+
+def corr_l1_bwd(kp, warped, w, seg_off, pose, grad, den):
+    """Backward of CorrCriterion('mae') (regtr_corr_l1_bwd): kp / warped (N, 3), w (N,) packed by seg_off (B+1,) int32, pose (B, 3|4, 4),
+    grad and den 0-dim float32 device tensors (den: the clamped weight sum) -> d warped (N, 3)."""
+    n = kp.shape[0]
+    pose = pose.contiguous()
+    out = torch.empty((n, 3), dtype=torch.float32, device=kp.device)
+    check(_lib.lib().regtr_corr_l1_bwd(ptr(kp) if n else None, ptr(warped) if n else None, ptr(w) if n else None, iptr(seg_off),
+                                       seg_off.numel() - 1, n, ptr(pose), pose.shape[-2] * pose.shape[-1], ptr(grad.reshape(1)),
+                                       ptr(den.reshape(1)), ptr(out) if n else None, stream()), 'regtr_corr_l1_bwd')
+    return out
