@@ -70,24 +70,24 @@ __device__ void svd3(const double A[9], double U[9], double S[3], double V[9])
     for (int i = 0; i < 9; i++) V[i] = Vs[i];
     // normalise U; rebuild (near-)null directions so U stays orthonormal
     const double tiny = 1e-300 + 1e-14 * S[0];
-    for (int j = 0; j < 2; j++) {
-        if (S[j] > tiny) for (int i = 0; i < 3; i++) U[3 * i + j] /= S[j];
-        else {   // any unit vector orthogonal to the previous columns
-            double e[3] = {0, 0, 0};
-            if (j == 0) e[0] = 1.0;
-            else {
-                const double u0[3] = {U[0], U[3], U[6]};
-                int m = fabs(u0[0]) < fabs(u0[1]) ? (fabs(u0[0]) < fabs(u0[2]) ? 0 : 2) : (fabs(u0[1]) < fabs(u0[2]) ? 1 : 2);
-                double a[3] = {0, 0, 0};
-                a[m] = 1.0;
-                const double d = a[0] * u0[0] + a[1] * u0[1] + a[2] * u0[2];
-                double nn = 0;
-                for (int i = 0; i < 3; i++) { e[i] = a[i] - d * u0[i]; nn += e[i] * e[i]; }
-                nn = sqrt(nn);
-                for (int i = 0; i < 3; i++) e[i] /= nn;
-            }
-            for (int i = 0; i < 3; i++) U[3 * i + j] = e[i];
-        }
+    if (S[0] <= tiny) {
+        // a zero covariance (one point, coincident points, all weights 0): U = V = I as LAPACK returns for a zero matrix, so that
+        // R = I and t = cb - ca as in the reference.  Completing U from e0 would give a 90-degree turn about x instead.
+        for (int i = 0; i < 9; i++) U[i] = V[i] = (i % 4 == 0) ? 1.0 : 0.0;
+        return;
+    }
+    for (int i = 0; i < 3; i++) U[3 * i] /= S[0];
+    if (S[1] > tiny) for (int i = 0; i < 3; i++) U[3 * i + 1] /= S[1];
+    else {   // any unit vector orthogonal to u0
+        const double u0[3] = {U[0], U[3], U[6]};
+        int m = fabs(u0[0]) < fabs(u0[1]) ? (fabs(u0[0]) < fabs(u0[2]) ? 0 : 2) : (fabs(u0[1]) < fabs(u0[2]) ? 1 : 2);
+        double a[3] = {0, 0, 0};
+        a[m] = 1.0;
+        const double d = a[0] * u0[0] + a[1] * u0[1] + a[2] * u0[2];
+        double e[3], nn = 0;
+        for (int i = 0; i < 3; i++) { e[i] = a[i] - d * u0[i]; nn += e[i] * e[i]; }
+        nn = sqrt(nn);
+        for (int i = 0; i < 3; i++) U[3 * i + 1] = e[i] / nn;
     }
     {
         // third column: u2 = +-(u0 x u1), sign agreeing with A v2 (so that S[2] >= 0)

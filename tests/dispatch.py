@@ -1,9 +1,11 @@
 """Which kernel instantiation the host-side dispatchers launch for a shape: a restatement of the C++ policy, for the tests.
 
 route_x3 mirrors csrc/gemm_x3.hip (x3_plan, x3_plan_f16 and the launch ladder at the end of regtr_gemm_x3) as regtr_amd/ops.py:gemm
-drives it, route_stream csrc/gemm_stream.hip (sg_cols_per_wg, the SG_L2 / SG_L3 ladder), route_mha csrc/attention.hip (regtr_mha_fwd).
+drives it, route_stream csrc/gemm_stream.hip (sg_cols_per_wg, the SG_L2 / SG_L3 ladder), route_mha csrc/attention.hip (regtr_mha_fwd),
+route_attn_xyz its regtr_attn_xyz (the correspondence decoder's coordinate attention, one instantiation per head dimension).
 tests/test_dispatch_routes.py checks the mirror against the host-only plan queries of the library and asserts that the GPU cases
-(tests/test_gpu_dispatch.py, tests/test_gpu_ops.py) reach every instantiation listed in X3_KERNELS / STREAM_KERNELS / MHA_KERNELS.  route_gather / route_maxpool mirror csrc/kpconv.hip
+(tests/test_gpu_dispatch.py, tests/test_gpu_ops.py, tests/test_gpu_pose.py) reach every instantiation listed in X3_KERNELS / STREAM_KERNELS /
+MHA_KERNELS / ATTN_XYZ_KERNELS.  route_gather / route_maxpool mirror csrc/kpconv.hip
 (regtr_kpconv_gather with the flag decision of ops.kpconv, regtr_maxpool_gather); their cases are in tests/test_gpu_gather.py and their
 universes GATHER_KERNELS / MAXPOOL_KERNELS.  route_instnorm / route_finalize_tiles mirror csrc/norm.hip (in_rows, the finalize split at
 n_clouds C = 4096) and route_block_tail csrc/block_tail.hip; their cases are in tests/test_gpu_norm.py and their universes NORM_KERNELS
@@ -182,6 +184,17 @@ X3_KERNELS = _x3_kernels()
 STREAM_KERNELS = {f'strip<{K // 16},{nb // 32},{fold}>' for K in (32, 64, 128) for nb in (32, 64, 128) for fold in ((0, 1) if K <= 64 else (0,))
                   if sg_cols_per_wg(nb, K) == nb}
 MHA_KERNELS = {'mha_f32<1>', 'mha_f32<4>'} | {f'mha_bf16<{w}>/p{p}' for w in ('BW4', 'BW8') for p in (0, 1, 3)}
+
+
+def route_attn_xyz(lens, head_dim):
+    """regtr_attn_xyz: k_attn_xyz<HDX> for HDX = head_dim.  No launch without a query row or a token, a check the launcher makes before
+    it looks at the head dimension; any other head dimension is refused (RG_ERR_ARG)."""
+    if max(lens, default=0) == 0 or sum(lens) == 0:
+        return 'none'
+    return f'attn_xyz<{head_dim}>' if head_dim in (32, 64, 128, 256) else 'refused'
+
+
+ATTN_XYZ_KERNELS = {f'attn_xyz<{hd}>' for hd in (32, 64, 128, 256)}
 
 
 # ------------------------------------------------------------------------------------------------ KPConv gather, max-pool (csrc/kpconv.hip)

@@ -2,9 +2,9 @@
 the GPU cases reach every instantiation they can launch.
 
 The mirror is checked against the plan queries libregtr_hip.so exports (host-only: no GPU needed); the coverage gate lists every
-instantiation of the launch ladders (dispatch.X3_KERNELS / STREAM_KERNELS / MHA_KERNELS / GATHER_KERNELS / MAXPOOL_KERNELS) and fails when
-no parametrized GPU case of tests/test_gpu_dispatch.py, tests/test_gpu_ops.py or tests/test_gpu_gather.py routes to one -- e.g. after a
-planner retune moved a case off its branch.  The gather mirror is checked against the library's regtr_kpconv_gather_computes_flag only:
+instantiation of the launch ladders (dispatch.X3_KERNELS / STREAM_KERNELS / MHA_KERNELS / ATTN_XYZ_KERNELS / GATHER_KERNELS /
+MAXPOOL_KERNELS) and fails when no parametrized GPU case of tests/test_gpu_dispatch.py, tests/test_gpu_ops.py, tests/test_gpu_pose.py or
+tests/test_gpu_gather.py routes to one -- e.g. after a planner retune moved a case off its branch.  The gather mirror is checked against the library's regtr_kpconv_gather_computes_flag only:
 a refusal is never probed by calling a launcher with stand-in pointers (a mirror wrong about it would launch on garbage)."""
 import itertools
 
@@ -98,6 +98,15 @@ def test_every_mha_instantiation_is_reached():
         routes.append(route)
     routes += [dispatch.route_mha(gd.MHA_8V4_LENS, p, min_wg=1) for p in (0, 1, 3)]     # the dispatch variant's side of the bit-identity test
     _gate(dispatch.MHA_KERNELS, routes)
+
+
+def test_every_attn_xyz_instantiation_is_reached():
+    from tests import test_gpu_pose as gp
+    routes = []
+    for head_dim, lens, route in _params(gp.test_attn_xyz_vs_fp64, ['head_dim', 'lens', 'route']):
+        assert dispatch.route_attn_xyz(lens, head_dim) == route, (head_dim, lens)
+        routes.append(route)
+    _gate(dispatch.ATTN_XYZ_KERNELS, routes)
 
 
 def test_gather_flag_mirror_matches_library():
