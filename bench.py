@@ -10,10 +10,15 @@ A "step" is one forward of the hot path (preprocess -> KPConv encoder -> 6 cross
 weighted Procrustes) over one batch of `--pairs` synthetic 3DMatch-sized pairs (BASELINE.json configs[2]: ~20k points
 per cloud, conf/3dmatch.yaml architecture, random-init weights), inputs resident in HBM.  Independent pairs shard across
 ranks with no data-path collective; the only RCCL traffic is one all_gather of the poses at the end of the timed region.
-Rank 0 prints ONE JSON line (metric pairs/s, whole-job aggregate) with `roofline` (KPConv gather, HBM bound) and
-`cpu_baseline` (the CPU oracle port timed on this box's host cores on a bounded sample of the same workload).
+Rank 0 prints ONE JSON line (metric pairs/s, whole-job aggregate).  A plain run does only what that figure needs: set-up, warm-up,
+the timed steps, --dump-outputs, the line.  --full adds the measurements and checks around it, after the timed steps: the `parity` gate
+against the CPU oracle, `roofline*` (KPConv gather, HBM bound) and the forward's roofline / traffic, the float32-grade comparison of the
+reduced-precision modes, `fp32x3_pairs_per_s`, `real_fragments_pairs_per_s` and `cpu_baseline` (the CPU oracle port timed on this box's
+host cores on a bounded sample of the same workload); --parity-pairs, --no-roofline, --no-strict-f32, --no-real and --no-cpu-baseline pick
+among them.
 """
 import argparse
+import contextlib
 import json
 import os
 import socket
@@ -90,6 +95,29 @@ def usable_cores():
     except (OSError, ValueError):
         pass
     return n
+
+
+@contextlib.contextmanager
+def synth_pairs_in_parallel(ids, points, shuffle, overlap):
+    """Set-up time only.  build_workload generates its synthetic pairs one after another -- 196 of ~86 ms each for the default line, most
+    of a plain run's time outside its steps; numpy releases the GIL in the heavy parts, so a thread pool generates them ahead instead.
+    Inside the `with`, regtr_amd.workload's synth_pair hands out these results for exactly these calls (same id, points, shuffle and
+    overlap, each once) and generates any other pair itself: the workload is what one-by-one generation gives, bit for bit."""
+    from concurrent.futures import ThreadPoolExecutor
+    from regtr_amd import workload
+    gen = workload.synth_pair
+    with ThreadPoolExecutor(max(1, min(usable_cores(), 16))) as ex:
+        made = ex.map(lambda i: gen(i, points, shuffle, overlap=overlap), ids)
+        ready = {((i, points, shuffle), (('overlap', overlap),)): p for i, p in zip(ids, made)}
+
+    def synth_pair(*a, **k):
+        key = (a, tuple(sorted(k.items())))
+        return ready.pop(key) if key in ready else gen(*a, **k)
+    workload.synth_pair = synth_pair
+    try:
+        yield
+    finally:
+        workload.synth_pair = gen
 
 
 def pick_cpu_threads(run_probe):
@@ -420,7 +448,7 @@ def main():
                          'predicted_pairs_per_s = total pairs / shard time -- a strong-scaling PREDICTION for W GPUs, flagged as such (no multi-GPU node needed)')
     ap.add_argument('--distinct-pairs', type=int, default=128, help='lomatch: different synthetic pairs generated per rank (cycled; set-up time only)')
     ap.add_argument('--parity-mode', action='store_true', help='cfg.kpconv_ref_row_order: the reference CPU ops\' row / tie orders on the GPU (slower; DESIGN section 4)')
-    ap.add_argument('--parity-pairs', type=int, default=8, help='pairs of the last timed step checked against the CPU oracle: first, last, largest, smallest slot of the batch + evenly spaced others (0 = off)')
+    ap.add_argument('--parity-pairs', type=int, default=8, help='--full: pairs of the last timed step checked against the CPU oracle: first, last, largest, smallest slot of the batch + evenly spaced others (0 = off)')
     ap.add_argument('--dtype', choices=['fp32', 'fp32x3', 'bf16', 'bf16x2'], default=None, help='cfg.compute_dtype (default: fp32 for 3dmatch, bf16 for modelnet)')
     ap.add_argument('--pairs', type=int, default=0, help='pairs per FORWARD (default 64 for 3dmatch -- three forwards in flight, see --replicas: 192 pairs per step --, 128 for modelnet -- three in flight --, at most 64 per forward for lomatch: a shard is cut into equal forwards; pairs are independent, 288 GB of HBM holds far more)')
     ap.add_argument('--points', type=int, default=20000, help='approx. points per cloud')
@@ -433,10 +461,13 @@ def main():
                          'forwards = R x --pairs pairs).  Default 3 for the 3dmatch / lomatch configurations (3 x 64 pairs: +6 % over one 192-pair forward at a time -- '
                          'forwards in flight fill each other\'s host waits and 5-6 ms heads; workload.ReplicaRunner), 3 for modelnet (3 x 128), 1 in parity mode and for --pairs < 16 of ~20 k-point clouds; '
                          '`--pairs 192 --replicas 1` = the round-5 line')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-real', action='store_true', help='skip the side measurement of the same configuration on the shipped real fragments (real_fragments_pairs_per_s)')
-    ap.add_argument('--no-roofline', action='store_true')
-    ap.add_argument('--no-strict-f32', action='store_true', help="skip the side measurement of compute_dtype 'fp32x3' on the same workload")
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run the side measurements and checks of the line: parity gate, rooflines, reduced-precision error, '
+                         'fp32x3 and real-fragment rates, CPU baseline (--parity-pairs and the --no-* options of each apply to them; a plain run has none)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-real', action='store_true', help='--full: skip the side measurement of the same configuration on the shipped real fragments (real_fragments_pairs_per_s)')
+    ap.add_argument('--no-roofline', action='store_true', help='--full: skip the roofline and traffic blocks')
+    ap.add_argument('--no-strict-f32', action='store_true', help="--full: skip the side measurement of compute_dtype 'fp32x3' on the same workload")
     ap.add_argument('--no-range-check', action='store_true', help='diagnostic: cfg.f16_range_check off -- no status-word wait at the end of a forward, so consecutive forwards are enqueued back to back')
     ap.add_argument('--stub-backend', default=None, help=argparse.SUPPRESS)   # tests/test_bench_entry.py: 'gloo'
     ap.add_argument('--collect-pmc', action='store_true', help='run the rocprofv3 counter passes behind roofline.traffic on this workload and write profiles/pmc_traffic.json (stamped with the code version)')
@@ -511,8 +542,13 @@ def main():
     n_local = int(pair_ids.numel())
     if args.real and args.config != '3dmatch':
         sys.exit('bench.py: --real is the 3dmatch configuration on the shipped real fragments')
-    cfg, model, pairs, batch = build_workload(args.config, n_local, args.points, args.shuffle, rank, dev, dtype, args.parity_mode,
-                                              distinct=args.distinct_pairs if lomatch else None, real=args.real, head_init=args.head_init)
+    # the synthetic pairs build_workload will ask for: its head-probe calibration pairs, then ids rank * 100003 + i
+    ids = [] if (args.config == 'modelnet' or args.real) else \
+        [900000 + i for i in range(4 if (args.head_init or 'probe') == 'probe' else 0)] + \
+        [rank * 100003 + i for i in range(min(n_local, args.distinct_pairs) if lomatch else n_local)]
+    with synth_pairs_in_parallel(ids, args.points, args.shuffle, 'lomatch' if lomatch else None):
+        cfg, model, pairs, batch = build_workload(args.config, n_local, args.points, args.shuffle, rank, dev, dtype, args.parity_mode,
+                                                  distinct=args.distinct_pairs if lomatch else None, real=args.real, head_init=args.head_init)
     if args.no_range_check:
         model._range_check = False
 
@@ -594,14 +630,14 @@ def main():
                 'PREDICTION': f'rank 0\'s shard of a {W}-rank pass over the {args.total_pairs}-pair set, timed on ONE GPU with the pose gather through a one-rank RCCL group: '
                               f'a {W}-GPU pass takes at least this long (largest shard; the {W}-rank all_gather moves {W} x {-(-args.total_pairs // W)} x 52 bytes over xGMI instead of one '
                               'rank\'s rows, and the ranks share the host).  NOT a measurement of a multi-GPU run.'}
-        if args.parity_pairs > 0:
+        if args.full and args.parity_pairs > 0:
             # "pose err vs ref" (BASELINE.json metric): the last timed forward's outputs against the CPU oracle, >= 2 pairs
             lo, hi = chunks[-1]
             slots = parity_slots([len(a) + len(b) for a, b in pairs[lo:hi]], args.parity_pairs)
             res['parity'] = parity_check(cfg, model, pairs[lo:hi], last_out, slots, args.parity_mode)
             res['parity']['enforced'] = dtype in ('fp32', 'fp32x3')      # 'bf16' reports the error; the 1e-4 gate is the float32 modes'
         fwd_batch = {k: v[chunks[0][0]:chunks[0][1]] for k, v in batch.items()}
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             keep = {}
             r = measure_kpconv_roofline(model, fwd_batch, keep=keep)
             traffic = pmc_traffic(args.pairs, args.points, args.shuffle, r, args.real) if (args.config == '3dmatch' and not args.parity_mode) else None
@@ -647,7 +683,7 @@ def main():
                 {'hbm_GB': None, 'compulsory_GB': round(comp / 1e9, 3), 'ratio': None, 'top3': None, 'note': 'counter passes are kept for the default 3dmatch workload only'}
             # the candid companion of roofline.frac, at the top level: HBM bytes the COUNTERS saw per gather launch / launch time / peak
             res['counter_hbm_frac_of_peak'] = r.get('counter_hbm_frac_of_peak')
-        if dtype not in ('fp32', 'fp32x3'):
+        if args.full and dtype not in ('fp32', 'fp32x3'):
             # reduced-precision error, reported next to the number (parity is gated in fp32): same batch, float32-grade model
             from regtr_amd import RegTR, load_config
             cfg32 = load_config(os.path.join(ROOT, 'regtr_amd', 'conf', f'{"3dmatch" if lomatch else args.config}.yaml'))
@@ -696,15 +732,15 @@ def main():
             res['config']['fp32x3_same_workload'] = {'value': n_local / t3, 'unit': 'pairs/s', 'ms_per_step': t3 * 1e3, 'steps': k3,
                                                      'max_abs_pose_vs_default': float((o3[0]['pose'] - model(dict(fwd_batch))['pose']).abs().max())}
             del run3, o3, m3
-        if dtype == 'fp32' and world == 1 and not args.no_strict_f32 and not args.parity_mode:
+        if args.full and dtype == 'fp32' and world == 1 and not args.no_strict_f32 and not args.parity_mode:
             side('fp32x3', measure_fp32x3)
-        if args.config == '3dmatch' and world == 1 and not args.real and not args.no_real and not args.parity_mode and args.points == 20000 and not args.shuffle:
+        if args.full and args.config == '3dmatch' and world == 1 and not args.real and not args.no_real and not args.parity_mode and args.points == 20000 and not args.shuffle:
             # the same configuration on the REAL fragments the reference ships (demo.py:26-49), same pairs per forward, measured in this run outside
             # the timed region: the synthetic rooms are calibrated to the red-kitchen pair's level sizes (regtr_amd/synthetic.py), this is the check
             def measure_real():
                 res['real_fragments_pairs_per_s'], res['real_fragments'] = measure_real_fragments(args, dev, dtype)
             side('real_fragments', measure_real)
-        if not args.no_cpu_baseline and world == 1:      # the CPU leg is reported by the single-GPU run only
+        if args.full and not args.no_cpu_baseline and world == 1:      # the CPU leg is reported by the single-GPU run only
             try:
                 res['cpu_baseline'] = cpu_baseline(cfg, [pairs[i % len(pairs)] for i in range(24 if args.config == 'modelnet' else 6)],
                                                    cfg_name='3dmatch' if lomatch else args.config)

@@ -263,3 +263,24 @@ def test_dump_outputs_budget_sampling_and_layout(tmp_path):
     full = torch.cat([t for o in outs for t in o['src_feat']], 1).numpy()
     assert feat.shape == (6, a['src_feat']['rows_kept'], 256)
     assert any(np.array_equal(feat[:, 0], full[:, i]) for i in range(full.shape[1]))             # rows of the real output
+
+
+def test_parallel_synthetic_pairs_equal_one_by_one_generation():
+    """bench.synth_pairs_in_parallel (set-up of every run): inside the `with`, workload.synth_pair returns the pre-generated pairs for
+    the calls build_workload makes -- bit for bit what one-by-one generation gives, each handed out once --, generates any other call
+    itself, and the original function is back afterwards."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from regtr_amd import synthetic, workload
+    ids = [900000, 5, 6]
+    want = {i: synthetic.synth_pair(i, 3000, False, overlap='lomatch') for i in ids + [7]}
+    orig = workload.synth_pair
+    with bench.synth_pairs_in_parallel(ids, 3000, False, 'lomatch'):
+        assert workload.synth_pair is not orig
+        got = [(i, workload.synth_pair(i, 3000, False, overlap='lomatch')) for i in (6, 900000, 5, 7, 5)]
+        other = workload.synth_pair(5, 3000, False)                     # another overlap: not a pre-generated call
+    assert workload.synth_pair is orig
+    for i, (s, t) in got:
+        assert s.dtype == np.float32 and np.array_equal(s, want[i][0]) and np.array_equal(t, want[i][1])
+    assert np.array_equal(other[0], synthetic.synth_pair(5, 3000, False)[0])

@@ -29,8 +29,8 @@ def _torchrun(nproc, script_args, timeout=600):
 
 def test_bench_under_torchrun_nccl_world1():
     """The driver's N > 1 command line at N = 1: bench.py as a rank of a torch.distributed.run job with the RCCL backend.  The line's
-    n_gpus counts ranks whose poses came THROUGH the collective; the parity gate runs as in a plain launch."""
-    r = _torchrun(1, [os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--pairs', '4', '--no-cpu-baseline',
+    n_gpus counts ranks whose poses came THROUGH the collective; the parity gate (--full) runs as in a plain launch."""
+    r = _torchrun(1, [os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--pairs', '4', '--full', '--no-cpu-baseline',
                       '--no-roofline', '--parity-pairs', '2'])
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])

@@ -11,7 +11,7 @@ tag=${1:-evidence}; out=gpurun_out/$tag; mkdir -p $out; export TMPDIR=/tmp
 timeout 1500 python -m pytest tests -m gpu -q -rs --durations=5 > $out/pytest.log 2>&1; echo "pytest exit $?" >> $out/pytest.log; tail -6 $out/pytest.log
 timeout 900 python bench.py --collect-pmc --pmc-tag $tag > $out/collect_pmc.log 2>&1; tail -2 $out/collect_pmc.log | cut -c1-400
 cp profiles/pmc_traffic.json $out/pmc_traffic.json; cp profiles/${tag}_pmc_traffic_kernels.md $out/ 2>/dev/null
-timeout 900 python bench.py > $out/bench.json 2> $out/bench.err; python - <<PY
+timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err; python - <<PY
 import json
 d=json.loads(open('$out/bench.json').read().strip().splitlines()[-1]); p=d['parity']; r=d['roofline']; ft=d['forward_traffic']
 print('bench', round(d['value'],1), round(d['ms_per_step'],3), 'parity', p['ok'], p['pose_max_abs'], p['corr_max_abs'], 'gather frac', round(r['frac'],3), 'traffic', r['traffic'], r['detail'].get('traffic_note'), 'counter frac', d.get('counter_hbm_frac_of_peak'),
@@ -30,7 +30,7 @@ pmc 3 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT
 python tools/pmc_summary.py --mfma $out > $out/pmc_mfma.md 2>&1; head -14 $out/pmc_mfma.md; find $out -name "*.csv" -size +4M -delete
 for cfg in "--replicas 1 --steps 40 --warmup 5" "--pairs 192 --replicas 1 --steps 20 --warmup 3" "--pairs 192 --replicas 2 --steps 10 --warmup 3" "--real --steps 10 --warmup 3" "--real --replicas 1 --pairs 192 --steps 10 --warmup 3" "--pairs 1 --steps 300 --warmup 30" "--pairs 3 --steps 100 --warmup 10" "--pairs 8 --steps 50 --warmup 5" "--shuffle --steps 10 --warmup 2" "--points 100000 --pairs 8 --steps 6 --warmup 2" "--config modelnet --steps 10 --warmup 2" "--config modelnet --pairs 256 --replicas 1 --steps 10 --warmup 2" "--config modelnet --dtype fp32 --steps 10 --warmup 2" "--parity-mode --pairs 64 --steps 5 --warmup 2 --no-roofline" "--config lomatch --total-pairs 1781 --steps 3 --warmup 1" "--config lomatch --total-pairs 1781 --emulate-rank-of 2 --steps 5 --warmup 2 --no-roofline" "--config lomatch --total-pairs 1781 --emulate-rank-of 4 --steps 8 --warmup 2 --no-roofline" "--config lomatch --total-pairs 1781 --emulate-rank-of 8 --steps 12 --warmup 3 --no-roofline" "--dtype fp32x3 --steps 10 --warmup 2"; do
   t=$(echo $cfg | tr -d ' -' | cut -c1-44)
-  timeout 600 python bench.py $cfg --no-cpu-baseline --no-strict-f32 --no-real > $out/bench_$t.json 2> $out/bench_$t.err; echo "exit $?" >> $out/bench_$t.err
+  timeout 600 python bench.py $cfg --full --no-cpu-baseline --no-strict-f32 --no-real > $out/bench_$t.json 2> $out/bench_$t.err; echo "exit $?" >> $out/bench_$t.err
   python - <<PY
 import json
 try:

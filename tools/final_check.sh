@@ -5,7 +5,7 @@ tag=${1:-final}; out=gpurun_out/$tag; mkdir -p $out; export TMPDIR=/tmp
 timeout 1500 python -m pytest tests -m gpu -q -rs --durations=5 > $out/pytest.log 2>&1; echo "pytest exit $?" >> $out/pytest.log; tail -5 $out/pytest.log
 timeout 900 python bench.py --collect-pmc --pmc-tag $tag > $out/collect_pmc.log 2>&1; tail -1 $out/collect_pmc.log | cut -c1-300
 cp profiles/pmc_traffic.json $out/pmc_traffic.json; cp profiles/${tag}_pmc_traffic_kernels.md $out/ 2>/dev/null
-timeout 900 python bench.py > $out/bench.json 2> $out/bench.err; echo "bench exit $?"; tail -2 $out/bench.err
+timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench exit $?"; tail -2 $out/bench.err
 python - <<PY
 import json
 d=json.loads([l for l in open('$out/bench.json') if l.startswith('{')][-1]); p=d['parity']; r=d['roofline']; ft=d['forward_traffic']

@@ -8,7 +8,7 @@ fi
 shift; shift
 for cfg in "$@"; do
   t=$(echo "$cfg" | tr -d ' -' | cut -c1-30)
-  timeout 400 python bench.py $cfg --no-cpu-baseline > $out/bench_$t.json 2> $out/bench_$t.err; echo "exit $?" >> $out/bench_$t.err
+  timeout 400 python bench.py $cfg --full --no-cpu-baseline > $out/bench_$t.json 2> $out/bench_$t.err; echo "exit $?" >> $out/bench_$t.err
   python - <<PY
 import json
 try:
