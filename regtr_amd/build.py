@@ -1,6 +1,5 @@
-"""Builds regtr_amd/libregtr_hip.so (gfx950) in-tree with hipcc.  `python -m regtr_amd.build [--force] [--experimental] [--dispatch]`.
---experimental additionally builds libregtr_hip.experimental.so (-DREGTR_EXPERIMENTAL: the measured-slower experiment kernels of
-include/regtr_hip_experimental.h, which the shipped library does not contain; regtr_amd/experimental.py)."""
+"""Builds regtr_amd/libregtr_hip.so and libregtr_parity.so (gfx950) in-tree with hipcc.  `python -m regtr_amd.build [--force] [--dispatch]`.
+--dispatch additionally builds libregtr_hip.dispatch.so (tests only: build_dispatch)."""
 import os
 import subprocess
 import sys
@@ -63,67 +62,50 @@ def write_build_info():
     return info
 
 
-def build(force=False, verbose=False, variant=None, variant_flags=None):
-    """variant / variant_flags default to REGTR_VARIANT / REGTR_VARIANT_FLAGS (development builds next to the product library)."""
-    VARIANT = globals()['VARIANT'] if variant is None else variant
-    VARIANT_FLAGS = globals()['VARIANT_FLAGS'] if variant_flags is None else list(variant_flags)
-    LIB = os.path.join(HERE, f'libregtr_hip.{VARIANT}.so') if VARIANT else globals()['LIB']
-    objdir = os.path.join(HERE, 'build', VARIANT) if VARIANT else os.path.join(HERE, 'build')
+def _compile_and_link(lib, sources, objdir, flags, force, verbose):
+    """Compiles the stale ones of `sources` (in parallel) into objdir and links `lib` if an object changed or the library is missing."""
     os.makedirs(objdir, exist_ok=True)
     inc = os.path.join(os.path.dirname(HERE), 'include')
     headers = ([os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')]
                + [os.path.join(inc, f) for f in os.listdir(inc) if f.endswith('.h')])      # the public C-ABI header is a dependency too
 
+    def run(cmd):
+        if verbose:
+            print(' '.join(cmd))
+        subprocess.check_call(cmd)
+
     def compile_one(src):
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src.replace('.hip', '.o'))
         if force or _stale(o, [s] + headers):
-            cmd = [HIPCC] + COMMON + EXTRA.get(src, []) + VARIANT_FLAGS + ['-c', s, '-o', o]
-            if verbose:
-                print(' '.join(cmd))
-            subprocess.check_call(cmd)
+            run([HIPCC] + COMMON + EXTRA.get(src, []) + flags + ['-c', s, '-o', o])
             return o, True
         return o, False
 
-    with ThreadPoolExecutor(max_workers=len(SOURCES)) as ex:
-        res = list(ex.map(compile_one, SOURCES))
-    objs = [o for o, _ in res]
-    if force or any(ch for _, ch in res) or not os.path.exists(LIB):
-        cmd = [HIPCC, '--offload-arch=' + ARCH, '-shared', '-fPIC', '-o', LIB] + objs
-        if verbose:
-            print(' '.join(cmd))
-        subprocess.check_call(cmd)
-    if not VARIANT:
-        build_parity(force, verbose)
-    if not VARIANT and os.path.isdir(os.path.join(os.path.dirname(HERE), '.git')):
+    with ThreadPoolExecutor(max_workers=len(sources)) as ex:
+        res = list(ex.map(compile_one, sources))
+    if force or any(ch for _, ch in res) or not os.path.exists(lib):
+        run([HIPCC, '--offload-arch=' + ARCH, '-shared', '-fPIC', '-o', lib] + [o for o, _ in res])
+    return lib
+
+
+def build(force=False, verbose=False, variant=None, variant_flags=None):
+    """variant / variant_flags default to REGTR_VARIANT / REGTR_VARIANT_FLAGS (development builds next to the product library).  The product
+    build (no variant) builds libregtr_parity.so as well."""
+    variant = VARIANT if variant is None else variant
+    flags = VARIANT_FLAGS if variant_flags is None else list(variant_flags)
+    if variant:
+        return _compile_and_link(os.path.join(HERE, f'libregtr_hip.{variant}.so'), SOURCES, os.path.join(HERE, 'build', variant), flags, force, verbose)
+    _compile_and_link(LIB, SOURCES, os.path.join(HERE, 'build'), flags, force, verbose)
+    build_parity(force, verbose)
+    if os.path.isdir(os.path.join(os.path.dirname(HERE), '.git')):
         write_build_info()
     return LIB
 
 
 def build_parity(force=False, verbose=False):
     """libregtr_parity.so from csrc/ref_order.hip (regtr_amd/_lib.py: parity_lib; loaded only when parity mode asks for KD-tree tables)."""
-    objdir = os.path.join(HERE, 'build', 'parity')
-    os.makedirs(objdir, exist_ok=True)
-    inc = os.path.join(os.path.dirname(HERE), 'include')
-    deps = ([os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')] + [os.path.join(inc, f) for f in os.listdir(inc) if f.endswith('.h')])
-    objs, changed = [], False
-    for src in PARITY_SOURCES:
-        s, o = os.path.join(CSRC, src), os.path.join(objdir, src.replace('.hip', '.o'))
-        if force or _stale(o, [s] + deps):
-            cmd = [HIPCC] + COMMON + EXTRA.get(src, []) + ['-c', s, '-o', o]
-            if verbose:
-                print(' '.join(cmd))
-            subprocess.check_call(cmd)
-            changed = True
-        objs.append(o)
-    if force or changed or not os.path.exists(PARITY_LIB):
-        subprocess.check_call([HIPCC, '--offload-arch=' + ARCH, '-shared', '-fPIC', '-o', PARITY_LIB] + objs)
-    return PARITY_LIB
-
-
-def build_experimental(force=False, verbose=False):
-    """libregtr_hip.experimental.so: the product sources + the experiment kernels (regtr_amd/experimental.py)."""
-    return build(force, verbose, variant='experimental', variant_flags=['-DREGTR_EXPERIMENTAL=1'])
+    return _compile_and_link(PARITY_LIB, PARITY_SOURCES, os.path.join(HERE, 'build', 'parity'), [], force, verbose)
 
 
 def build_dispatch(force=False, verbose=False):
@@ -134,9 +116,6 @@ def build_dispatch(force=False, verbose=False):
 
 
 if __name__ == '__main__':
-    print(build(force='--force' in sys.argv, verbose=True))
-    print(build_parity(force='--force' in sys.argv, verbose=True))
-    if '--experimental' in sys.argv:
-        print(build_experimental(force='--force' in sys.argv, verbose=True))
+    print(build(force='--force' in sys.argv, verbose=True))      # (the parity library with it)
     if '--dispatch' in sys.argv:
         print(build_dispatch(force='--force' in sys.argv, verbose=True))

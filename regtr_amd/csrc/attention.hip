@@ -191,7 +191,6 @@ __global__ void __launch_bounds__(KS * RG_WAVE) __attribute__((amdgpu_waves_per_
 // ------------------------------------------------------------------------------------------------------------------
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int BW = 4;                 // waves (32-query tiles) per workgroup; clouds of more than 128 tokens: BW8 = 8 (round 6, below)
 constexpr int BW8 = 8;
 constexpr int BROW = 64;              // bytes per LDS row
@@ -214,20 +213,8 @@ constexpr float MHA_F16_SCALE = 2048.f;
 #ifndef MHA_WAVES_ATTR
 #define MHA_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(3)))
 #endif
-#ifndef MHA_PACKED
-#define MHA_PACKED 0                  // softmax / pair-split arithmetic on two-element vectors (v_pk_*_f32): measured SLOWER (below); A/B: -DMHA_PACKED=1
-#endif
 #ifndef MHA_WIDE_MIN_WG
 #define MHA_WIDE_MIN_WG 4096         // eight-wave workgroups only on launches with at least this many of them (A/B: -DMHA_WIDE_MIN_WG=..)
-#endif
-#ifndef MHA_WIDE
-#define MHA_WIDE 1                    // 8-wave workgroups for clouds of more than 128 tokens (A/B: -DMHA_WIDE=0)
-#endif
-#ifndef MHA_OPT_SWAP
-#define MHA_OPT_SWAP 1
-#endif
-#ifndef MHA_OPT_MASK
-#define MHA_OPT_MASK 1
 #endif
 __device__ __forceinline__ unsigned f16_pack(float a, float b)
 {
@@ -243,12 +230,7 @@ __device__ __forceinline__ void bf_split2(float a, float b, unsigned (&p)[NP])
         static_assert(NP == 2, "the f16 pair has two planes");
         p[0] = f16_pack(a, b);
         const f16x2v h = __builtin_bit_cast(f16x2v, p[0]);
-#if MHA_PACKED
-        const f32x2 r = (f32x2{a, b} - f32x2{(float)h.x, (float)h.y}) * f32x2{MHA_F16_SCALE, MHA_F16_SCALE};      // (v_pk_add_f32 + v_pk_mul_f32)
-        p[1] = f16_pack(r.x, r.y);
-#else
         p[1] = f16_pack((a - (float)h.x) * MHA_F16_SCALE, (b - (float)h.y) * MHA_F16_SCALE);
-#endif
         return;
     }
     p[0] = bf_pack(a, b);
@@ -298,17 +280,11 @@ __device__ __forceinline__ void f16_mma(const bf16x8 (&a)[2], const bf16x8 (&b)[
 // through ds_bpermute_b32 and a wait on LDS.  max and + are commutative: both halves get bit-identical results.
 __device__ __forceinline__ float mha_max_halves(float x)
 {
-#if !MHA_OPT_SWAP
-    return fmaxf(x, __shfl_xor(x, 32, RG_WAVE));
-#endif
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
     return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
 }
 __device__ __forceinline__ float mha_sum_halves(float x)
 {
-#if !MHA_OPT_SWAP
-    return x + __shfl_xor(x, 32, RG_WAVE);
-#endif
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
@@ -421,17 +397,12 @@ __global__ void __launch_bounds__(NW * RG_WAVE) MHA_WAVES_ATTR k_mha_fwd_bf16(Mh
 #pragma unroll
     for (int ks = 0; ks < 2; ks++) f_off[ks] = (unsigned)l31 * BROW + ((((unsigned)(2 * ks + hi)) ^ (((unsigned)l31 >> 2) & 3u)) * 16u);
 
-// development A-B (variant build -DMHA_SETPRIO=1): raise the wave's issue priority around its MFMA groups -- the explicit form of the
+// (Measured and dropped: s_setprio 2 / 0 around the wave's MFMA groups -- the explicit form of the
 // MFMA / VALU "ping-pong" between the 3 waves a SIMD holds (144 VGPRs + 16 AGPRs, 24 KB of LDS per workgroup: three workgroups per CU,
 // so the hardware already interleaves one wave's MFMAs with its neighbours' softmax).  Measured on a 64-pair forward, alternating
 // runs on one box: 165 us per launch against 155-156 us without (gpurun_out/r03_y4): the kernel is VALU-bound (per 32-key tile and
 // wave 768 matrix-pipe cycles against ~1500 of softmax / split arithmetic + ~900 of K/V split and staging), and prioritising the
-// pipe that has slack delays the one that has none.  Off.
-#ifdef MHA_SETPRIO
-#define MHA_PRIO(p) __builtin_amdgcn_s_setprio(p)
-#else
-#define MHA_PRIO(p)
-#endif
+// pipe that has slack delays the one that has none.)
 #ifdef MHA_PROF          // development: per-wave phase clocks (REGTR_VARIANT_FLAGS=-DMHA_PROF)
     long long pt[6] = {0, 0, 0, 0, 0, 0}, pc = clock64(), pstart = pc;
 #define MHA_STAMP(I) do { const long long n_ = clock64(); pt[I] += n_ - pc; pc = n_; } while (0)
@@ -460,29 +431,19 @@ __global__ void __launch_bounds__(NW * RG_WAVE) MHA_WAVES_ATTR k_mha_fwd_bf16(Mh
                 bf16x8 kf[NP];
 #pragma unroll
                 for (int p = 0; p < NP; p++) kf[p] = __builtin_bit_cast(bf16x8, *(const uint4*)(&Ks[buf][p][f_off[ks]]));
-                MHA_PRIO(2);
                 if constexpr (F16) f16_mma(kf, qf[ks], sc, sc_lo);
                 else sc = bf_mma<NP>(kf, qf[ks], sc);
-                MHA_PRIO(0);
             }
-            // (PAIRS, round 6: written on two-element vectors so that hipcc emits the packed-f32 instructions -- v_pk_fma_f32 / v_pk_add_f32 do two
-            //  lanes' worth of elements per issue slot.  The scalar form compiled to 17 v_sub + 17 v_add (+ 16 v_fma in the f16 pair form) per key
-            //  tile next to 17 quarter-rate v_exp: the softmax is what bounds this kernel at head dimension 32.)
+            // (Measured and dropped, round 6: the softmax / pair-split arithmetic written on two-element vectors so that hipcc emits the packed-f32
+            //  instructions, v_pk_fma_f32 / v_pk_add_f32.  This scalar form compiles to 17 v_sub + 17 v_add (+ 16 v_fma in the f16 pair form) per key
+            //  tile next to 17 quarter-rate v_exp -- the softmax is what bounds this kernel at head dimension 32 -- and the packed form had 6-7 % fewer
+            //  vector instructions but ran 2-4 % slower: docs/NEGATIVES.md.)
             if constexpr (F16) {
-#if MHA_PACKED
-                const f32x2 lsc = {1.0f / MHA_F16_SCALE, 1.0f / MHA_F16_SCALE};
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    const f32x2 v = f32x2{sc_lo[r], sc_lo[r + 1]} * lsc + f32x2{sc[r], sc[r + 1]};
-                    sc[r] = v.x; sc[r + 1] = v.y;
-                }
-#else
 #pragma unroll
                 for (int r = 0; r < 16; r++) sc[r] += sc_lo[r] * (1.0f / MHA_F16_SCALE);
-#endif
             }
             MHA_STAMP(2);
-            if (!MHA_OPT_MASK || kt + TK > nk) {       // (workgroup-uniform: only the last tile of a cloud has keys past the end)
+            if (kt + TK > nk) {       // (workgroup-uniform: only the last tile of a cloud has keys past the end)
 #pragma unroll
                 for (int r = 0; r < 16; r++)
                     if (kt + acc_row(r, hi) >= nk) sc[r] = -INFINITY;
@@ -494,23 +455,10 @@ __global__ void __launch_bounds__(NW * RG_WAVE) MHA_WAVES_ATTR k_mha_fwd_bf16(Mh
             const float m_new = fmaxf(m_run, mx);
             const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
             float pr[16];
-#if MHA_PACKED
-            f32x2 ps2 = {0.f, 0.f};
-            const f32x2 mm = {m_new, m_new};
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-                const f32x2 d = f32x2{sc[r], sc[r + 1]} - mm;
-                pr[r] = __builtin_amdgcn_exp2f(d.x);
-                pr[r + 1] = __builtin_amdgcn_exp2f(d.y);
-                ps2 += f32x2{pr[r], pr[r + 1]};
-            }
-            float psum = mha_sum_halves(ps2.x + ps2.y);
-#else
             float psum = 0.f;
 #pragma unroll
             for (int r = 0; r < 16; r++) { pr[r] = __builtin_amdgcn_exp2f(sc[r] - m_new); psum += pr[r]; }
             psum = mha_sum_halves(psum);
-#endif
             l_run = l_run * alpha + psum;
             m_run = m_new;
 #pragma unroll
@@ -524,10 +472,8 @@ __global__ void __launch_bounds__(NW * RG_WAVE) MHA_WAVES_ATTR k_mha_fwd_bf16(Mh
                 bf_split8<NP, F16>(x, pf);
 #pragma unroll
                 for (int p = 0; p < NP; p++) vf[p] = __builtin_bit_cast(bf16x8, *(const uint4*)(&Vt[buf][p][f_off[ks]]));
-                MHA_PRIO(2);
                 if constexpr (F16) f16_mma(vf, pf, o, o_lo);
                 else o = bf_mma<NP>(vf, pf, o);
-                MHA_PRIO(0);
             }
             MHA_STAMP(3);
         }
@@ -721,7 +667,7 @@ int regtr_mha_fwd(const float* q, int ldq, const float* k, int ldk, const float*
         // -- on launches of many rounds of workgroups only.  Measured (tools/mha_bench.py, profiles/r06_f_mha_wide.txt; us per launch, 4 -> 8 waves):
         // 384 clouds of 330-460 tokens, f16 pair 439.7 -> 419.5, bf16x3 553.7 -> 515.3; 512 clouds of 560-640, bf16 572.9 -> 554.9 (inside the
         // ModelNet forward 547 -> 464); but 128 clouds of 230-360 (2048 eight-wave workgroups, four rounds on 256 CUs x 2) 93.9 -> 110.8.
-        if (MHA_WIDE && max_len > BW * TQ && (long long)rg_cdiv(max_len, BW8 * TQ) * n_heads * n_clouds >= MHA_WIDE_MIN_WG) {
+        if (max_len > BW * TQ && (long long)rg_cdiv(max_len, BW8 * TQ) * n_heads * n_clouds >= MHA_WIDE_MIN_WG) {
             const dim3 grid(rg_cdiv(max_len, BW8 * TQ), n_heads, n_clouds);
             if (precision == 0) k_mha_fwd_bf16<3, false, BW8><<<grid, BW8 * RG_WAVE, 0, st>>>(g);
             else if (precision == 3) k_mha_fwd_bf16<2, true, BW8><<<grid, BW8 * RG_WAVE, 0, st>>>(g);

@@ -212,7 +212,7 @@ struct Enc {
                     shortcut = sc;
                 }
                 // :727-730  IN + LReLU of the conv output: folded into unary2's operand -- or, where the fold would route a wide product to
-                // the tiled kernel (ops.preapply_unary2: >= 8192 rows and more than 64 channels), applied in place first
+                // the tiled kernel (ops.PREAPPLY_MIN_ROWS: >= 8192 rows and more than 64 channels), applied in place first
                 if (conv_stats && Q.n >= ENC_PREAPPLY_ROWS && mid > 64) {
                     if (!dry) {
                         rc = regtr_instnorm_apply(conv, Q.seg_off, n_clouds, Q.max_len, mid, conv_stats, nullptr, nullptr, 1, slope, conv, nullptr, nullptr, st);

@@ -523,9 +523,6 @@ __device__ __forceinline__ void x3h_splitf_b(float a, float b, float ha, float h
                  "v_cvt_pk_f16_f32 %0, %1, %2"
                  : "=&v"(p1), "=&v"(t0), "=&v"(t1) : "v"(a), "v"(b), "v"(ha), "v"(hb));
 }
-#ifndef X3D_HAND
-#define X3D_HAND 1       // development (REGTR_VARIANT_FLAGS=-DX3D_HAND=0): the compiler-scheduled k loop for A/B runs
-#endif
 
 // MW waves (4 or 8: 128- or 256-row tiles; the weight tile is shared by all of them, so twice the rows halve the weight traffic per
 // MFMA), CW 32-column blocks per wave, AR slots of the wave-private A ring (3: the A rows of tile t + 2 are in flight while tile t is
@@ -547,7 +544,7 @@ __global__ void __launch_bounds__(64 * MW, 2) k_gemm_x3d(X3Args g)
     constexpr int LDS_BYTES = RING_BYTES > STAT_BYTES ? RING_BYTES : STAT_BYTES;
     static_assert(NQ * 1024 * MW == B_BYTES && NQ >= 1, "the weight tile must split evenly over the waves");
     static_assert(AR == 2 || AR == 3 || AR == 4, "A ring mode");
-    static_assert(!IL || (NP == 3 && X3D_HAND), "the interleaved schedule exists in the hand-scheduled loop only");
+    static_assert(!IL || NP == 3, "the interleaved schedule exists in the hand-scheduled loop only");
     __shared__ __align__(1024) unsigned char sm[LDS_BYTES];   // [A ring: AR x BM rows x 128 B][weight ring: 2 x NP planes x BN x 64 B]
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -620,7 +617,7 @@ __global__ void __launch_bounds__(64 * MW, 2) k_gemm_x3d(X3Args g)
 #pragma unroll
         for (int r = 0; r < 16; r++) { acc[j][r] = 0.f; if (FMT == 1) acc_lo[FMT == 1 ? j : 0][r] = 0.f; }
 
-    if constexpr (NP == 3 && X3D_HAND) {
+    if constexpr (NP == 3) {
     // ---- hand-scheduled k loop.  Per 16-k step and column block: three fragment reads of the NEXT block are issued, the wait
     // leaves exactly those in flight, then the block's six MFMAs go out with the two halves of one float pair's split (of the next
     // step's A piece) behind the first two.  Register sets are static -- fa[2] (step parity), fb[2] (block parity), raw[2] -- and
@@ -655,26 +652,16 @@ __global__ void __launch_bounds__(64 * MW, 2) k_gemm_x3d(X3Args g)
     // the six MFMAs of column block J from fa[FS] x fb[CS] (smallest terms first) with the split of pairs PJ J .. of raw[FS ^ 1] behind them
     // H1 / H2: statements issued behind the fifth / sixth MFMA (the interleaved schedule's LDS-DMA instructions: their issue -- 16 cycles
     // of the CU's texture-address path each, more when eight waves queue up -- overlaps the 32 matrix-pipe cycles of the MFMA in front)
-#ifndef X3H_SPLIT_AFTER
-#define X3H_SPLIT_AFTER 0          // development A-B: 1 = the six MFMAs of a block back to back, the split and DMA instructions after them.
-                                   // Measured (gpurun_out/r03_z7, 18 shapes): 4953 vs 4788 us -- the VALU between same-accumulator MFMAs is
-                                   // not what the matrix pipe waits for here (two waves per SIMD fill each other's gaps); off
-#endif
+    // (Measured and dropped: the six MFMAs of a block back to back, the split and DMA instructions after them -- 4953 vs 4788 us over 18 shapes:
+    //  the VALU between same-accumulator MFMAs is not what the matrix pipe waits for here, two waves per SIMD fill each other's gaps.)
 #define X3H_BLOCKH(J, FS, CS, H1, H2) do { \
         const bf16x8 b0_ = __builtin_bit_cast(bf16x8, fbq[CS][0]), b1_ = __builtin_bit_cast(bf16x8, fbq[CS][1]), b2_ = __builtin_bit_cast(bf16x8, fbq[CS][2]); \
-        if (X3H_SPLIT_AFTER) { \
-            x3h_mfma(acc[J], fa[FS][2], b0_); x3h_mfma(acc[J], fa[FS][1], b1_); x3h_mfma(acc[J], fa[FS][0], b2_); \
-            x3h_mfma(acc[J], fa[FS][1], b0_); x3h_mfma(acc[J], fa[FS][0], b1_); x3h_mfma(acc[J], fa[FS][0], b0_); \
-            X3H_PAIR_A((FS) ^ 1, PJ * (J)); X3H_PAIR_B((FS) ^ 1, PJ * (J)); \
-            if (PJ == 2) { X3H_PAIR_A((FS) ^ 1, PJ * (J) + 1); X3H_PAIR_B((FS) ^ 1, PJ * (J) + 1); } \
-            H1; H2; \
-        } else { \
         x3h_mfma(acc[J], fa[FS][2], b0_); X3H_PAIR_A((FS) ^ 1, PJ * (J)); \
         x3h_mfma(acc[J], fa[FS][1], b1_); X3H_PAIR_B((FS) ^ 1, PJ * (J)); \
         x3h_mfma(acc[J], fa[FS][0], b2_); if (PJ == 2) X3H_PAIR_A((FS) ^ 1, PJ * (J) + 1); \
         x3h_mfma(acc[J], fa[FS][1], b0_); if (PJ == 2) X3H_PAIR_B((FS) ^ 1, PJ * (J) + 1); \
         x3h_mfma(acc[J], fa[FS][0], b1_); H1; \
-        x3h_mfma(acc[J], fa[FS][0], b0_); H2; } } while (0)
+        x3h_mfma(acc[J], fa[FS][0], b0_); H2; } while (0)
 #define X3H_BLOCK(J, FS, CS) X3H_BLOCKH(J, FS, CS, (void)0, (void)0)
     // one 16-k step KS of the current slot using fa[FS]; at its end fa[FS ^ 1] is complete.  _MID: the first block of the slot's next
     // step is prefetched behind the last block; _END: last step of a tile (the next tile's fragments need the barrier first).  LDS
@@ -792,7 +779,7 @@ __global__ void __launch_bounds__(64 * MW, 2) k_gemm_x3d(X3Args g)
         printf("x3d M %d N %d K %d MW %d CW %d AR %d blk %d wave %d nk %d: dma-issue %lld step0 %lld own-A-wait %lld step1 %lld sync %lld (cycles)\n", g.M, g.N, g.K,
                MW, CW, AR, (int)blockIdx.x, wave, nk, pt[0], pt[1], pt[2], pt[3], pt[4]);
 #endif
-    } else if constexpr (FMT == 1 && X3D_HAND) {
+    } else if constexpr (FMT == 1) {
     // ---- hand-scheduled k loop of the f16 pair format, 128 x 64 tiles.  The interleaved schedule of the bf16 loop above (two A slots, own
     // rows two tiles ahead, every LDS-DMA instruction issued between MFMAs), with TWO planes per operand and THREE MFMAs per column
     // block -- a0 w1 into the low accumulator, a0 w0 into the high one, a1 w0 into the low one -- and the f16 split of the next step's A
@@ -888,7 +875,7 @@ __global__ void __launch_bounds__(64 * MW, 2) k_gemm_x3d(X3Args g)
     }
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");          // MFMA results -> the epilogue's reads (the compiler does not see the MFMAs)
     } else {
-    // ---- compiler-scheduled k loop (one / two planes per operand: cfg.compute_dtype 'bf16' / 'bf16x2'; development builds -DX3D_HAND=0)
+    // ---- compiler-scheduled k loop (one / two planes per operand: cfg.compute_dtype 'bf16' / 'bf16x2')
     static_assert(AR == 2, "the compiler-scheduled loop uses the two-slot A ring");
     constexpr int PJ = 4 / CW;
     static_assert(CW == 2 || CW == 4, "the split is spread over 2 or 4 column blocks");
@@ -1467,21 +1454,6 @@ int regtr_gemm_x3_preferred(int M, int N, int K)
     return K >= 32 ? 1 : 0;
 }
 
-#ifdef REGTR_EXPERIMENTAL
-// Diagnostic: workgroups of the row-strip kernel the runtime will keep resident per CU (hipOccupancyMaxActiveBlocksPerMultiprocessor)
-// for column width cw (2 | 4 blocks of 32), A-ring mode ar (2 | 3; 4 = interleaved, cw 4 only) and the statistics epilogue; -1 = no such variant.
-int regtr_gemm_x3_strip_occupancy(int cw, int ar, int stats)
-{
-    int n = -1;
-    const void* k = nullptr;
-    if (cw == 4 && ar == 2) k = stats ? (const void*)k_gemm_x3d<4, 4, 2, true> : (const void*)k_gemm_x3d<4, 4, 2, false>;
-    else if (cw == 4 && ar == 4) k = stats ? (const void*)k_gemm_x3d<4, 4, 4, true> : (const void*)k_gemm_x3d<4, 4, 4, false>;
-    else if (cw == 2 && ar == 2) k = stats ? (const void*)k_gemm_x3d<4, 2, 2, true> : (const void*)k_gemm_x3d<4, 2, 2, false>;
-    else if (cw == 2 && ar == 3) k = stats ? (const void*)k_gemm_x3d<4, 2, 3, true> : (const void*)k_gemm_x3d<4, 2, 3, false>;
-    if (!k || hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, 256, 0) != hipSuccess) return -1;
-    return n;
-}
-#endif  // REGTR_EXPERIMENTAL
 
 size_t regtr_gemm_split_weights_bytes(int N, int K)
 {
@@ -1623,7 +1595,7 @@ int regtr_gemm_x3(const float* A, int lda, const void* planes, float* C, int ldc
     // Interleaved schedule (A two tiles ahead in TWO slots, every DMA instruction issued between MFMAs) for the 128 x 128 tile: measured
     // on the 18 RegTR shapes (gpurun_out/r03_z5) sum 4716 -> 4670 us, level-3 contraction 472 -> 458 us; on the 128 x 64 tile it loses
     // on the strided contractions (153 -> 165, 145 -> 151 us) and is not instantiated.  Hiding the ~1250-cycle DMA-issue phase bought
-    // 1 %, not the 30 % its share of a tile suggested: with two workgroups per CU (regtr_gemm_x3_strip_occupancy) that phase already
+    // 1 %, not the 30 % its share of a tile suggested: with two workgroups per CU (hipOccupancyMaxActiveBlocksPerMultiprocessor) that phase already
     // overlapped the other workgroup's MFMAs.
     if (strip && il && p.tile == 0) X3D_LAUNCH(4, 4, 4);
     else if (strip && p.tile == 0) X3D_LAUNCH(4, 4, 2);              // 128 x 128: 4 waves of 32 rows x 128 columns, both operands by LDS-DMA

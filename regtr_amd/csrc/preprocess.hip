@@ -218,9 +218,6 @@ __global__ void __launch_bounds__(256) k_clear_tables(const int* __restrict__ n_
     if (first) first[h] = 0x7F7F7F7F;
 }
 
-#ifndef RG_RANK2
-#define RG_RANK2 1            // development A/B (REGTR_VARIANT_FLAGS=-DRG_RANK2=0): for_each_ranked below
-#endif
 constexpr int CELL_BITS = 21;
 constexpr int64_t CELL_BIAS = 1 << 20;
 
@@ -605,7 +602,7 @@ template <typename F>
 __device__ __forceinline__ void for_each_ranked(uint64_t* list, int n, F&& f)
 {
     const int lane = rg_lane();
-    if (RG_RANK2 && n <= 32) {                       // wave-uniform
+    if (n <= 32) {                       // wave-uniform
         if (lane >= n && lane < 32) list[lane] = ~0ULL;
         __builtin_amdgcn_wave_barrier();
         const uint64_t mine = list[lane & 31];

@@ -393,7 +393,7 @@ class ResnetBottleneckBlock(nn.Module):
         # the fold (K <= 64); for the deeper levels (K >= 128) the fold would route the product to the tiled kernel (A staged through
         # registers, two barriers per k-tile: 246 us against 118 us for the same shape on the row-strip kernel at level 3), so the narrow
         # conv output is normalised in place first (one pass over [M, K]: 20-35 us) and the row-strip kernel multiplies it
-        if ops.preapply_unary2 and st is not None and x.shape[0] >= ops.PREAPPLY_MIN_ROWS and (ops.preapply_unary2 >= 2 or x.shape[1] > 64):
+        if st is not None and x.shape[0] >= ops.PREAPPLY_MIN_ROWS and x.shape[1] > 64:
             ops.instnorm_apply(x, v.seg_post, v.max_post, st, lrelu=True, out=x)
             st = None
         y, y_st = self.unary2.linear(x, v.seg_post, v.max_post, a_stats=st, a_seg_off=v.seg_post if st is not None else None)
@@ -459,7 +459,7 @@ class KPFEncoder(nn.Module):
     def _one_call_ok(self, x, meta):
         ctx = context.current()
         return bool(ops.use_one_call_encoder and ctx.gather_records is None and ctx.gemm_records is None and ctx.f16_range_log is None
-                    and not ops.force_f32_gemm and not ops.force_x3_gemm and ops.use_tile_info and ops.preapply_unary2 == 1
+                    and not ops.force_f32_gemm and not ops.force_x3_gemm
                     and meta['points'][0].shape[0] < min(ops.SMALL_REGIME_ROWS, ops.STREAM_MIN_ROWS) and x.dim() == 2 and x.is_contiguous() and x.data_ptr() % 16 == 0
                     and x.shape[0] > 0)
 

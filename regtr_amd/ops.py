@@ -6,7 +6,7 @@ import math
 
 import torch
 
-from . import _lib, context, devflags
+from . import _lib, context
 from ._lib import bptr, check, dptr, iptr, ptr, raw, stream
 
 
@@ -155,11 +155,9 @@ class SplitWeight:
 
 
 # float32-grade contractions as three f16 MFMA terms (the f16 pair split, csrc/gemm_x3.hip) where the row-strip kernel serves the shape,
-# instead of six (planes = 3) / three (planes = 2) bf16 terms.  f16_pair_default: what cfg.compute_dtype 'fp32' asks for (A-B runs:
-# REGTR_DEV=1 REGTR_F16_PAIR=0).  Whether a given launch takes the format is a field of the per-forward context (context.current().f16_pair, set by
-# RegTR.forward; `with ops.f16_pair(flag):` for tests and direct op calls) -- not a module global: two models on two host threads do not
-# share it.
-f16_pair_default = devflags.on('REGTR_F16_PAIR')
+# instead of six (planes = 3) / three (planes = 2) bf16 terms: what cfg.compute_dtype 'fp32' asks for.  Whether a given launch takes the format
+# is a field of the per-forward context (context.current().f16_pair, set by RegTR.forward; `with ops.f16_pair(flag):` for tests and direct op
+# calls) -- not a module global: two models on two host threads do not share it.
 _f16_shape = {}
 
 
@@ -258,7 +256,7 @@ def gemm(a, b, bias=None, row_div=None, residual=None, relu=False, out=None, a_s
             partial = torch.empty((((M + R - 1) // R + n_clouds) * N, 2), dtype=torch.float64, device=a.device)
         seg_rows = s_off if R else a_seg_off                    # the cloud table of the rows, when the launch needs one
         ti = None
-        if seg_rows is not None and use_tile_info and (a_seg_off is None or s_off is None or a_seg_off is s_off):
+        if seg_rows is not None and (a_seg_off is None or s_off is None or a_seg_off is s_off):
             ti = tile_segments(seg_rows, M, x3_rows)
         pl, npl = sw.planes, int(planes)
         if use_f16_pair and npl >= 2 and sw.f16_ok and f16_pair_ok(M, N, K, R > 0 or a_stats is not None or ti is not None):
@@ -409,23 +407,23 @@ STREAM_MIN_ROWS = 131072     # below this a forward is launch-bound (a pair or t
 # records / pre-normalised gather, no strip GEMM, no block tails) and the encoder's blocks go out through one C call (regtr_encoder_fwd).
 # Measured with the one-call encoder (profiles/r05_ab_h.txt: bench.py --pairs n, small regime forced on / off): 2 pairs 3.01 vs 3.30 ms, 3 pairs
 # 3.32 vs 3.50, 4 pairs 3.85 vs 3.67, 8 pairs 5.52 vs 5.33 -- the crossover sits between 114 k and 152 k rows.  (Round 4, op-by-op issue: 65536.)
-SMALL_REGIME_ROWS = int(devflags.flag('REGTR_SMALL_ROWS', '131072'))
-use_stream_gemm = devflags.on('REGTR_STREAM_GEMM')      # one-shot strip kernel for the shallow levels' Linears
-use_block_tail = devflags.on('REGTR_BLOCK_TAIL')        # resnet-block tail / first block from input moments (csrc/block_tail.hip)
+SMALL_REGIME_ROWS = 131072
+# Routing switches: plain module attributes, never read from the environment.  Tests and measure.py assign them to take the other path as the reference.
+use_stream_gemm = True      # one-shot strip kernel for the shallow levels' Linears
+use_block_tail = True       # resnet-block tail / first block from input moments (csrc/block_tail.hip)
 PRENORM_MIN_ROWS = 65536        # a LEVEL with fewer rows than this (of a large batch): the extra normalise pass costs more than the gather saves
-prenorm_gather = devflags.on('REGTR_PRENORM')           # unary1's IN + LReLU applied before the gather (packed support records)
-use_tile_info = devflags.on('REGTR_TILE_INFO')
-# unary2's folded InstanceNorm + LeakyReLU operand applied by a separate in-place pass instead (kpconv.py ResnetBottleneckBlock): 1 = where the
-# fold would route to the tiled kernel (K > 64), 2 = everywhere, 0 = never
-preapply_unary2 = int(devflags.flag('REGTR_PREAPPLY_UNARY2', '1'))
-PREAPPLY_MIN_ROWS = 8192        # (a pair or two per forward is launch-bound: the fold saves the extra launch there)
+prenorm_gather = True       # unary1's IN + LReLU applied before the gather (packed support records)
+# unary2's folded InstanceNorm + LeakyReLU operand is applied by a separate in-place pass instead where the fold would route to the tiled kernel
+# (K > 64) and the level has at least this many rows (kpconv.py ResnetBottleneckBlock; a pair or two per forward is launch-bound: the fold saves
+# the extra launch there)
+PREAPPLY_MIN_ROWS = 8192
 # csrc/encoder.hip sequences the small-batch regime with these rules compiled in (ENC_PREAPPLY_ROWS, no strip / block-tail form below
 # STREAM_MIN_ROWS): the one-call path equals the op-by-op path only while the gates nest like this (kpconv.KPFEncoder._one_call_ok)
-assert PREAPPLY_MIN_ROWS == 8192, 'csrc/encoder.hip compiles this gate in (ENC_PREAPPLY_ROWS)'      # (a REGTR_SMALL_ROWS override beyond STREAM_MIN_ROWS: _one_call_ok caps it)
+assert PREAPPLY_MIN_ROWS == 8192, 'csrc/encoder.hip compiles this gate in (ENC_PREAPPLY_ROWS)'      # (a SMALL_REGIME_ROWS beyond STREAM_MIN_ROWS: _one_call_ok caps it)
 # the six cross-encoder layers enqueued by one C call (regtr_cross_encoder_fwd) instead of 72 op calls
-use_one_call_cross_encoder = devflags.on('REGTR_ONE_CALL_XENC')
+use_one_call_cross_encoder = True
 # the encoder's blocks enqueued by one C call (regtr_encoder_fwd) in the small-batch regime (< 65536 level-0 rows) instead of ~130 op calls
-use_one_call_encoder = devflags.on('REGTR_ONE_CALL_ENC')
+use_one_call_encoder = True
 force_f32_gemm = False      # tests / A-B runs: route every GEMM to the exact-f32 MFMA kernel
 force_x3_gemm = False       # tests: route every supported shape to the split kernel, also where it is not the faster one
 

@@ -17,7 +17,7 @@ import threading
 import torch
 import torch.nn as nn
 
-from . import _lib, context, devflags, ops, overlap
+from . import _lib, context, ops, overlap
 from .config import as_config
 from .kpconv import KPFEncoder, PreprocessorGPU, _prepared
 from .transformer import TransformerCrossEncoder, TransformerCrossEncoderLayer
@@ -40,7 +40,7 @@ class PositionEmbeddingCoordsSine(nn.Module):
 
 
 # A-B switch and size gate of the two-stream forward (RegTR._forward)
-overlap_preprocessing = devflags.on('REGTR_OVERLAP')          # (read only under REGTR_DEV=1)
+overlap_preprocessing = True
 OVERLAP_MIN_POINTS = 131072
 
 
@@ -173,8 +173,8 @@ class RegTR(nn.Module):
             raise NotImplementedError(f'compute_dtype {dt!r}: choose fp32, fp32x3, bf16x2 or bf16')
         # (bf16 planes per operand where the f16 pair does not serve a launch: 'fp32' then means six terms, like 'fp32x3')
         encoder_layer.gemm_planes = {'fp32': 3, 'fp32x3': 3, 'bf16x2': 2, 'bf16': 1}[dt]
-        encoder_layer.attn_precision = 1 if dt == 'bf16' else (3 if (dt == 'fp32' and ops.f16_pair_default) else 0)      # ops.mha's codes
-        self._f16_pair = dt in ('fp32', 'bf16') and ops.f16_pair_default      # ('bf16': the encoder / head GEMMs, which stay float32-grade)
+        encoder_layer.attn_precision = 1 if dt == 'bf16' else (3 if dt == 'fp32' else 0)      # ops.mha's codes
+        self._f16_pair = dt in ('fp32', 'bf16')      # ('bf16': the encoder / head GEMMs, which stay float32-grade)
         self._range_check = bool(cfg.get('f16_range_check', True))
         self.f16_range_fallbacks = 0          # forwards re-run in fp32x3 arithmetic because an f16 pair operand left the format's range
         self.nonfinite_pose_forwards = 0      # forwards whose pose came out non-finite with every f16 pair product finite (bad inputs / weights)
@@ -230,7 +230,7 @@ class RegTR(nn.Module):
         79.98 ms under a world-1 process group against 77.84 ms without, the rocprofv3 trace showing no overlap at all (busy 78.2 ms inside 79.5 ms
         of wall time, against 84.4 inside 76.6).  A high-priority stream draws from its own queue pool: 78.20 / 77.94 ms (profiles/r05_z_dist_stream.txt)."""
         return _prepared(self._cache, ('side_stream', dev), self.feat_proj.bias,
-                         lambda _: torch.cuda.Stream(device=dev, priority=int(devflags.flag('REGTR_SIDE_PRIO', '-1'))))
+                         lambda _: torch.cuda.Stream(device=dev, priority=-1))
 
     @staticmethod
     def _record_meta(meta, stream):

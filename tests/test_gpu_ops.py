@@ -439,40 +439,6 @@ def test_fused_instnorm_paths_vs_oracle():
     assert (out2.cpu() - ref2).abs().max() < 3e-5 * max(1.0, ref2.abs().max().item())
 
 
-@pytest.mark.parametrize('nq_take', [1, 3])
-def test_kpconv_fused_vs_two_kernel_path(nq_take):
-    """regtr_kpconv_fused (level-0 shape: 32 -> 32 channels, weighted features kept in LDS) against gather + contraction, same inputs:
-    float32 rounding only.  Query counts that are not multiples of the workgroup's 256 (surplus waves run zero tiles).
-    The kernel is NOT in the product library (measured slower, docs/NEGATIVES.md): libregtr_hip.experimental.so, regtr_amd/experimental.py."""
-    from oracle import native
-    from regtr_amd import experimental
-    from regtr_amd.kernel_points import K015_CENTER
-    if not experimental.available():
-        pytest.skip('libregtr_hip.experimental.so not built (python -m regtr_amd.build --experimental)')
-    ops = _ops()
-    rng = np.random.default_rng(21)
-    clouds = [synth_cloud(rng, 3000), synth_cloud(rng, 2101) + 6.0]
-    s = np.concatenate(clouds).astype(np.float32); lens = np.array([3000, 2101], np.int32)
-    q = s[::nq_take].copy(); ql = np.array([len(range(0, 3000, nq_take)), len(s[::nq_take]) - len(range(0, 3000, nq_take))], np.int32)
-    if nq_take > 1:      # strided-style: queries are a subset; keep clouds separate
-        q = np.concatenate([clouds[0][::nq_take], clouds[1][::nq_take]]).astype(np.float32)
-        ql = np.array([len(clouds[0][::nq_take]), len(clouds[1][::nq_take])], np.int32)
-    r = 0.12
-    idx, _, _ = native.radius_neighbors(q, s, ql, lens, r, 40)
-    x = rng.standard_normal((len(s), 32)).astype(np.float32)
-    x[rng.random(len(s)) < 0.3] *= -1.0
-    w = (rng.standard_normal((15 * 32, 32)) / 20).astype(np.float32)
-    kp = (K015_CENTER * r).astype(np.float32)
-    xd = to_dev(x)
-    xyzf = torch.cat((to_dev(s), (xd.sum(1, keepdim=True) > 0).float()), 1).contiguous()
-    sw = ops.SplitWeight(to_dev(w), 'kn')
-    assert sw.planes is not None
-    args = (to_dev(q), to_dev(s), to_dev(idx), xd, sw, to_dev(kp), r * 0.8)
-    fused = experimental.kpconv_fused(args[0], args[2], xd, xyzf, sw, args[5], r * 0.8)       # the experiment library
-    plain = ops.kpconv(*args, xyzf=xyzf)                                                         # the product path
-    assert (fused - plain).abs().max().item() < 3e-6 * max(1.0, plain.abs().max().item())
-
-
 def test_maxpool_instnorm_vs_oracle():
     from oracle import native, regtr_ref
     ops = _ops()
@@ -595,43 +561,6 @@ def test_gemm_stream_vs_exact_f32(lens, K, N):
         rst = stats64(out, lens)       # float64 (regtr_instnorm_stats takes N / 4 a power of two only: not N = 96, 192)
         assert (st[..., 0].double() - rst[..., 0]).abs().max() <= 1e-6 * max(1.0, rst[..., 0].abs().max().item())
         assert ((st[..., 1].double() - rst[..., 1]).abs() <= 2e-6 * rst[..., 1].abs() + 1e-30).all()
-
-
-@pytest.mark.parametrize('lens', [[70000], [20000, 0, 33001, 12999], [300, 66000, 5], [1000] * 70])
-@pytest.mark.parametrize('linear_shortcut', [False, True])
-def test_block_tail_res_vs_separate_ops(lens, linear_shortcut):
-    """regtr_block_tail_res (level-1 resnet tails: unary2's statistics from the 64 x 64 second moments of its input, the product never
-    written, the finished second summand -- identity / max-pooled shortcut, or a Linear shortcut's product with its statistics --
-    added in the epilogue) against unary2 GEMM + instnorm_apply with the residual.  Experiment library only (measured slower,
-    docs/NEGATIVES.md): the product neither contains nor routes to it."""
-    from regtr_amd import experimental
-    if not experimental.available():
-        pytest.skip('libregtr_hip.experimental.so not built (python -m regtr_amd.build --experimental)')
-    ops = _ops()
-    rng = np.random.default_rng(len(lens) + 7)
-    M, K1, N = sum(lens), 64, 256
-    seg = seg_of(lens)
-    x1 = (rng.standard_normal((M, K1)) * rng.uniform(0.3, 3, K1) + rng.uniform(-2, 2, K1)).astype(np.float32)
-    x1[:, 9] = 0.5 * x1[:, 8] - 1.0                      # correlated channels: the covariance terms matter
-    res = (rng.standard_normal((M, N)) * rng.uniform(0.3, 2, N) + rng.uniform(-1, 1, N)).astype(np.float32)
-    w1 = (rng.standard_normal((N, K1)) / math.sqrt(K1)).astype(np.float32)
-    w1[11] *= 1e-3                                       # a nearly dead output column (eps dominates its rstd)
-    x1d, rd = to_dev(x1), to_dev(res)
-    sw1 = ops.SplitWeight(to_dev(w1), 'nk')
-    x1_st = ops.instnorm_stats(x1d, seg, max(lens))
-    r_st = ops.instnorm_stats(rd, seg, max(lens)) if linear_shortcut else None
-    y = experimental.block_tail_res(x1d, x1_st, sw1, rd, r_st, seg, max(lens))
-    u, u_st = ops.gemm(x1d, sw1, a_stats=x1_st, a_seg_off=seg, want_stats=(seg, max(lens)))
-    ref = ops.instnorm_apply(u, seg, max(lens), u_st, residual=rd, res_stats=r_st, lrelu=True)
-    assert (y - ref).abs().max().item() < 3e-5 * max(1.0, ref.abs().max().item())
-    # float64 reference of the whole expression on one cloud
-    from oracle import regtr_ref
-    L = torch.tensor(lens)
-    xn = torch.nn.functional.leaky_relu(regtr_ref.instance_norm(torch.from_numpy(x1).double(), L), 0.1)
-    un = regtr_ref.instance_norm(xn @ torch.from_numpy(w1).double().t(), L)
-    rn = regtr_ref.instance_norm(torch.from_numpy(res).double(), L) if linear_shortcut else torch.from_numpy(res).double()
-    want = torch.nn.functional.leaky_relu(un + rn, 0.1)
-    assert (y.cpu().double() - want).abs().max().item() < 5e-5 * max(1.0, want.abs().max().item())
 
 
 @pytest.mark.parametrize('lens,offset', [([70000], 0.0), ([20000, 0, 33001, 12999], 0.0), ([300, 66000, 5], 0.0), ([1000] * 70, 0.0),

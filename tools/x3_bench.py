@@ -38,7 +38,7 @@ def arm():
         kw = dict(a_stats=a_stats if s_in else None, a_seg_off=seg if s_in else None, want_stats=(seg, max_len) if s_out else None, planes=planes)
         ops.force_x3_gemm = True; ops.use_stream_gemm = False
         def run():
-            with ops.f16_pair(ops.f16_pair_default):          # (REGTR_F16_PAIR=0 / 1 arms)
+            with ops.f16_pair(True):
                 return ops.gemm(a, sw, **kw)
         for _ in range(3):
             run()
