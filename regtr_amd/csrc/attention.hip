@@ -13,10 +13,9 @@
 //   accumulator register s of this half-wave already corresponds to, so the probabilities never leave registers.
 // K / V tiles are staged through LDS with an odd row stride (33) so both fragment read patterns are conflict free.
 #include "common.h"
+#include "mfma_operands.h"
 
 namespace {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 constexpr int HD = 32;       // head dimension handled by this kernel
 constexpr int TQ = 32, TK = 32;
@@ -189,23 +188,11 @@ __global__ void __launch_bounds__(KS * RG_WAVE) __attribute__((amdgpu_waves_per_
 // half-wave hi is the key accumulator register 8 ks + j of that half-wave belongs to, so V^T is stored with its key columns
 // permuted accordingly (bits 2 and 3 of the key index swapped).  Scores carry log2(e): softmax uses the hardware exp2.
 // ------------------------------------------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
 constexpr int BW = 4;                 // waves (32-query tiles) per workgroup; clouds of more than 128 tokens: BW8 = 8 (round 6, below)
 constexpr int BW8 = 8;
 constexpr int BROW = 64;              // bytes per LDS row
 
-__device__ __forceinline__ unsigned bf_pack(float a, float b)
-{
-    bf16x2v v;
-    v.x = (__bf16)a; v.y = (__bf16)b;
-    return __builtin_bit_cast(unsigned, v);
-}
-// F16 (NP = 2): the f16 pair of gemm_x3.hip -- x = h0 + h1 / 2048, h0 = f16(x), h1 = f16((x - h0) * 2048): 22 mantissa bits in two planes,
-// three MFMA terms per product (the two low ones in a second accumulator, scaled by 1 / 2048 where it is read)
-typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
-constexpr float MHA_F16_SCALE = 2048.f;
+// F16 (NP = 2): the f16 pair of mfma_operands.h -- three MFMA terms per product, the two low ones in a second accumulator
 // development A-B switches (REGTR_VARIANT_FLAGS): measured on one box with tools/mha_bench.py (128 clouds of ~295 tokens), per launch:
 // accumulators in AGPRs (no register budget) 132-135 us, in VGPRs 126-130 us, + the last-tile-only key mask and the
 // v_permlane32_swap exchange 122-125 us.  (Vector conversions -- v_cvt_pk_f16_f32 -- for the pair split: no change, hipcc's SLP pass
@@ -216,37 +203,13 @@ constexpr float MHA_F16_SCALE = 2048.f;
 #ifndef MHA_WIDE_MIN_WG
 #define MHA_WIDE_MIN_WG 4096         // eight-wave workgroups only on launches with at least this many of them (A/B: -DMHA_WIDE_MIN_WG=..)
 #endif
-__device__ __forceinline__ unsigned f16_pack(float a, float b)
-{
-    f16x2v v;
-    v.x = (_Float16)a; v.y = (_Float16)b;
-    return __builtin_bit_cast(unsigned, v);
-}
-// (a, b) -> NP packed bf16 pairs; for NP = 3: a = a0 + a1 + a2 exactly (likewise b)
-template <int NP, bool F16 = false>
-__device__ __forceinline__ void bf_split2(float a, float b, unsigned (&p)[NP])
-{
-    if constexpr (F16) {
-        static_assert(NP == 2, "the f16 pair has two planes");
-        p[0] = f16_pack(a, b);
-        const f16x2v h = __builtin_bit_cast(f16x2v, p[0]);
-        p[1] = f16_pack((a - (float)h.x) * MHA_F16_SCALE, (b - (float)h.y) * MHA_F16_SCALE);
-        return;
-    }
-    p[0] = bf_pack(a, b);
-    if (NP > 1) {
-        const float ra = a - __uint_as_float(p[0] << 16), rb = b - __uint_as_float(p[0] & 0xffff0000u);
-        p[1] = bf_pack(ra, rb);
-        if (NP > 2) p[2] = bf_pack(ra - __uint_as_float(p[1] << 16), rb - __uint_as_float(p[1] & 0xffff0000u));
-    }
-}
 // 8 floats -> NP fragments of 8 bf16
 template <int NP, bool F16 = false>
 __device__ __forceinline__ void bf_split8(const float (&x)[8], bf16x8 (&f)[NP])
 {
     unsigned w[4][NP];
 #pragma unroll
-    for (int i = 0; i < 4; i++) bf_split2<NP, F16>(x[2 * i], x[2 * i + 1], w[i]);
+    for (int i = 0; i < 4; i++) rg_split2<NP, F16>(x[2 * i], x[2 * i + 1], w[i]);
 #pragma unroll
     for (int p = 0; p < NP; p++) f[p] = __builtin_bit_cast(bf16x8, make_uint4(w[0][p], w[1][p], w[2][p], w[3][p]));
 }
@@ -269,9 +232,9 @@ __device__ __forceinline__ floatx16 bf_mma(const bf16x8 (&a)[NP], const bf16x8 (
 // f16 pair product: hi += a0 b0, lo += a1 b0 + a0 b1 (alternating accumulators)
 __device__ __forceinline__ void f16_mma(const bf16x8 (&a)[2], const bf16x8 (&b)[2], floatx16& hi, floatx16& lo)
 {
-    lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8v, a[1]), __builtin_bit_cast(f16x8v, b[0]), lo, 0, 0, 0);
-    hi = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8v, a[0]), __builtin_bit_cast(f16x8v, b[0]), hi, 0, 0, 0);
-    lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8v, a[0]), __builtin_bit_cast(f16x8v, b[1]), lo, 0, 0, 0);
+    lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[1]), __builtin_bit_cast(f16x8, b[0]), lo, 0, 0, 0);
+    hi = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[0]), __builtin_bit_cast(f16x8, b[0]), hi, 0, 0, 0);
+    lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[0]), __builtin_bit_cast(f16x8, b[1]), lo, 0, 0, 0);
 }
 
 // combine a value of lane l with that of lane l ^ 32 (the two half-waves hold complementary key sets of the same 32 queries):
@@ -371,17 +334,17 @@ __global__ void __launch_bounds__(NW * RG_WAVE) MHA_WAVES_ATTR k_mha_fwd_bf16(Mh
     };
     auto stage = [&](const KV& r, int buf) {
         unsigned a[NP], b[NP];
-        bf_split2<NP, F16>(r.k.x, r.k.y, a);
+        rg_split2<NP, F16>(r.k.x, r.k.y, a);
         if constexpr (NW == 4) {
-            bf_split2<NP, F16>(r.k.z, r.k.w, b);
+            rg_split2<NP, F16>(r.k.z, r.k.w, b);
 #pragma unroll
             for (int p = 0; p < NP; p++) *(uint2*)(&Ks[buf][p][k_dst]) = make_uint2(a[p], b[p]);
         } else {
 #pragma unroll
             for (int p = 0; p < NP; p++) *(unsigned*)(&Ks[buf][p][k_dst]) = a[p];
         }
-        bf_split2<NP, F16>(r.v0.x, r.v1.x, a);        // (key 2u, key 2u + 1) of channel sd2
-        if constexpr (NW == 4) bf_split2<NP, F16>(r.v0.y, r.v1.y, b);        // ... of channel sd2 + 1
+        rg_split2<NP, F16>(r.v0.x, r.v1.x, a);        // (key 2u, key 2u + 1) of channel sd2
+        if constexpr (NW == 4) rg_split2<NP, F16>(r.v0.y, r.v1.y, b);        // ... of channel sd2 + 1
 #pragma unroll
         for (int p = 0; p < NP; p++) {
             *(unsigned*)(&Vt[buf][p][v_dst[0]]) = a[p];
@@ -439,8 +402,7 @@ __global__ void __launch_bounds__(NW * RG_WAVE) MHA_WAVES_ATTR k_mha_fwd_bf16(Mh
             //  tile next to 17 quarter-rate v_exp -- the softmax is what bounds this kernel at head dimension 32 -- and the packed form had 6-7 % fewer
             //  vector instructions but ran 2-4 % slower: docs/NEGATIVES.md.)
             if constexpr (F16) {
-#pragma unroll
-                for (int r = 0; r < 16; r++) sc[r] += sc_lo[r] * (1.0f / MHA_F16_SCALE);
+                rg_fold_low(sc, sc_lo);
             }
             MHA_STAMP(2);
             if (kt + TK > nk) {       // (workgroup-uniform: only the last tile of a cloud has keys past the end)
@@ -496,11 +458,8 @@ __global__ void __launch_bounds__(NW * RG_WAVE) MHA_WAVES_ATTR k_mha_fwd_bf16(Mh
     if constexpr (F16) {
         // a q / k / v value beyond f16's range converts to Inf (its residual to NaN): scores, and with them the outputs, come out
         // non-finite -- reported through the status word (x * 0 is NaN exactly for a non-finite x)
-        float chk = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; r++) { o[r] += o_lo[r] * (1.0f / MHA_F16_SCALE); chk = fmaf(o[r], 0.f, chk); }
-        chk = fmaf(l_run, 0.f, chk);
-        if (g.status && wave_live && chk != chk) atomicOr(g.status, REGTR_STATUS_F16_RANGE);
+        const float chk = fmaf(l_run, 0.f, rg_fold_low(o, o_lo));
+        rg_report_range(g.status, chk, wave_live);
     }
     const int qrow = q0 + l31;
     if (wave_live && qrow < q_end) {

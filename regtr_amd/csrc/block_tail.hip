@@ -20,12 +20,10 @@
 // Float32-grade like every dense op here: six bf16 MFMAs per product block; the statistics are those of the exact products (float64),
 // where the straightforward form takes them from float32-rounded values: the two agree to ~1e-7 relative.
 #include "common.h"
+#include "mfma_operands.h"
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int MO_WAVES = 4;
 constexpr int MO_ROWS_WAVE = 512;
@@ -179,20 +177,6 @@ __global__ void __launch_bounds__(MO_WAVES* RG_WAVE, 4) k_moments(const float* _
     }
 }
 
-__device__ __forceinline__ unsigned bt_pack(float a, float b)
-{
-    bf16x2 v;
-    v.x = (__bf16)a; v.y = (__bf16)b;
-    return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ void bt_split2(float a, float b, unsigned& p0, unsigned& p1, unsigned& p2)
-{
-    p0 = bt_pack(a, b);
-    const float ra = a - __uint_as_float(p0 << 16), rb = b - __uint_as_float(p0 & 0xffff0000u);
-    p1 = bt_pack(ra, rb);
-    p2 = bt_pack(ra - __uint_as_float(p1 << 16), rb - __uint_as_float(p1 & 0xffff0000u));
-}
-
 // One source of one cloud: covariance into LDS, then per output column j: mean / rstd of (x W)_j and the scaled + split weight row.
 // 256 threads = 64 columns x 4 row quarters; the workgroup covers columns [col0, col0 + 64).
 // planes[cloud][p][N][K] bf16 (k contiguous), in_mean[cloud][K], out_stats (optional) [cloud][N] (mean, rstd).
@@ -252,7 +236,7 @@ __device__ void bt_prepare_source(const double* __restrict__ partial, int n_chun
     uint16_t* row = planes + ((size_t)cloud * 3 * N + j) * K;        // plane p at + p N K
     for (int k = h * (K / 4); k < (h + 1) * (K / 4); k += 2) {
         unsigned p0, p1, p2;
-        bt_split2(W_kn[(size_t)k * N + j] * rstd, W_kn[(size_t)(k + 1) * N + j] * rstd, p0, p1, p2);   // (L1 hits)
+        rg_split2(W_kn[(size_t)k * N + j] * rstd, W_kn[(size_t)(k + 1) * N + j] * rstd, p0, p1, p2);   // (L1 hits)
         *(unsigned*)(row + k) = p0;
         *(unsigned*)(row + (size_t)N * K + k) = p1;
         *(unsigned*)(row + (size_t)2 * N * K + k) = p2;
@@ -319,7 +303,6 @@ __device__ __forceinline__ void ts_copy_planes(const uint16_t* __restrict__ src 
     // trips per thread, and the kernel has no registers to batch them in.)
     constexpr int CPR = 2 * KT, K = 16 * KT, NDMA = 3 * NB * CPR / RG_WAVE;
     static_assert(3 * NB * CPR % RG_WAVE == 0, "whole DMA instructions");
-    typedef __attribute__((address_space(3))) void* lds_ptr;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63;
 #pragma unroll 1                 // (rolled: a DMA returns nothing to wait for, and the addresses of nine of them at once would spill)
     for (int q0 = 0; q0 < NDMA; q0 += TS_WAVES) {
@@ -328,7 +311,7 @@ __device__ __forceinline__ void ts_copy_planes(const uint16_t* __restrict__ src 
             const int sidx = q * RG_WAVE + lane;
             const int p = sidx / (NB * CPR), rem = sidx - p * (NB * CPR), n = rem / CPR, cs = rem - n * CPR;
             __builtin_amdgcn_global_load_lds((const void*)(src + (size_t)p * plane + (size_t)n * K + (((unsigned)cs ^ ts_swz<KT>((unsigned)n)) * 8)),
-                                             (lds_ptr)(dst + (size_t)q * 1024), 16, 0, 0);
+                                             (rg_lds_ptr)(dst + (size_t)q * 1024), 16, 0, 0);
         }
     }
 }
@@ -417,10 +400,10 @@ __global__ void __launch_bounds__(TS_WAVES* RG_WAVE, NT <= 2 ? 4 : 2) k_tail_str
     }
     auto frag = [&](const float4 (&r)[2], bf16x8 (&fa)[3]) {
         unsigned w[4][3];
-        bt_split2(r[0].x, r[0].y, w[0][0], w[0][1], w[0][2]);
-        bt_split2(r[0].z, r[0].w, w[1][0], w[1][1], w[1][2]);
-        bt_split2(r[1].x, r[1].y, w[2][0], w[2][1], w[2][2]);
-        bt_split2(r[1].z, r[1].w, w[3][0], w[3][1], w[3][2]);
+        rg_split2(r[0].x, r[0].y, w[0]);
+        rg_split2(r[0].z, r[0].w, w[1]);
+        rg_split2(r[1].x, r[1].y, w[2]);
+        rg_split2(r[1].z, r[1].w, w[3]);
 #pragma unroll
         for (int p = 0; p < 3; p++) fa[p] = __builtin_bit_cast(bf16x8, make_uint4(w[0][p], w[1][p], w[2][p], w[3][p]));
     };

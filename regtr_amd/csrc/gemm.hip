@@ -16,10 +16,9 @@
 // Optional A-operand transform (per-cloud InstanceNorm + LeakyReLU folded into the load, kpconv_blocks.py:727-730):
 //   a[m,k] <- lrelu((a[m,k] - mean[cloud(m),k]) * rstd[cloud(m),k])
 #include "common.h"
+#include "mfma_operands.h"
 
 namespace {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 constexpr int BK = 32;
 constexpr int LDA_S = BK + 1;   // odd stride: A-fragment column reads hit 32 distinct banks

@@ -23,12 +23,9 @@
 //  the accumulators.  Both passes pay the split + MFMA work again (~350 us at level 0) and the residual tile next to four live
 //  accumulators spills: 0.33 + 1.75 ms against 0.41 + 0.71 ms for this kernel followed by k_instnorm_apply.)
 #include "common.h"
+#include "mfma_operands.h"
 
 namespace {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int SG_WAVES = 8;
 constexpr int SG_ROWS = 32 * SG_WAVES;       // rows per workgroup = statistics tile
@@ -43,20 +40,6 @@ struct SgArgs {
     int M, N, Kp, lda, ldc, n_seg;
     float a_slope;
 };
-
-__device__ __forceinline__ unsigned sg_pack(float a, float b)
-{
-    bf16x2 v;
-    v.x = (__bf16)a; v.y = (__bf16)b;
-    return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ void sg_split2(float a, float b, unsigned& p0, unsigned& p1, unsigned& p2)
-{
-    p0 = sg_pack(a, b);
-    const float ra = a - __uint_as_float(p0 << 16), rb = b - __uint_as_float(p0 & 0xffff0000u);
-    p1 = sg_pack(ra, rb);
-    p2 = sg_pack(ra - __uint_as_float(p1 << 16), rb - __uint_as_float(p1 & 0xffff0000u));
-}
 
 // LDS image of the weights: plane p, column n = one row of K bf16 (CPR = K / 8 sixteen-byte chunks); chunk c of row n sits at
 // c ^ swz(n), swz chosen so that the 16 lanes a ds_read_b128 services together (rows {0-3,12-15,20-27} / {4-11,16-19,28-31})
@@ -113,7 +96,6 @@ __global__ void __launch_bounds__(SG_WAVES* RG_WAVE, (KT <= 4 || NT <= 2) ? 4 : 
         //  s_waitcnt vmcnt(0) per piece: 11-40 k of a wave's ~50 k cycles, profiles/r04_strip_phase_clocks.md.)
         constexpr int NDMA = 3 * NB * CPR / RG_WAVE;
         static_assert(3 * NB * CPR % RG_WAVE == 0, "whole DMA instructions");
-        typedef __attribute__((address_space(3))) void* lds_ptr;
 #pragma unroll
         for (int q0 = 0; q0 < NDMA; q0 += SG_WAVES) {
             const int q = q0 + wave;
@@ -121,7 +103,7 @@ __global__ void __launch_bounds__(SG_WAVES* RG_WAVE, (KT <= 4 || NT <= 2) ? 4 : 
                 const int sidx = q * RG_WAVE + lane;
                 const int p = sidx / (NB * CPR), rem = sidx - p * (NB * CPR), n = rem / CPR, cs = rem - n * CPR;
                 const uint16_t* src = g.Wt + (size_t)p * g.plane + (size_t)(n0 + n) * g.Kp + (((unsigned)cs ^ sg_swz<KT>((unsigned)n)) * 8);
-                __builtin_amdgcn_global_load_lds((const void*)src, (lds_ptr)(Ws + (size_t)q * 1024), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((const void*)src, (rg_lds_ptr)(Ws + (size_t)q * 1024), 16, 0, 0);
             }
         }
     }
@@ -154,7 +136,7 @@ __global__ void __launch_bounds__(SG_WAVES* RG_WAVE, (KT <= 4 || NT <= 2) ? 4 : 
             }
             unsigned w[4][3];
 #pragma unroll
-            for (int e = 0; e < 4; e++) sg_split2(row_ok ? x[2 * e] : 0.f, row_ok ? x[2 * e + 1] : 0.f, w[e][0], w[e][1], w[e][2]);
+            for (int e = 0; e < 4; e++) rg_split2(row_ok ? x[2 * e] : 0.f, row_ok ? x[2 * e + 1] : 0.f, w[e]);
 #pragma unroll
             for (int p = 0; p < 3; p++) fa[ks][p] = __builtin_bit_cast(bf16x8, make_uint4(w[0][p], w[1][p], w[2][p], w[3][p]));
         }
@@ -279,9 +261,9 @@ int regtr_gemm_stream(const float* A, int lda, const void* planes, float* C, int
     if (a_stats && (K > 64 || ((uintptr_t)a_stats % 16))) return RG_ERR_ARG;
     if (stat_partial && ((uintptr_t)stat_partial % 16)) return RG_ERR_ARG;
     if (M == 0) return RG_OK;
-    const int Npad = rg_cdiv(N, 128) * 128, Kp = rg_cdiv(K, 32) * 32;
+    const RgPlaneDims pd = rg_plane_dims(N, K);
     SgArgs g{A, (const uint16_t*)planes, C, (const float2*)a_stats, seg_off, (const int4*)tile_info, (double2*)stat_partial,
-             (size_t)Npad * Kp, M, N, Kp, lda, ldc, n_seg, a_slope};
+             pd.elems(), M, N, pd.Kp, lda, ldc, n_seg, a_slope};
     const int NB = sg_cols_per_wg(N, K);
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = (size_t)3 * NB * K * 2 + (size_t)SG_WAVES * NB * 16;

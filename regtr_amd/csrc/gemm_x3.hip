@@ -7,7 +7,7 @@
 //     accumulator set scaled once in the epilogue (the scale keeps the residual plane out of f16's subnormal range).  Measured
 //     against float64 it is as accurate as the six-term form (fewer f32 accumulation roundings) at half the matrix-pipe work and
 //     two thirds of the weight bytes; operands must stay below 65504 (an overflow yields a non-finite result).  What
-//     cfg.compute_dtype 'fp32' uses; see x3_split2_f16, the FMT = 1 paths of both kernels and the f16 hand loop of k_gemm_x3d.
+//     cfg.compute_dtype 'fp32' uses; see rg_split2_f16 (mfma_operands.h), the FMT = 1 paths of both kernels and the f16 hand loop of k_gemm_x3d.
 //
 // gfx950 runs f32-input MFMA at 1/16 of its bf16 MFMA rate (157 TF vs 2.5 PF).  A float32 value is EXACTLY the sum of
 // three bf16 values (8 significant bits each):  x = x0 + x1 + x2,  x0 = bf16(x), x1 = bf16(x - x0), x2 = bf16(x - x0 - x1),
@@ -38,6 +38,7 @@
 // repeated by every wave sharing the rows, and these few-hundred-tile problems are bound by tile quantisation and L2
 // traffic of the 6-byte weight planes, not by prefetch depth.)
 #include "common.h"
+#include "mfma_operands.h"
 #include <stdlib.h>
 
 // Development switches of the tile planner (A/B sweeps: tools/x3_bench.py): read from the environment ONLY in variant builds
@@ -52,14 +53,8 @@ static inline int x3_dev_env(const char* name, int dflt) { const char* v = geten
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
 constexpr int XBK = 32;          // k per tile
 constexpr int XROW = 64;         // bytes per LDS row: 32 bf16, chunk-swizzled
-
-typedef __attribute__((address_space(3))) void* x3_lds_ptr;
 
 struct X3Args {
     const float* A; const uint16_t* Wt; float* C;
@@ -75,48 +70,92 @@ struct X3Args {
     int* status;                 // optional: REGTR_STATUS_F16_RANGE is OR-ed in when an f16 pair product came out non-finite
 };
 
-// f16 pair: an operand at or beyond f16's range converts to +-Inf and its residual plane to NaN, so every product of that row (or
-// column) is non-finite -- the raw accumulators tell.  x * 0 is 0 for a finite x and NaN otherwise: one FMA per accumulator value.
-__device__ __forceinline__ void x3_report_range(int* status, float chk)
+// Workgroup -> tile map, XCD aware: workgroup b runs on XCD b % 8 (each XCD has its own L2).  The nc column tiles
+// that share one A row-tile get the same b % 8 and consecutive b / 8, so the row-tile is fetched from HBM once and
+// hit in that XCD's L2 by the others; the weight planes are small enough to live in every L2.
+// False: the grid is rounded up to 8 row-tiles and this workgroup has none (the caller returns before any barrier: whole WG exits).
+template <int BM>
+__device__ __forceinline__ bool x3_tile_of_workgroup(int M, int nc, int& tile_m, int& tile_n)
 {
-    if (status && chk != chk) atomicOr(status, REGTR_STATUS_F16_RANGE);
+    const int b = blockIdx.x, x = b & 7, q = b >> 3;
+    tile_n = q % nc;
+    tile_m = (q / nc) * 8 + x;
+    return tile_m * BM < M;
 }
 
-__device__ __forceinline__ unsigned x3_pack(float a, float b)
+// Clouds of a row tile for the statistics epilogue: first / last cloud owning rows of the tile, the first cloud's row range
+struct X3StatRange { int lo, hi, lo_begin, lo_end; };
+
+// ONE 16-byte load where a per-level table exists (regtr_tile_segments, shared by every launch over the level's rows) instead of a chain of
+// dependent round trips (boundary search, then the found cloud's offsets): on the short-K launches that chain, times the rounds of
+// workgroups per CU, set the kernel's time.  Without the table: the clouds of the tile's first / last row, found by the whole wave in one
+// round trip each.
+template <int BM>
+__device__ __forceinline__ X3StatRange x3_stat_range(const X3Args& g, int tile_m)
 {
-    bf16x2 v;
-    v.x = (__bf16)a; v.y = (__bf16)b;            // v_cvt_pk_bf16_f32, round to nearest even
-    return __builtin_bit_cast(unsigned, v);
+    if (g.tile_info) {
+        const int4 ti = g.tile_info[tile_m];
+        return {ti.x, ti.y, ti.z, ti.w};
+    }
+    const int m0 = tile_m * BM, row_last = min(m0 + BM, g.M) - 1;
+    const int lo = rg_find_segment_wave(g.stat_seg_off, g.n_stat_seg, m0);
+    const int hi = rg_find_segment_wave(g.stat_seg_off, g.n_stat_seg, row_last);
+    return {lo, hi, g.stat_seg_off[lo], g.stat_seg_off[lo + 1]};
 }
 
-// (a, b) -> three packed bf16 pairs, a = a0 + a1 + a2 exactly (likewise b)
-__device__ __forceinline__ void x3_split2(float a, float b, unsigned& p0, unsigned& p1, unsigned& p2)
+// Weight streaming by LDS-DMA: instruction q of this wave fills LDS bytes [(wave NQ + q) 1024, +1024) of a weight buffer; lane i is slot
+// s = (wave NQ + q) 64 + i = ((p BN + n) 4 + pc), holding logical chunk pc ^ ((n >> 2) & 3) of column n, plane p (the swizzle is applied
+// to the per-lane SOURCE address).  b_src[q]: that lane's source at k = k_begin.
+template <int BN, int NQ>
+__device__ __forceinline__ void x3_weight_dma_src(const X3Args& g, int wave, int lane, int n0, int k_begin, const uint16_t* (&b_src)[NQ])
 {
-    p0 = x3_pack(a, b);
-    const float ra = a - __uint_as_float(p0 << 16), rb = b - __uint_as_float(p0 & 0xffff0000u);
-    p1 = x3_pack(ra, rb);
-    p2 = x3_pack(ra - __uint_as_float(p1 << 16), rb - __uint_as_float(p1 & 0xffff0000u));
+#pragma unroll
+    for (int q = 0; q < NQ; q++) {
+        const int sidx = (wave * NQ + q) * 64 + lane;
+        const int p = sidx / (BN * 4), r = sidx % (BN * 4), n = r >> 2, kc = (r & 3) ^ ((n >> 2) & 3);
+        b_src[q] = g.Wt + (size_t)p * g.plane + (size_t)(n0 + n) * g.Kp + kc * 8 + k_begin;
+    }
 }
 
-// ---- f16 pair split (operand format 1, "f16x2s"): x = h0 + h1 / 2048 with h0 = f16(x), h1 = f16((x - h0) * 2048) -- 22 mantissa bits in
-// TWO planes where the bf16 split needs three for 24.  A product is a0 w0 + (a0 w1 + a1 w0) / 2048 + O(2^-22 |a w|): THREE
-// v_mfma_f32_32x32x16_f16 instead of six bf16 ones, the two low terms in a second accumulator that is scaled once in the epilogue
-// (the scale keeps the low planes out of f16's subnormal range, where an unscaled residual of anything below 0.12 would sit).
-// Range: |x| < 65504 (f16); values below 6.1e-5 have a subnormal (coarse) h0 whose rounding the scaled h1 picks up again.
-typedef _Float16 x3_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 x3_f16x2 __attribute__((ext_vector_type(2)));
-constexpr float X3_F16_SCALE = 2048.f;
-__device__ __forceinline__ unsigned x3_pack_f16(float a, float b)
+// Raw float32 A rows by LDS-DMA (128 bytes per row and k-tile): instruction q of this wave fills rows 8 NA wave + 8 q + (lane >> 3) of the
+// tile, LDS chunk lane & 7 <- source chunk (lane & 7) ^ ((row >> 1) & 7).  Rows past M are clamped: they compute garbage that the epilogue
+// never stores.
+template <int NA>
+__device__ __forceinline__ void x3_raw_a_dma_src(const X3Args& g, int wave, int lane, int m0, int k_begin, const float* (&a_src)[NA])
 {
-    x3_f16x2 v;
-    v.x = (_Float16)a; v.y = (_Float16)b;
-    return __builtin_bit_cast(unsigned, v);
+#pragma unroll
+    for (int q = 0; q < NA; q++) {
+        const int r = wave * (8 * NA) + q * 8 + (lane >> 3);
+        const int row = m0 + r, rc = row < g.M ? row : g.M - 1;
+        a_src[q] = g.A + (size_t)rc * g.lda + k_begin + (((lane & 7) ^ ((r >> 1) & 7)) * 4);
+    }
 }
-__device__ __forceinline__ void x3_split2_f16(float a, float b, unsigned& p0, unsigned& p1)
+
+// Fragment byte offsets of a lane.  In a 64-byte-row image (weight planes; the split A planes of k_gemm_x3), 16-k step ks: row l31 of a
+// 32-row block, logical chunk 2 ks + hi.  In the raw A image, tile row r: the two 16-byte chunks 4 ks + 2 hi (+ 1) of the step, swizzled.
+__device__ __forceinline__ unsigned x3_frag_off(int l31, int hi, int ks)
 {
-    p0 = x3_pack_f16(a, b);
-    const x3_f16x2 h = __builtin_bit_cast(x3_f16x2, p0);
-    p1 = x3_pack_f16((a - (float)h.x) * X3_F16_SCALE, (b - (float)h.y) * X3_F16_SCALE);
+    return (unsigned)l31 * XROW + ((((unsigned)(2 * ks + hi)) ^ (((unsigned)l31 >> 2) & 3u)) * 16u);
+}
+__device__ __forceinline__ void x3_raw_a_frag_off(unsigned r, int hi, unsigned (&fa_off)[2][2])
+{
+    const unsigned sw = (r >> 1) & 7u;
+#pragma unroll
+    for (int ks = 0; ks < 2; ks++)
+#pragma unroll
+        for (int h = 0; h < 2; h++) fa_off[ks][h] = r * 128u + ((((unsigned)(4 * ks + 2 * hi + h)) ^ sw) * 16u);
+}
+
+// The epilogue's arithmetic on one value: C = act(acc / row_div + bias) + residual (an absent bias is bv = 0; rd / rs are read only where
+// the launch has the operand).  The product kernels load rd / rs from CLAMPED rows, a block's loads in flight before the first use: a load
+// under the per-lane `row < M` predicate compiles to load + s_waitcnt vmcnt(0) -- sixteen serial memory round trips per column block.
+__device__ __forceinline__ float x3_finish(const X3Args& g, float v, float rd, float bv, float rs)
+{
+    if (g.row_div) v = v / rd;
+    v += bv;
+    if (g.act == 1) v = fmaxf(v, 0.f);
+    if (g.residual) v += rs;
+    return v;
 }
 
 // NP = bf16 planes per operand: 3 = float32-grade (six MFMA terms, the default); 2 = the three leading terms a0 w0 + a0 w1 +
@@ -139,16 +178,8 @@ __global__ void __launch_bounds__(64 * MW * NW, (MW * NW >= 8) ? 4 : 2) k_gemm_x
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);      // wave-uniform (SGPR): LDS-DMA bases live in M0
     const int wm = wave / NW, wn = wave % NW;
     const int l31 = lane & 31, hi = lane >> 5;
-    // Workgroup -> tile map, XCD aware: workgroup b runs on XCD b % 8 (each XCD has its own L2).  The N / BN column tiles
-    // that share one A row-tile get the same b % 8 and consecutive b / 8, so the row-tile is fetched from HBM once and
-    // hit in that XCD's L2 by the others; the weight planes are small enough to live in every L2.
     int tile_m, tile_n;
-    {
-        const int nc = g.N / BN, b = blockIdx.x, x = b & 7, q = b >> 3;
-        tile_n = q % nc;
-        tile_m = (q / nc) * 8 + x;
-        if (tile_m * BM >= g.M) return;            // grid is rounded up to 8 row-tiles (before any barrier: whole WG exits)
-    }
+    if (!x3_tile_of_workgroup<BM>(g.M, g.N / BN, tile_m, tile_n)) return;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const int k_begin = blockIdx.z * g.k_chunk;
     const int k_end = min(g.K, k_begin + g.k_chunk);
@@ -160,33 +191,20 @@ __global__ void __launch_bounds__(64 * MW * NW, (MW * NW >= 8) ? 4 : 2) k_gemm_x
     const float* a_ptr[AV];
     const float2* st_ptr[AV];
     bool a_ok[AV];
-    // clouds of the tile's first / last row, found by the whole wave in one round trip each; almost every tile lies inside
+    // clouds of the tile's first / last row (of the folded operand's statistics: seg_first / seg_last); almost every tile lies inside
     // one cloud, and only rows of a straddling tile pay the per-lane binary search (log2(n) dependent loads)
     // The epilogue's cloud range (SOUT) is looked up here too, so that its round trips overlap the first operand loads
     // instead of being a serial tail: on the short-K GEMMs the per-workgroup chain of dependent memory round trips, not
     // bandwidth or MFMA, sets the time.
-    int seg_first = 0, seg_last = 0, s_lo = 0, s_hi = 0, s_lo_begin = 0, s_lo_end = 0;
-    const int row_last = min(m0 + BM, g.M) - 1;
-    if ((SOUT || STATS) && g.tile_info) {
-        // ONE 16-byte load instead of a chain of dependent round trips (boundary search, then the found cloud's offsets): on the
-        // short-K launches that chain, times the rounds of workgroups per CU, set the kernel's time.  The table is per level
-        // (regtr_tile_segments), shared by every launch over the level's rows.
-        const int4 ti = g.tile_info[tile_m];
-        s_lo = ti.x; s_hi = ti.y; s_lo_begin = ti.z; s_lo_end = ti.w;
-        seg_first = s_lo; seg_last = s_hi;
-    } else {
-    if (SOUT) {
-        s_lo = rg_find_segment_wave(g.stat_seg_off, g.n_stat_seg, m0);
-        s_hi = rg_find_segment_wave(g.stat_seg_off, g.n_stat_seg, row_last);
-        s_lo_begin = g.stat_seg_off[s_lo]; s_lo_end = g.stat_seg_off[s_lo + 1];
-    }
+    X3StatRange sr{0, 0, 0, 0};
+    int seg_first = 0, seg_last = 0;
+    if (SOUT || (STATS && g.tile_info)) sr = x3_stat_range<BM>(g, tile_m);
     if (STATS) {
-        if (SOUT && g.a_seg_off == g.stat_seg_off && g.n_seg == g.n_stat_seg) { seg_first = s_lo; seg_last = s_hi; }
+        if (g.tile_info || (SOUT && g.a_seg_off == g.stat_seg_off && g.n_seg == g.n_stat_seg)) { seg_first = sr.lo; seg_last = sr.hi; }
         else {
             seg_first = rg_find_segment_wave(g.a_seg_off, g.n_seg, m0);
-            seg_last = rg_find_segment_wave(g.a_seg_off, g.n_seg, row_last);
+            seg_last = rg_find_segment_wave(g.a_seg_off, g.n_seg, min(m0 + BM, g.M) - 1);
         }
-    }
     }
 #pragma unroll
     for (int i = 0; i < AV; i++) {
@@ -233,27 +251,20 @@ __global__ void __launch_bounds__(64 * MW * NW, (MW * NW >= 8) ? 4 : 2) k_gemm_x
             const bool ok = a_ok[i] && ra_kin;
             v = make_float4(ok ? v.x : 0.f, ok ? v.y : 0.f, ok ? v.z : 0.f, ok ? v.w : 0.f);
             unsigned p0a, p1a, p2a = 0, p0b, p1b, p2b = 0;
-            if (FMT == 1) { x3_split2_f16(v.x, v.y, p0a, p1a); x3_split2_f16(v.z, v.w, p0b, p1b); }
-            else { x3_split2(v.x, v.y, p0a, p1a, p2a); x3_split2(v.z, v.w, p0b, p1b, p2b); }
+            if (FMT == 1) { rg_split2_f16(v.x, v.y, p0a, p1a); rg_split2_f16(v.z, v.w, p0b, p1b); }
+            else { rg_split2(v.x, v.y, p0a, p1a, p2a); rg_split2(v.z, v.w, p0b, p1b, p2b); }
             unsigned char* dst = As + a_st_off + i * RPP * XROW;
             *(uint2*)(dst) = make_uint2(p0a, p0b);
             if (NP > 1) *(uint2*)(dst + BM * XROW) = make_uint2(p1a, p1b);
             if (NP > 2) *(uint2*)(dst + 2 * BM * XROW) = make_uint2(p2a, p2b);
         }
     };
-    // ---- B streaming: DMA q of this wave fills LDS bytes [(wave NQ + q) 1024, +1024) of the buffer; lane i is slot
-    // s = (wave NQ + q) 64 + i = ((p BN + n) 4 + pc), holding logical chunk pc ^ ((n >> 2) & 3) of column n, plane p
     const uint16_t* b_src[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; q++) {
-        const int sidx = (wave * NQ + q) * 64 + lane;
-        const int p = sidx / (BN * 4), r = sidx % (BN * 4), n = r >> 2, kc = (r & 3) ^ ((n >> 2) & 3);
-        b_src[q] = g.Wt + (size_t)p * g.plane + (size_t)(n0 + n) * g.Kp + kc * 8;
-    }
+    x3_weight_dma_src<BN>(g, wave, lane, n0, 0, b_src);
     auto dma_b = [&](int k0, unsigned char* Bb) {
 #pragma unroll
         for (int q = 0; q < NQ; q++)
-            __builtin_amdgcn_global_load_lds((const void*)(b_src[q] + k0), (x3_lds_ptr)(Bb + (wave * NQ + q) * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((const void*)(b_src[q] + k0), (rg_lds_ptr)(Bb + (wave * NQ + q) * 1024), 16, 0, 0);
     };
 
     floatx16 acc[WM][WN];
@@ -265,10 +276,9 @@ __global__ void __launch_bounds__(64 * MW * NW, (MW * NW >= 8) ? 4 : 2) k_gemm_x
 #pragma unroll
             for (int r = 0; r < 16; r++) { acc[i][j][r] = 0.f; if (FMT == 1) acc_lo[FMT == 1 ? i : 0][FMT == 1 ? j : 0][r] = 0.f; }
 
-    // fragment byte offset of this lane within a 32-row block: row l31, logical chunk (2 ks + hi)
     unsigned f_off[XBK / 16];
 #pragma unroll
-    for (int ks = 0; ks < XBK / 16; ks++) f_off[ks] = (unsigned)l31 * XROW + ((((unsigned)(2 * ks + hi)) ^ (((unsigned)l31 >> 2) & 3u)) * 16u);
+    for (int ks = 0; ks < XBK / 16; ks++) f_off[ks] = x3_frag_off(l31, hi, ks);
 
     auto compute = [&](const unsigned char* Bb) {
 #pragma unroll
@@ -292,8 +302,8 @@ __global__ void __launch_bounds__(64 * MW * NW, (MW * NW >= 8) ? 4 : 2) k_gemm_x
 #define X3_TERM_F16(ACC, PA, PB)                                                                                    \
             _Pragma("unroll") for (int i = 0; i < WM; i++)                                                           \
                 _Pragma("unroll") for (int j = 0; j < WN; j++)                                                       \
-                    ACC[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(x3_f16x8, fa[i][PA]),      \
-                                                                       __builtin_bit_cast(x3_f16x8, fb[j][PB]), ACC[i][j], 0, 0, 0);
+                    ACC[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[i][PA]),      \
+                                                                       __builtin_bit_cast(f16x8, fb[j][PB]), ACC[i][j], 0, 0, 0);
             if constexpr (FMT == 1) { X3_TERM_F16(acc_lo, 1, 0) X3_TERM_F16(acc, 0, 0) X3_TERM_F16(acc_lo, 0, 1) }
             else {
             if (NP == 3) { X3_TERM(2, 0) X3_TERM(1, 1) X3_TERM(0, 2) }
@@ -339,10 +349,8 @@ __global__ void __launch_bounds__(64 * MW * NW, (MW * NW >= 8) ? 4 : 2) k_gemm_x
 #pragma unroll
         for (int i = 0; i < WM; i++)
 #pragma unroll
-            for (int j = 0; j < WN; j++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) { acc[i][j][r] += acc_lo[i][j][r] * (1.0f / X3_F16_SCALE); chk = fmaf(acc[i][j][r], 0.f, chk); }
-        x3_report_range(g.status, chk);
+            for (int j = 0; j < WN; j++) chk = rg_fold_low(acc[i][j], acc_lo[i][j], chk);
+        rg_report_range(g.status, chk);
     }
     // ---- epilogue (C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5))
 #pragma unroll
@@ -361,8 +369,8 @@ __global__ void __launch_bounds__(64 * MW * NW, (MW * NW >= 8) ? 4 : 2) k_gemm_x
                 continue;
             }
             const float bv = g.bias ? g.bias[col] : 0.f;
-            // row_div / residual from clamped rows, eight rows' loads in flight at once (see k_gemm_x3d's epilogue; eight, not
-            // sixteen: the <2,4,..> variants sit at their 128-register launch bound)
+            // row_div / residual from clamped rows, eight rows' loads in flight at once (x3_finish; eight, not sixteen: the <2,4,..>
+            // variants sit at their 128-register launch bound)
 #pragma unroll
             for (int h = 0; h < 2; h++) {
                 float rd[8], rs[8];
@@ -380,17 +388,14 @@ __global__ void __launch_bounds__(64 * MW * NW, (MW * NW >= 8) ? 4 : 2) k_gemm_x
 #pragma unroll
                 for (int q = 0; q < 8; q++) {
                     const int r = 8 * h + q, row = rbase + (r & 3) + 8 * (r >> 2);
-                    float v = acc[i][j][r];
-                    if (g.row_div) v = v / rd[q];
-                    v += bv;
-                    if (g.act == 1) v = fmaxf(v, 0.f);
-                    if (g.residual) v += rs[q];
+                    const float v = x3_finish(g, acc[i][j][r], rd[q], bv, rs[q]);
                     if (row >= g.M) continue;
                     g.C[(size_t)row * g.ldc + col] = v;
                     if (SOUT) acc[i][j][r] = v;
                 }
             }
         }
+
 
     // ---- optional: InstanceNorm statistics of the rows just produced (kpconv_blocks.py:510-519), so that no separate
     // pass re-reads C.  For every cloud s that owns rows of this tile: per-column (sum, sum of squares) in float64 over
@@ -399,9 +404,9 @@ __global__ void __launch_bounds__(64 * MW * NW, (MW * NW >= 8) ? 4 : 2) k_gemm_x
     // statistics kernel.
     if (SOUT) {
         double2* red = (double2*)As;                       // [MW][BN], As is free after the last barrier of the k loop
-        for (int sg = s_lo; sg <= s_hi; sg++) {            // workgroup-uniform; one cloud per tile almost always
-            const int r_lo = sg == s_lo ? s_lo_begin : g.stat_seg_off[sg];
-            const int r_hi = min(sg == s_lo ? s_lo_end : g.stat_seg_off[sg + 1], g.M);
+        for (int sg = sr.lo; sg <= sr.hi; sg++) {            // workgroup-uniform; one cloud per tile almost always
+            const int r_lo = sg == sr.lo ? sr.lo_begin : g.stat_seg_off[sg];
+            const int r_hi = min(sg == sr.lo ? sr.lo_end : g.stat_seg_off[sg + 1], g.M);
 #pragma unroll
             for (int j = 0; j < WN; j++) {
                 double sm = 0.0, sq = 0.0;
@@ -426,8 +431,6 @@ __global__ void __launch_bounds__(64 * MW * NW, (MW * NW >= 8) ? 4 : 2) k_gemm_x
         }
     }
 }
-
-typedef float x3_f4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ void x3_asm_dma16(const void* gsrc, unsigned lds_dst)
 {
@@ -474,7 +477,7 @@ __device__ __forceinline__ void x3h_lds128(uint4& d, unsigned addr)
 {
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF));
 }
-// first half of the exact three-way split of a float pair: p0 = bf16 pair, (ra, rb) = residuals
+// first half of the exact three-way split of a float pair: p0 = bf16 pair, (ra, rb) = residuals.  With x3h_split_b it must equal rg_split2.
 __device__ __forceinline__ void x3h_split_a(float a, float b, unsigned& p0, float& ra, float& rb)
 {
     unsigned t0, t1;
@@ -498,13 +501,12 @@ __device__ __forceinline__ void x3h_split_b(float ra, float rb, unsigned& p1, un
                  "v_cvt_pk_bf16_f32 %1, %4, %5"
                  : "=&v"(p1), "=&v"(p2), "=&v"(t0), "=&v"(t1), "=&v"(sa), "=&v"(sb) : "v"(ra), "v"(rb));
 }
-#define X3H_LGKM(N) asm volatile("s_waitcnt lgkmcnt(%0)" :: "n"(N) : "memory")
 // ---- the same for the f16 pair format (three MFMA terms; x = h0 + h1 / 2048)
 __device__ __forceinline__ void x3h_mfma_f16(floatx16& c, const bf16x8& a, const bf16x8& b)      // (operands are eight f16; the type only carries the bits)
 {
     asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
 }
-// first half of the split of a float pair: p0 = f16 pair, (ha, hb) = its two values back in float32
+// first half of the split of a float pair: p0 = f16 pair, (ha, hb) = its two values back in float32.  With x3h_splitf_b it must equal rg_split2_f16.
 __device__ __forceinline__ void x3h_splitf_a(float a, float b, unsigned& p0, float& ha, float& hb)
 {
     asm volatile("v_cvt_pk_f16_f32 %0, %3, %4\n\t"
@@ -512,7 +514,7 @@ __device__ __forceinline__ void x3h_splitf_a(float a, float b, unsigned& p0, flo
                  "v_cvt_f32_f16_sdwa %2, %0 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1"
                  : "=&v"(p0), "=&v"(ha), "=&v"(hb) : "v"(a), "v"(b));
 }
-// second half: p1 = f16 pair of the residuals scaled by 2048 (0x45000000)
+// second half: p1 = f16 pair of the residuals scaled by RG_F16_SCALE (0x45000000)
 __device__ __forceinline__ void x3h_splitf_b(float a, float b, float ha, float hb, unsigned& p1)
 {
     float t0, t1;
@@ -549,46 +551,20 @@ __global__ void __launch_bounds__(64 * MW, 2) k_gemm_x3d(X3Args g)
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int l31 = lane & 31, hi = lane >> 5;
-    int tile_m, tile_n;
-    {
-        const int nc = (g.N + BN - 1) / BN, b = blockIdx.x, x = b & 7, q = b >> 3;       // XCD-aware map, as in k_gemm_x3
-        tile_n = q % nc;                                       // (N = 32: one 64-column tile whose upper half multiplies the planes' zero padding)
-        tile_m = (q / nc) * 8 + x;
-        if (tile_m * BM >= g.M) return;
-    }
+    int tile_m, tile_n;                                        // (N = 32: one 64-column tile whose upper half multiplies the planes' zero padding)
+    if (!x3_tile_of_workgroup<BM>(g.M, (g.N + BN - 1) / BN, tile_m, tile_n)) return;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const int k_begin = blockIdx.z * g.k_chunk;
     const int k_end = min(g.K, k_begin + g.k_chunk);
     const int nk = (k_end - k_begin) / XBK;                    // whole k-tiles only (the launcher checks)
 
-    int s_lo = 0, s_hi = 0, s_lo_begin = 0, s_lo_end = 0;
-    if (SOUT) {
-        if (g.tile_info) {
-            const int4 ti = g.tile_info[tile_m];
-            s_lo = ti.x; s_hi = ti.y; s_lo_begin = ti.z; s_lo_end = ti.w;
-        } else {
-            const int row_last = min(m0 + BM, g.M) - 1;
-            s_lo = rg_find_segment_wave(g.stat_seg_off, g.n_stat_seg, m0);
-            s_hi = rg_find_segment_wave(g.stat_seg_off, g.n_stat_seg, row_last);
-            s_lo_begin = g.stat_seg_off[s_lo]; s_lo_end = g.stat_seg_off[s_lo + 1];
-        }
-    }
-    // ---- A DMA: instruction q of this wave fills rows 32 wave + 8 q + (lane >> 3), LDS slot lane & 7 <- source chunk slot ^ ((row >> 1) & 7)
+    X3StatRange sr{0, 0, 0, 0};
+    if (SOUT) sr = x3_stat_range<BM>(g, tile_m);
     const float* a_src[NA];
-#pragma unroll
-    for (int q = 0; q < NA; q++) {
-        const int r = wave * 32 + q * 8 + (lane >> 3);
-        const int row = m0 + r, rc = row < g.M ? row : g.M - 1;    // rows past M compute garbage that the epilogue never stores
-        a_src[q] = g.A + (size_t)rc * g.lda + k_begin + (((lane & 7) ^ ((r >> 1) & 7)) * 4);
-    }
+    x3_raw_a_dma_src(g, wave, lane, m0, k_begin, a_src);
     const uint16_t* b_src[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; q++) {
-        const int sidx = (wave * NQ + q) * 64 + lane;
-        const int p = sidx / (BN * 4), r = sidx % (BN * 4), n = r >> 2, kc = (r & 3) ^ ((n >> 2) & 3);
-        b_src[q] = g.Wt + (size_t)p * g.plane + (size_t)(n0 + n) * g.Kp + kc * 8 + k_begin;
-    }
-    const unsigned lds_base = (unsigned)(unsigned long long)(x3_lds_ptr)(&sm[0]);
+    x3_weight_dma_src<BN>(g, wave, lane, n0, k_begin, b_src);
+    const unsigned lds_base = (unsigned)(unsigned long long)(rg_lds_ptr)(&sm[0]);
     const unsigned a_wave = lds_base + (unsigned)wave * (NA * 1024u);             // this wave's 4 KiB of an A slot
     const unsigned b_wave = lds_base + A_RING + (unsigned)wave * (NQ * 1024u);    // this wave's share of a weight slot
     auto dma_a = [&](int kt, unsigned slot) {                  // own A rows of k-tile kt -> A slot
@@ -599,17 +575,10 @@ __global__ void __launch_bounds__(64 * MW, 2) k_gemm_x3d(X3Args g)
 #pragma unroll
         for (int q = 0; q < NQ; q++) x3_asm_dma16((const void*)(b_src[q] + kt * XBK), b_wave + slot * B_BYTES + q * 1024u);
     };
-    // fragment addresses: A row 32 wave + l31, 16-byte chunks 4 ks + 2 hi (+ 1), swizzled; B as in k_gemm_x3
-    unsigned fa_off[2][2], f_off[2];
-    {
-        const unsigned r = (unsigned)wave * 32u + (unsigned)l31, sw = (r >> 1) & 7u;
+    unsigned fa_off[2][2], f_off[2];                           // fragment addresses: A row 32 wave + l31
+    x3_raw_a_frag_off((unsigned)wave * 32u + (unsigned)l31, hi, fa_off);
 #pragma unroll
-        for (int ks = 0; ks < 2; ks++) {
-#pragma unroll
-            for (int h = 0; h < 2; h++) fa_off[ks][h] = r * 128u + ((((unsigned)(4 * ks + 2 * hi + h)) ^ sw) * 16u);
-            f_off[ks] = (unsigned)l31 * XROW + ((((unsigned)(2 * ks + hi)) ^ (((unsigned)l31 >> 2) & 3u)) * 16u);
-        }
-    }
+    for (int ks = 0; ks < 2; ks++) f_off[ks] = x3_frag_off(l31, hi, ks);
     floatx16 acc[CW];
     floatx16 acc_lo[FMT == 1 ? CW : 1];                         // f16 pair: the two scaled low terms
 #pragma unroll
@@ -617,6 +586,12 @@ __global__ void __launch_bounds__(64 * MW, 2) k_gemm_x3d(X3Args g)
 #pragma unroll
         for (int r = 0; r < 16; r++) { acc[j][r] = 0.f; if (FMT == 1) acc_lo[FMT == 1 ? j : 0][r] = 0.f; }
 
+    // plumbing shared by the two hand-scheduled loops: counted waits, the barrier, the two reads of an A piece, weight DMA I of tile kt + 1
+#define X3H_LGKM(N) asm volatile("s_waitcnt lgkmcnt(%0)" :: "n"(N) : "memory")
+#define X3H_VM(N) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory")
+#define X3H_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
+#define X3H_RAW(KS, SET) do { x3h_lds128<0>(rawq[SET][0], va[KS][0]); x3h_lds128<0>(rawq[SET][1], va[KS][1]); } while (0)
+#define X3H_DB(I) do { if ((I) < NQ && more_b) x3_asm_dma16((const void*)(b_src[(I) < NQ ? (I) : 0] + (kt + 1) * XBK), b_wave + b_slot * B_BYTES + (I) * 1024u); } while (0)
     if constexpr (NP == 3) {
     // ---- hand-scheduled k loop.  Per 16-k step and column block: three fragment reads of the NEXT block are issued, the wait
     // leaves exactly those in flight, then the block's six MFMAs go out with the two halves of one float pair's split (of the next
@@ -643,7 +618,6 @@ __global__ void __launch_bounds__(64 * MW, 2) k_gemm_x3d(X3Args g)
 #define X3H_FB(KS, J, SET) do { x3h_lds128<(0 * BN + (J) * 32) * XROW>(fbq[SET][0], vb[KS]); \
                                 x3h_lds128<(1 * BN + (J) * 32) * XROW>(fbq[SET][1], vb[KS]); \
                                 x3h_lds128<(2 * BN + (J) * 32) * XROW>(fbq[SET][2], vb[KS]); } while (0)
-#define X3H_RAW(KS, SET) do { x3h_lds128<0>(rawq[SET][0], va[KS][0]); x3h_lds128<0>(rawq[SET][1], va[KS][1]); } while (0)
 #define X3H_PAIR_A(SET, Q) do { const uint4 v_ = rawq[SET][(Q) >> 1]; \
         x3h_split_a(__uint_as_float(((Q) & 1) ? v_.z : v_.x), __uint_as_float(((Q) & 1) ? v_.w : v_.y), pl[SET][0][Q], ra, rb); } while (0)
 #define X3H_PAIR_B(SET, Q) x3h_split_b(ra, rb, pl[SET][1][Q], pl[SET][2][Q])
@@ -691,7 +665,6 @@ __global__ void __launch_bounds__(64 * MW, 2) k_gemm_x3d(X3Args g)
         X3H_PACK((FS) ^ 1); } while (0)
     // the interleaved schedule's steps: step 0 of a tile carries the NQ weight DMAs of tile t + 1 (X3H_DB), step 1 the NA own-row DMAs of
     // tile t + 2 (X3H_DA), two per column block at most
-#define X3H_DB(I) do { if ((I) < NQ && more_b) x3_asm_dma16((const void*)(b_src[(I) < NQ ? (I) : 0] + (kt + 1) * XBK), b_wave + b_slot * B_BYTES + (I) * 1024u); } while (0)
 #define X3H_DA(I) do { if ((I) < NA && more_a) x3_asm_dma16((const void*)(a_src[(I) < NA ? (I) : 0] + (kt + 2) * XBK), a_wave + a_tgt * A_BYTES + (I) * 1024u); } while (0)
 #define X3H_STEP_MID_IL(KS, FS, NKS) do { \
         if constexpr (CW == 4) { \
@@ -715,8 +688,6 @@ __global__ void __launch_bounds__(64 * MW, 2) k_gemm_x3d(X3Args g)
             X3H_LGKM(0); X3H_BLOCKH(1, FS, 1, X3H_DA(2), X3H_DA(3)); \
         } \
         X3H_PACK((FS) ^ 1); } while (0)
-#define X3H_VM(N) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory")
-#define X3H_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
     // prologue: weights and A of tile 0 (and, with the deeper ring, A of tile 1)
     dma_b(0, 0);
     dma_a(0, 0);
@@ -779,6 +750,18 @@ __global__ void __launch_bounds__(64 * MW, 2) k_gemm_x3d(X3Args g)
         printf("x3d M %d N %d K %d MW %d CW %d AR %d blk %d wave %d nk %d: dma-issue %lld step0 %lld own-A-wait %lld step1 %lld sync %lld (cycles)\n", g.M, g.N, g.K,
                MW, CW, AR, (int)blockIdx.x, wave, nk, pt[0], pt[1], pt[2], pt[3], pt[4]);
 #endif
+#undef X3H_FB
+#undef X3H_PAIR_A
+#undef X3H_PAIR_B
+#undef X3H_PACK
+#undef X3H_BLOCKH
+#undef X3H_BLOCK
+#undef X3H_STEP_MID
+#undef X3H_STEP_END
+#undef X3H_DA
+#undef X3H_STEP_MID_IL
+#undef X3H_STEP_END_IL
+#undef X3D_STAMP
     } else if constexpr (FMT == 1) {
     // ---- hand-scheduled k loop of the f16 pair format, 128 x 64 tiles.  The interleaved schedule of the bf16 loop above (two A slots, own
     // rows two tiles ahead, every LDS-DMA instruction issued between MFMAs), with TWO planes per operand and THREE MFMAs per column
@@ -800,7 +783,6 @@ __global__ void __launch_bounds__(64 * MW, 2) k_gemm_x3d(X3Args g)
     float ha = 0.f, hb = 0.f;
 #define X3F_FB(KS, J, SET) do { x3h_lds128<(0 * BN + (J) * 32) * XROW>(fbq[SET][0], vb[KS]); \
                                 x3h_lds128<(1 * BN + (J) * 32) * XROW>(fbq[SET][1], vb[KS]); } while (0)
-#define X3F_RAW(KS, SET) do { x3h_lds128<0>(rawq[SET][0], va[KS][0]); x3h_lds128<0>(rawq[SET][1], va[KS][1]); } while (0)
 #define X3F_PAIR_A(SET, Q) do { const uint4 v_ = rawq[SET][(Q) >> 1]; \
         x3h_splitf_a(__uint_as_float(((Q) & 1) ? v_.z : v_.x), __uint_as_float(((Q) & 1) ? v_.w : v_.y), pl[SET][0][Q], ha, hb); } while (0)
 #define X3F_PAIR_B(SET, Q) do { const uint4 v_ = rawq[SET][(Q) >> 1]; \
@@ -812,15 +794,12 @@ __global__ void __launch_bounds__(64 * MW, 2) k_gemm_x3d(X3Args g)
         x3h_mfma_f16(acc_lo[J], fa[FS][1], b0_); X3F_PAIR_A((FS) ^ 1, PJ * (J)); \
         x3h_mfma_f16(acc[J], fa[FS][0], b0_); X3F_PAIR_B((FS) ^ 1, PJ * (J)); H1; \
         x3h_mfma_f16(acc_lo[J], fa[FS][0], b1_); if (PJ == 2) { X3F_PAIR_A((FS) ^ 1, PJ * (J) + 1); X3F_PAIR_B((FS) ^ 1, PJ * (J) + 1); } H2; } while (0)
-#define X3F_DB(I) do { if ((I) < NQ && more_b) x3_asm_dma16((const void*)(b_src[(I) < NQ ? (I) : 0] + (kt + 1) * XBK), b_wave + b_slot * B_BYTES + (I) * 1024u); } while (0)
 #define X3F_DA(I) do { if (more_a) x3_asm_dma16((const void*)(a_src[I] + (kt + 2) * XBK), a_wave + a_tgt * A_BYTES + (I) * 1024u); } while (0)
-#define X3F_VM(N) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory")
-#define X3F_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
     // prologue: weights and own rows of tile 0, own rows of tile 1
     dma_b(0, 0);
     dma_a(0, 0);
-    if (nk > 1) { dma_a(1, 1); X3F_VM(4); } else X3F_VM(0);
-    X3F_BARRIER();
+    if (nk > 1) { dma_a(1, 1); X3H_VM(4); } else X3H_VM(0);
+    X3H_BARRIER();
     {
         unsigned a00 = lds_base + fa_off[0][0], a01 = lds_base + fa_off[0][1], a10 = lds_base + fa_off[1][0], a11 = lds_base + fa_off[1][1];
         x3h_lds128<0>(rawq[0][0], a00); x3h_lds128<0>(rawq[0][1], a01);
@@ -836,18 +815,18 @@ __global__ void __launch_bounds__(64 * MW, 2) k_gemm_x3d(X3Args g)
         X3F_FB(0, 0, 0);
         // step 0 (fa[0]); behind it: the split of this tile's second A piece (raw[1] -> fa[1]) and the weight DMAs of tile kt + 1
         if constexpr (CW == 2) {
-            X3F_FB(0, 1, 1); X3H_LGKM(2); X3F_BLOCK(0, 0, 0, X3F_DB(0), X3F_DB(1));
+            X3F_FB(0, 1, 1); X3H_LGKM(2); X3F_BLOCK(0, 0, 0, X3H_DB(0), X3H_DB(1));
             X3F_FB(1, 0, 0); X3H_LGKM(2); X3F_BLOCK(1, 0, 1, (void)0, (void)0);
         } else {
-            X3F_FB(0, 1, 1); X3H_LGKM(2); X3F_BLOCK(0, 0, 0, X3F_DB(0), X3F_DB(1));
-            X3F_FB(0, 2, 0); X3H_LGKM(2); X3F_BLOCK(1, 0, 1, X3F_DB(2), X3F_DB(3));
+            X3F_FB(0, 1, 1); X3H_LGKM(2); X3F_BLOCK(0, 0, 0, X3H_DB(0), X3H_DB(1));
+            X3F_FB(0, 2, 0); X3H_LGKM(2); X3F_BLOCK(1, 0, 1, X3H_DB(2), X3H_DB(3));
             X3F_FB(0, 3, 1); X3H_LGKM(2); X3F_BLOCK(2, 0, 0, (void)0, (void)0);
             X3F_FB(1, 0, 0); X3H_LGKM(2); X3F_BLOCK(3 % CW, 0, 1, (void)0, (void)0);
         }
         X3F_PACK(1);
-        if (more_b) X3F_VM(NQ); else X3F_VM(0);                     // this wave's rows of tile kt + 1 have landed (issued a tile ago; only W(kt + 1) is younger)
-        X3F_RAW(0, 0);
-        X3F_RAW(1, 1);
+        if (more_b) X3H_VM(NQ); else X3H_VM(0);                     // this wave's rows of tile kt + 1 have landed (issued a tile ago; only W(kt + 1) is younger)
+        X3H_RAW(0, 0);
+        X3H_RAW(1, 1);
         // step 1 (fa[1]); behind it: the split of the next tile's first A piece (raw[0] -> fa[0]) and the own-row DMAs of tile kt + 2
         if constexpr (CW == 2) {
             X3F_FB(1, 1, 1); X3H_LGKM(2); X3F_BLOCK(0, 1, 0, X3F_DA(0), X3F_DA(1));
@@ -859,8 +838,8 @@ __global__ void __launch_bounds__(64 * MW, 2) k_gemm_x3d(X3Args g)
             X3H_LGKM(0); X3F_BLOCK(3 % CW, 1, 1, X3F_DA(3), (void)0);
         }
         X3F_PACK(0);
-        if (more_a) X3F_VM(4); else X3F_VM(0);                      // W(kt + 1) has landed (the rows of tile kt + 2 stay in flight)
-        X3F_BARRIER();
+        if (more_a) X3H_VM(4); else X3H_VM(0);                      // W(kt + 1) has landed (the rows of tile kt + 2 stay in flight)
+        X3H_BARRIER();
         {
             const unsigned nb = b_slot;
             b_slot ^= 1u;
@@ -874,6 +853,12 @@ __global__ void __launch_bounds__(64 * MW, 2) k_gemm_x3d(X3Args g)
         }
     }
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");          // MFMA results -> the epilogue's reads (the compiler does not see the MFMAs)
+#undef X3F_FB
+#undef X3F_PAIR_A
+#undef X3F_PAIR_B
+#undef X3F_PACK
+#undef X3F_BLOCK
+#undef X3F_DA
     } else {
     // ---- compiler-scheduled k loop (one / two planes per operand: cfg.compute_dtype 'bf16' / 'bf16x2')
     static_assert(AR == 2, "the compiler-scheduled loop uses the two-slot A ring");
@@ -889,11 +874,11 @@ __global__ void __launch_bounds__(64 * MW, 2) k_gemm_x3d(X3Args g)
     auto split_pair = [&](int set, int q) {                   // float pair q (0..3) of raw[set] -> pl[.][q]
         const float4 v = raw[set][q >> 1];
         if (FMT == 1) {
-            if (q & 1) x3_split2_f16(v.z, v.w, pl[0][q], pl[1][q]);
-            else x3_split2_f16(v.x, v.y, pl[0][q], pl[1][q]);
+            if (q & 1) rg_split2_f16(v.z, v.w, pl[0][q], pl[1][q]);
+            else rg_split2_f16(v.x, v.y, pl[0][q], pl[1][q]);
         } else {
-            if (q & 1) x3_split2(v.z, v.w, pl[0][q], pl[1][q], pl[2][q]);
-            else x3_split2(v.x, v.y, pl[0][q], pl[1][q], pl[2][q]);
+            if (q & 1) rg_split2(v.z, v.w, pl[0][q], pl[1][q], pl[2][q]);
+            else rg_split2(v.x, v.y, pl[0][q], pl[1][q], pl[2][q]);
         }
     };
     auto pack_fa = [&](int set) {
@@ -912,8 +897,8 @@ __global__ void __launch_bounds__(64 * MW, 2) k_gemm_x3d(X3Args g)
             if (jj + 1 < CW) read_fb(Bb, ks, jj + 1, cs ^ 1);
             else if (have_next) read_fb(Bn, ksn, 0, cs ^ 1);
 #define X3D_TERM(PA, PB) acc[jj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[fs][PA], fb[cs][PB], acc[jj], 0, 0, 0);
-#define X3D_TERM_F16(ACC, PA, PB) ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(x3_f16x8, fa[fs][PA]), \
-                                                                                __builtin_bit_cast(x3_f16x8, fb[cs][PB]), ACC, 0, 0, 0);
+#define X3D_TERM_F16(ACC, PA, PB) ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[fs][PA]), \
+                                                                                __builtin_bit_cast(f16x8, fb[cs][PB]), ACC, 0, 0, 0);
             if constexpr (FMT == 1) {
                 X3D_TERM_F16(acc_lo[jj], 1, 0) X3D_TERM_F16(acc[jj], 0, 0) X3D_TERM_F16(acc_lo[jj], 0, 1)      // (alternating accumulators)
             } else {
@@ -964,6 +949,11 @@ __global__ void __launch_bounds__(64 * MW, 2) k_gemm_x3d(X3Args g)
 #undef X3D_SYNC
 #undef X3D_OWN_A
     }
+#undef X3H_LGKM
+#undef X3H_VM
+#undef X3H_BARRIER
+#undef X3H_RAW
+#undef X3H_DB
 
     // ---- epilogue (C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5))
     // SOUT: the finished values also go to an LDS image of the tile (row-major, BN floats per row: a store instruction covers 2 x 32
@@ -973,10 +963,8 @@ __global__ void __launch_bounds__(64 * MW, 2) k_gemm_x3d(X3Args g)
     if constexpr (FMT == 1) {                              // f16 pair: fold the scaled low terms in
         float chk = 0.f;
 #pragma unroll
-        for (int j = 0; j < CW; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) { acc[j][r] += acc_lo[j][r] * (1.0f / X3_F16_SCALE); chk = fmaf(acc[j][r], 0.f, chk); }
-        x3_report_range(g.status, chk);
+        for (int j = 0; j < CW; j++) chk = rg_fold_low(acc[j], acc_lo[j], chk);
+        rg_report_range(g.status, chk);
     }
     float* T = (float*)&sm[0];                             // [BM][BN], free after the k loop's last barrier
 #pragma unroll
@@ -994,8 +982,7 @@ __global__ void __launch_bounds__(64 * MW, 2) k_gemm_x3d(X3Args g)
             continue;
         }
         const float bv = g.bias ? g.bias[col] : 0.f;
-        // row_div / residual come from CLAMPED rows, all sixteen loads in flight before the first use: a load under the per-lane
-        // `row < M` predicate compiles to load + s_waitcnt vmcnt(0) -- sixteen serial memory round trips per column block.
+        // row_div / residual from clamped rows, all sixteen loads in flight before the first use (x3_finish)
         float rd[16], rs[16];
         if (g.row_div) {
 #pragma unroll
@@ -1008,11 +995,7 @@ __global__ void __launch_bounds__(64 * MW, 2) k_gemm_x3d(X3Args g)
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             const int rl = rloc + (r & 3) + 8 * (r >> 2), row = m0 + rl;
-            float v = acc[j][r];
-            if (g.row_div) v = v / rd[r];
-            v += bv;
-            if (g.act == 1) v = fmaxf(v, 0.f);
-            if (g.residual) v += rs[r];
+            float v = x3_finish(g, acc[j][r], rd[r], bv, rs[r]);
             if (row < g.M) g.C[(size_t)row * g.ldc + col] = v;
             else v = 0.f;
             if (SOUT) T[rl * BN + j * 32 + l31] = v;
@@ -1027,9 +1010,9 @@ __global__ void __launch_bounds__(64 * MW, 2) k_gemm_x3d(X3Args g)
         double2* red = (double2*)&sm[BM * BN * 4];
         const int c = t % BN, part = t / BN;
         __syncthreads();
-        for (int sg = s_lo; sg <= s_hi; sg++) {            // workgroup-uniform; one cloud per tile almost always
-            const int r_lo = max((sg == s_lo ? s_lo_begin : g.stat_seg_off[sg]) - m0, 0);
-            const int r_hi = min(min(sg == s_lo ? s_lo_end : g.stat_seg_off[sg + 1], g.M) - m0, BM);
+        for (int sg = sr.lo; sg <= sr.hi; sg++) {            // workgroup-uniform; one cloud per tile almost always
+            const int r_lo = max((sg == sr.lo ? sr.lo_begin : g.stat_seg_off[sg]) - m0, 0);
+            const int r_hi = min(min(sg == sr.lo ? sr.lo_end : g.stat_seg_off[sg + 1], g.M) - m0, BM);
             double sm_ = 0.0, sq = 0.0;
             if (n0 + c < g.N)
                 for (int r = r_lo + part; r < r_hi; r += PARTS) { const double v = (double)T[r * BN + c]; sm_ += v; sq += v * v; }
@@ -1071,44 +1054,18 @@ __global__ void __launch_bounds__(256, 2) k_gemm_x3q(X3Args g)
     const int wm = wave >> 1, wn = wave & 1;
     const int l31 = lane & 31, hi = lane >> 5;
     int tile_m, tile_n;
-    {
-        const int nc = g.N / BN, b = blockIdx.x, x = b & 7, q = b >> 3;       // XCD-aware map, as in k_gemm_x3
-        tile_n = q % nc;
-        tile_m = (q / nc) * 8 + x;
-        if (tile_m * BM >= g.M) return;
-    }
+    if (!x3_tile_of_workgroup<BM>(g.M, g.N / BN, tile_m, tile_n)) return;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const int k_begin = blockIdx.z * g.k_chunk;
     const int k_end = min(g.K, k_begin + g.k_chunk);
     const int nk = (k_end - k_begin) / XBK;                    // whole k-tiles only (the launcher checks)
-    int s_lo = 0, s_hi = 0, s_lo_begin = 0, s_lo_end = 0;
-    if (SOUT) {
-        if (g.tile_info) {
-            const int4 ti = g.tile_info[tile_m];
-            s_lo = ti.x; s_hi = ti.y; s_lo_begin = ti.z; s_lo_end = ti.w;
-        } else {
-            const int row_last = min(m0 + BM, g.M) - 1;
-            s_lo = rg_find_segment_wave(g.stat_seg_off, g.n_stat_seg, m0);
-            s_hi = rg_find_segment_wave(g.stat_seg_off, g.n_stat_seg, row_last);
-            s_lo_begin = g.stat_seg_off[s_lo]; s_lo_end = g.stat_seg_off[s_lo + 1];
-        }
-    }
-    // A DMA: instruction q of this wave fills rows 16 wave + 8 q + (lane >> 3), LDS chunk lane & 7 <- source chunk (lane & 7) ^ ((row >> 1) & 7)
+    X3StatRange sr{0, 0, 0, 0};
+    if (SOUT) sr = x3_stat_range<BM>(g, tile_m);
     const float* a_src[NA];
-#pragma unroll
-    for (int q = 0; q < NA; q++) {
-        const int r = wave * (8 * NA) + q * 8 + (lane >> 3);
-        const int row = m0 + r, rc = row < g.M ? row : g.M - 1;    // rows past M compute garbage that the epilogue never stores
-        a_src[q] = g.A + (size_t)rc * g.lda + k_begin + (((lane & 7) ^ ((r >> 1) & 7)) * 4);
-    }
+    x3_raw_a_dma_src(g, wave, lane, m0, k_begin, a_src);
     const uint16_t* b_src[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; q++) {
-        const int sidx = (wave * NQ + q) * 64 + lane;
-        const int p = sidx / (BN * 4), r = sidx % (BN * 4), n = r >> 2, kc = (r & 3) ^ ((n >> 2) & 3);
-        b_src[q] = g.Wt + (size_t)p * g.plane + (size_t)(n0 + n) * g.Kp + kc * 8 + k_begin;
-    }
-    const unsigned lds_base = (unsigned)(unsigned long long)(x3_lds_ptr)(&sm[0]);
+    x3_weight_dma_src<BN>(g, wave, lane, n0, k_begin, b_src);
+    const unsigned lds_base = (unsigned)(unsigned long long)(rg_lds_ptr)(&sm[0]);
     auto dma = [&](int kt, unsigned slot) {
         const unsigned base = lds_base + slot * SLOT_BYTES;
 #pragma unroll
@@ -1116,17 +1073,10 @@ __global__ void __launch_bounds__(256, 2) k_gemm_x3q(X3Args g)
 #pragma unroll
         for (int q = 0; q < NQ; q++) x3_asm_dma16((const void*)(b_src[q] + kt * XBK), base + A_BYTES + (unsigned)(wave * NQ + q) * 1024u);
     };
-    // fragment addresses: A row 32 wm + l31, 16-byte chunks 4 ks + 2 hi (+ 1), swizzled; weights as in k_gemm_x3
-    unsigned fa_off[2][2], f_off[2];
-    {
-        const unsigned r = (unsigned)wm * 32u + (unsigned)l31, sw = (r >> 1) & 7u;
+    unsigned fa_off[2][2], f_off[2];                           // fragment addresses within a slot: A row 32 wm + l31; weights behind A, column block wn
+    x3_raw_a_frag_off((unsigned)wm * 32u + (unsigned)l31, hi, fa_off);
 #pragma unroll
-        for (int ks = 0; ks < 2; ks++) {
-#pragma unroll
-            for (int h = 0; h < 2; h++) fa_off[ks][h] = r * 128u + ((((unsigned)(4 * ks + 2 * hi + h)) ^ sw) * 16u);
-            f_off[ks] = (unsigned)A_BYTES + ((unsigned)wn * 32u + (unsigned)l31) * XROW + ((((unsigned)(2 * ks + hi)) ^ (((unsigned)l31 >> 2) & 3u)) * 16u);
-        }
-    }
+    for (int ks = 0; ks < 2; ks++) f_off[ks] = (unsigned)A_BYTES + (unsigned)wn * 32u * XROW + x3_frag_off(l31, hi, ks);
     floatx16 acc, acc_lo;
 #pragma unroll
     for (int r = 0; r < 16; r++) { acc[r] = 0.f; acc_lo[r] = 0.f; }
@@ -1144,11 +1094,11 @@ __global__ void __launch_bounds__(256, 2) k_gemm_x3q(X3Args g)
             const float4 r0 = *(const float4*)(S + fa_off[ks][0]), r1 = *(const float4*)(S + fa_off[ks][1]);
             unsigned pl[3][4];
             if constexpr (FMT == 1) {
-                x3_split2_f16(r0.x, r0.y, pl[0][0], pl[1][0]); x3_split2_f16(r0.z, r0.w, pl[0][1], pl[1][1]);
-                x3_split2_f16(r1.x, r1.y, pl[0][2], pl[1][2]); x3_split2_f16(r1.z, r1.w, pl[0][3], pl[1][3]);
+                rg_split2_f16(r0.x, r0.y, pl[0][0], pl[1][0]); rg_split2_f16(r0.z, r0.w, pl[0][1], pl[1][1]);
+                rg_split2_f16(r1.x, r1.y, pl[0][2], pl[1][2]); rg_split2_f16(r1.z, r1.w, pl[0][3], pl[1][3]);
             } else {
-                x3_split2(r0.x, r0.y, pl[0][0], pl[1][0], pl[2][0]); x3_split2(r0.z, r0.w, pl[0][1], pl[1][1], pl[2][1]);
-                x3_split2(r1.x, r1.y, pl[0][2], pl[1][2], pl[2][2]); x3_split2(r1.z, r1.w, pl[0][3], pl[1][3], pl[2][3]);
+                rg_split2(r0.x, r0.y, pl[0][0], pl[1][0], pl[2][0]); rg_split2(r0.z, r0.w, pl[0][1], pl[1][1], pl[2][1]);
+                rg_split2(r1.x, r1.y, pl[0][2], pl[1][2], pl[2][2]); rg_split2(r1.z, r1.w, pl[0][3], pl[1][3], pl[2][3]);
             }
             bf16x8 fa[NP], fb[NP];
 #pragma unroll
@@ -1157,9 +1107,9 @@ __global__ void __launch_bounds__(256, 2) k_gemm_x3q(X3Args g)
                 fb[p] = __builtin_bit_cast(bf16x8, *(const uint4*)(S + p * BN * XROW + f_off[ks]));
             }
             if constexpr (FMT == 1) {
-                acc_lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(x3_f16x8, fa[1]), __builtin_bit_cast(x3_f16x8, fb[0]), acc_lo, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(x3_f16x8, fa[0]), __builtin_bit_cast(x3_f16x8, fb[0]), acc, 0, 0, 0);
-                acc_lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(x3_f16x8, fa[0]), __builtin_bit_cast(x3_f16x8, fb[1]), acc_lo, 0, 0, 0);
+                acc_lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[1]), __builtin_bit_cast(f16x8, fb[0]), acc_lo, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[0]), __builtin_bit_cast(f16x8, fb[0]), acc, 0, 0, 0);
+                acc_lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[0]), __builtin_bit_cast(f16x8, fb[1]), acc_lo, 0, 0, 0);
             } else {
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[2], fb[0], acc, 0, 0, 0);       // six terms, smallest first (as k_gemm_x3)
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[1], acc, 0, 0, 0);
@@ -1172,13 +1122,8 @@ __global__ void __launch_bounds__(256, 2) k_gemm_x3q(X3Args g)
     }
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");       // the re-reads past the end have landed before the ring is reused or released
 
-    if constexpr (FMT == 1) {                              // f16 pair: fold the scaled low terms in
-        float chk = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; r++) { acc[r] += acc_lo[r] * (1.0f / X3_F16_SCALE); chk = fmaf(acc[r], 0.f, chk); }
-        x3_report_range(g.status, chk);
-    }
-    // ---- epilogue (C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)), as k_gemm_x3
+    if constexpr (FMT == 1) rg_report_range(g.status, rg_fold_low(acc, acc_lo));      // f16 pair: fold the scaled low terms in
+    // ---- epilogue (C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5))
     {
         const int col = n0 + wn * 32 + l31;
         const int rbase = m0 + wm * 32 + 4 * hi;
@@ -1203,21 +1148,17 @@ __global__ void __launch_bounds__(256, 2) k_gemm_x3q(X3Args g)
 #pragma unroll
             for (int r = 0; r < 16; r++) {
                 const int row = rbase + (r & 3) + 8 * (r >> 2);
-                float v = acc[r];
-                if (g.row_div) v = v / rd[r];
-                v += bv;
-                if (g.act == 1) v = fmaxf(v, 0.f);
-                if (g.residual) v += rs[r];
+                const float v = x3_finish(g, acc[r], rd[r], bv, rs[r]);
                 if (row < g.M) g.C[(size_t)row * g.ldc + col] = v;
                 acc[r] = v;
             }
         }
     }
-    if constexpr (SOUT) {       // per (tile, cloud) column sums of the finished values (float64, fixed order), as k_gemm_x3
+    if constexpr (SOUT) {       // per (tile, cloud) column sums of the finished values (float64, fixed order): k_gemm_x3's, one block per wave
         double2* red = (double2*)&sm[0];                   // [2 row blocks][BN]
-        for (int sg = s_lo; sg <= s_hi; sg++) {            // workgroup-uniform; one cloud per tile almost always
-            const int r_lo = sg == s_lo ? s_lo_begin : g.stat_seg_off[sg];
-            const int r_hi = min(sg == s_lo ? s_lo_end : g.stat_seg_off[sg + 1], g.M);
+        for (int sg = sr.lo; sg <= sr.hi; sg++) {            // workgroup-uniform; one cloud per tile almost always
+            const int r_lo = sg == sr.lo ? sr.lo_begin : g.stat_seg_off[sg];
+            const int r_hi = min(sg == sr.lo ? sr.lo_end : g.stat_seg_off[sg + 1], g.M);
             double sm_ = 0.0, sq = 0.0;
 #pragma unroll
             for (int r = 0; r < 16; r++) {
@@ -1248,11 +1189,8 @@ __global__ void __launch_bounds__(256) k_x3_splitk_reduce(X3Args g, int S)
     const int row = (int)(e / g.N), col = (int)(e % g.N);
     float v = 0.f;
     for (int s = 0; s < S; s++) v += g.partial[(size_t)s * g.M * g.N + e];   // fixed order: deterministic
-    if (g.row_div) v = v / g.row_div[row];
-    if (g.bias) v += g.bias[col];
-    if (g.act == 1) v = fmaxf(v, 0.f);
-    if (g.residual) v += g.residual[(size_t)row * g.ldr + col];
-    g.C[(size_t)row * g.ldc + col] = v;
+    g.C[(size_t)row * g.ldc + col] = x3_finish(g, v, g.row_div ? g.row_div[row] : 1.f, g.bias ? g.bias[col] : 0.f,
+                                               g.residual ? g.residual[(size_t)row * g.ldr + col] : 0.f);
 }
 
 // The same reduction WITH the InstanceNorm partial sums of the result (round 5): a split-K launch had no statistics epilogue, so a KPConv
@@ -1290,18 +1228,10 @@ __global__ void __launch_bounds__(256) k_x3_splitk_reduce_stats(X3Args g, int S,
                 a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
             }
             float v[4] = {a.x, a.y, a.z, a.w};
-            if (g.row_div) { const float d = g.row_div[r];
+            const float bj[4] = {bv.x, bv.y, bv.z, bv.w};
+            const float d = g.row_div ? g.row_div[r] : 1.f;
 #pragma unroll
-                for (int j = 0; j < 4; j++) v[j] = v[j] / d; }
-            v[0] += bv.x; v[1] += bv.y; v[2] += bv.z; v[3] += bv.w;
-            if (g.act == 1) {
-#pragma unroll
-                for (int j = 0; j < 4; j++) v[j] = fmaxf(v[j], 0.f);
-            }
-            if (g.residual) {
-#pragma unroll
-                for (int j = 0; j < 4; j++) v[j] += g.residual[(size_t)r * g.ldr + col + j];
-            }
+            for (int j = 0; j < 4; j++) v[j] = x3_finish(g, v[j], d, bj[j], g.residual ? g.residual[(size_t)r * g.ldr + col + j] : 0.f);
             if (vec_ok) *(float4*)(g.C + (size_t)r * g.ldc + col) = make_float4(v[0], v[1], v[2], v[3]);
             else {
 #pragma unroll
@@ -1328,7 +1258,8 @@ __global__ void __launch_bounds__(256) k_x3_splitk_reduce_stats(X3Args g, int S,
 static inline bool x3_rs_ok(int N) { const int c4 = N >> 2; return N % 4 == 0 && c4 >= 1 && c4 <= 256 && (c4 & (c4 - 1)) == 0; }
 
 // W (rows x cols, leading dimension ld) -> Wt[p][n][k]: n = row (transposed == 0: W is [N, K], an nn.Linear weight) or
-// n = col (transposed == 1: W is [K, N]).  Padding (k >= K, n >= N) is zero.
+// n = col (transposed == 1: W is [K, N]).  Padding (k >= K, n >= N) is zero.  FMT 0: three bf16 planes; 1: the f16 pair (plane 1 = scaled residual)
+template <int FMT>
 __global__ void __launch_bounds__(256) k_split_weights(const float* __restrict__ W, int ld, int N, int K, int transposed,
                                                        int Npad, int Kp, uint16_t* __restrict__ Wt)
 {
@@ -1337,25 +1268,22 @@ __global__ void __launch_bounds__(256) k_split_weights(const float* __restrict__
     const int n = (int)(e / Kp), k = (int)(e % Kp);
     float w = 0.f;
     if (n < N && k < K) w = transposed ? W[(size_t)k * ld + n] : W[(size_t)n * ld + k];
-    unsigned p0, p1, p2;
-    x3_split2(w, 0.f, p0, p1, p2);
+    constexpr int PLANES = FMT == 1 ? 2 : 3;
+    unsigned p[PLANES];
+    rg_split2<PLANES, FMT == 1>(w, 0.f, p);
     const size_t plane = (size_t)Npad * Kp;
-    Wt[e] = (uint16_t)(p0 & 0xffffu); Wt[plane + e] = (uint16_t)(p1 & 0xffffu); Wt[2 * plane + e] = (uint16_t)(p2 & 0xffffu);
+#pragma unroll
+    for (int i = 0; i < PLANES; i++) Wt[i * plane + e] = (uint16_t)(p[i] & 0xffffu);
 }
 
-// the same for the f16 pair format: Wt[2][Npad][Kp] f16 (plane 1 = scaled residual)
-__global__ void __launch_bounds__(256) k_split_weights_f16(const float* __restrict__ W, int ld, int N, int K, int transposed,
-                                                           int Npad, int Kp, uint16_t* __restrict__ Wt)
+template <int FMT>
+int x3_split_weights(const float* W, int ld, int N, int K, int transposed, void* planes, void* stream)
 {
-    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= (size_t)Npad * Kp) return;
-    const int n = (int)(e / Kp), k = (int)(e % Kp);
-    float w = 0.f;
-    if (n < N && k < K) w = transposed ? W[(size_t)k * ld + n] : W[(size_t)n * ld + k];
-    unsigned p0, p1;
-    x3_split2_f16(w, 0.f, p0, p1);
-    const size_t plane = (size_t)Npad * Kp;
-    Wt[e] = (uint16_t)(p0 & 0xffffu); Wt[plane + e] = (uint16_t)(p1 & 0xffffu);
+    if (!W || !planes || N < 1 || K < 1 || ld < (transposed ? N : K)) return RG_ERR_ARG;
+    const RgPlaneDims pd = rg_plane_dims(N, K);
+    k_split_weights<FMT><<<rg_cdiv((long long)pd.elems(), 256), 256, 0, (hipStream_t)stream>>>(W, ld, N, K, transposed, pd.Npad, pd.Kp, (uint16_t*)planes);
+    RG_RETURN_IF_LAUNCH_FAILED();
+    return RG_OK;
 }
 
 // tile t of `rows` rows -> (first cloud, last cloud, first cloud's begin, first cloud's end); one thread per tile
@@ -1412,6 +1340,37 @@ X3Plan x3_plan(int M, int N, int K)
     return p;
 }
 
+// The instantiation for a launch's runtime flags.  n_planes: 1 | 2 | 3 bf16 planes, 4 = the f16 pair; stats: InstanceNorm folded into A;
+// sout: statistics epilogue.  One or two planes come without either.  (Every k_gemm_x3* instantiation of the library is named here.)
+typedef void (*X3Kernel)(X3Args);
+
+template <int MW, int NW, int WM, int WN, int NP, int FMT>
+X3Kernel x3_tiled_variant(bool stats, bool sout)
+{
+    if (stats) return sout ? k_gemm_x3<MW, NW, WM, WN, true, true, NP, FMT> : k_gemm_x3<MW, NW, WM, WN, true, false, NP, FMT>;
+    return sout ? k_gemm_x3<MW, NW, WM, WN, false, true, NP, FMT> : k_gemm_x3<MW, NW, WM, WN, false, false, NP, FMT>;
+}
+template <int MW, int NW, int WM, int WN>
+X3Kernel x3_tiled_kernel(int n_planes, bool stats, bool sout)
+{
+    if (n_planes == 4) {      // (not on the 8-wave tile: two accumulator sets do not fit its 128-register budget)
+        if constexpr (NW == 2) return x3_tiled_variant<MW, NW, WM, WN, 2, 1>(stats, sout);
+        else return nullptr;
+    }
+    if (n_planes == 1) return k_gemm_x3<MW, NW, WM, WN, false, false, 1>;
+    if (n_planes == 2) return k_gemm_x3<MW, NW, WM, WN, false, false, 2>;
+    return x3_tiled_variant<MW, NW, WM, WN, 3, 0>(stats, sout);
+}
+// row-strip kernel, four waves: CW column blocks per wave, A ring mode AR (float32-grade bf16 only; the other formats run the two-slot ring)
+template <int CW, int AR>
+X3Kernel x3_strip_kernel(int n_planes, bool sout)
+{
+    if (n_planes == 4) return sout ? k_gemm_x3d<4, CW, 2, true, 2, 1> : k_gemm_x3d<4, CW, 2, false, 2, 1>;
+    if (n_planes == 1) return k_gemm_x3d<4, CW, 2, false, 1>;
+    if (n_planes == 2) return k_gemm_x3d<4, CW, 2, false, 2>;
+    return sout ? k_gemm_x3d<4, CW, AR, true> : k_gemm_x3d<4, CW, AR, false>;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1457,20 +1416,14 @@ int regtr_gemm_x3_preferred(int M, int N, int K)
 
 size_t regtr_gemm_split_weights_bytes(int N, int K)
 {
-    const size_t Npad = (size_t)rg_cdiv(N, 128) * 128, Kp = (size_t)rg_cdiv(K, XBK) * XBK;
-    return 3 * Npad * Kp * sizeof(uint16_t);
+    return 3 * rg_plane_dims(N, K).elems() * sizeof(uint16_t);
 }
 
 // W: float32 weights, [N, K] row-major (transposed = 0, an nn.Linear weight as stored) or [K, N] (transposed = 1, e.g. a
 // KPConv weight viewed as [15 Cin, Cout]).  planes: regtr_gemm_split_weights_bytes(N, K) bytes.
 int regtr_gemm_split_weights(const float* W, int ld, int N, int K, int transposed, void* planes, void* stream)
 {
-    if (!W || !planes || N < 1 || K < 1 || ld < (transposed ? N : K)) return RG_ERR_ARG;
-    const int Npad = rg_cdiv(N, 128) * 128, Kp = rg_cdiv(K, XBK) * XBK;
-    k_split_weights<<<rg_cdiv((long long)Npad * Kp, 256), 256, 0, (hipStream_t)stream>>>(W, ld, N, K, transposed, Npad, Kp,
-                                                                                         (uint16_t*)planes);
-    RG_RETURN_IF_LAUNCH_FAILED();
-    return RG_OK;
+    return x3_split_weights<0>(W, ld, N, K, transposed, planes, stream);
 }
 
 // Tile plan of the f16 pair format (regtr_gemm_x3 with n_planes = 4): the bf16 plan (strip or tiled kernel alike); without the
@@ -1492,18 +1445,12 @@ int regtr_gemm_x3_f16_supported(int M, int N, int K, int with_stats)
 
 size_t regtr_gemm_split_weights_f16_bytes(int N, int K)
 {
-    const size_t Npad = (size_t)rg_cdiv(N, 128) * 128, Kp = (size_t)rg_cdiv(K, XBK) * XBK;
-    return 2 * Npad * Kp * sizeof(uint16_t);
+    return 2 * rg_plane_dims(N, K).elems() * sizeof(uint16_t);
 }
 
 int regtr_gemm_split_weights_f16(const float* W, int ld, int N, int K, int transposed, void* planes, void* stream)
 {
-    if (!W || !planes || N < 1 || K < 1 || ld < (transposed ? N : K)) return RG_ERR_ARG;
-    const int Npad = rg_cdiv(N, 128) * 128, Kp = rg_cdiv(K, XBK) * XBK;
-    k_split_weights_f16<<<rg_cdiv((long long)Npad * Kp, 256), 256, 0, (hipStream_t)stream>>>(W, ld, N, K, transposed, Npad, Kp,
-                                                                                             (uint16_t*)planes);
-    RG_RETURN_IF_LAUNCH_FAILED();
-    return RG_OK;
+    return x3_split_weights<1>(W, ld, N, K, transposed, planes, stream);
 }
 
 size_t regtr_gemm_x3_ws_bytes(int M, int N, int K)
@@ -1559,32 +1506,13 @@ int regtr_gemm_x3(const float* A, int lda, const void* planes, float* C, int ldc
     // split-K: the product kernel writes raw partial products; the statistics (if asked for) come from the reduction kernel
     double* const stat_all = stat_partial;
     if (p.splits > 1) stat_partial = nullptr;
-    const int Npad = rg_cdiv(N, 128) * 128, Kp = rg_cdiv(K, XBK) * XBK;
+    const RgPlaneDims pd = rg_plane_dims(N, K);
     X3Args g{A, (const uint16_t*)planes, C, bias, row_div, residual, (const float2*)a_stats, a_seg_off,
-             p.splits > 1 ? (float*)ws : nullptr, (double2*)stat_partial, stat_seg_off, (const int4*)tile_info, (size_t)Npad * Kp,
-             M, N, K, Kp, lda, ldc, ldr, act, n_seg, p.k_chunk, n_stat_seg, a_slope, status};
+             p.splits > 1 ? (float*)ws : nullptr, (double2*)stat_partial, stat_seg_off, (const int4*)tile_info, pd.elems(),
+             M, N, K, pd.Kp, lda, ldc, ldr, act, n_seg, p.k_chunk, n_stat_seg, a_slope, status};
     hipStream_t st = (hipStream_t)stream;
     const int bm = p.tile == 2 ? 64 : 128, bn = p.tile == 0 ? 128 : 64;
     dim3 grid(rg_cdiv(rg_cdiv(M, bm), 8) * 8 * rg_cdiv(N, bn), 1, p.splits);      // see the XCD-aware tile map in the kernel
-#define X3_LAUNCH(MW_, NW_, WM_, WN_) do { \
-        if (n_planes == 4) { if constexpr (NW_ == 2) { \
-            if (a_stats) { if (stat_partial) k_gemm_x3<MW_, NW_, WM_, WN_, true, true, 2, 1><<<grid, 64 * MW_ * NW_, 0, st>>>(g); \
-                           else k_gemm_x3<MW_, NW_, WM_, WN_, true, false, 2, 1><<<grid, 64 * MW_ * NW_, 0, st>>>(g); } \
-            else { if (stat_partial) k_gemm_x3<MW_, NW_, WM_, WN_, false, true, 2, 1><<<grid, 64 * MW_ * NW_, 0, st>>>(g); \
-                   else k_gemm_x3<MW_, NW_, WM_, WN_, false, false, 2, 1><<<grid, 64 * MW_ * NW_, 0, st>>>(g); } } } \
-        else if (n_planes == 1) k_gemm_x3<MW_, NW_, WM_, WN_, false, false, 1><<<grid, 64 * MW_ * NW_, 0, st>>>(g); \
-        else if (n_planes == 2) k_gemm_x3<MW_, NW_, WM_, WN_, false, false, 2><<<grid, 64 * MW_ * NW_, 0, st>>>(g); \
-        else if (a_stats) { if (stat_partial) k_gemm_x3<MW_, NW_, WM_, WN_, true, true><<<grid, 64 * MW_ * NW_, 0, st>>>(g); \
-                       else k_gemm_x3<MW_, NW_, WM_, WN_, true, false><<<grid, 64 * MW_ * NW_, 0, st>>>(g); } \
-        else { if (stat_partial) k_gemm_x3<MW_, NW_, WM_, WN_, false, true><<<grid, 64 * MW_ * NW_, 0, st>>>(g); \
-               else k_gemm_x3<MW_, NW_, WM_, WN_, false, false><<<grid, 64 * MW_ * NW_, 0, st>>>(g); } } while (0)
-#define X3D_LAUNCH(MW_, CW_, AR_) do { \
-        if (n_planes == 4) { if (stat_partial) k_gemm_x3d<4, CW_, 2, true, 2, 1><<<grid, 256, 0, st>>>(g); \
-                             else k_gemm_x3d<4, CW_, 2, false, 2, 1><<<grid, 256, 0, st>>>(g); } \
-        else if (n_planes == 1) k_gemm_x3d<4, CW_, 2, false, 1><<<grid, 256, 0, st>>>(g); \
-        else if (n_planes == 2) k_gemm_x3d<4, CW_, 2, false, 2><<<grid, 256, 0, st>>>(g); \
-        else if (stat_partial) k_gemm_x3d<MW_, CW_, AR_, true><<<grid, 64 * MW_, 0, st>>>(g); \
-        else k_gemm_x3d<MW_, CW_, AR_, false><<<grid, 64 * MW_, 0, st>>>(g); } while (0)
     const bool strip = p.strip && !a_stats && K % XBK == 0 && p.k_chunk % XBK == 0;
     static const int a_ring = X3_DEV_ENV("REGTR_X3_ARING", 3);   // development: A/B runs
     static const int deep_pipe = X3_DEV_ENV("REGTR_X3_DEEP", 1);   // development: A/B runs
@@ -1597,21 +1525,24 @@ int regtr_gemm_x3(const float* A, int lda, const void* planes, float* C, int ldc
     // on the strided contractions (153 -> 165, 145 -> 151 us) and is not instantiated.  Hiding the ~1250-cycle DMA-issue phase bought
     // 1 %, not the 30 % its share of a tile suggested: with two workgroups per CU (hipOccupancyMaxActiveBlocksPerMultiprocessor) that phase already
     // overlapped the other workgroup's MFMAs.
-    if (strip && il && p.tile == 0) X3D_LAUNCH(4, 4, 4);
-    else if (strip && p.tile == 0) X3D_LAUNCH(4, 4, 2);              // 128 x 128: 4 waves of 32 rows x 128 columns, both operands by LDS-DMA
-    else if (strip && a_ring == 3) X3D_LAUNCH(4, 2, 3);              // 128 x 64, A rows two tiles ahead
-    else if (strip) X3D_LAUNCH(4, 2, 2);                             // 128 x 64
+    const bool stats = a_stats != nullptr, sout = stat_partial != nullptr;
+    X3Kernel kern = nullptr;
+    int threads = 256;
+    if (strip && il && p.tile == 0) kern = x3_strip_kernel<4, 4>(n_planes, sout);
+    else if (strip && p.tile == 0) kern = x3_strip_kernel<4, 2>(n_planes, sout);      // 128 x 128: 4 waves of 32 rows x 128 columns, both operands by LDS-DMA
+    else if (strip && a_ring == 3) kern = x3_strip_kernel<2, 3>(n_planes, sout);      // 128 x 64, A rows two tiles ahead
+    else if (strip) kern = x3_strip_kernel<2, 2>(n_planes, sout);                     // 128 x 64
     // small problems on 64 x 64 tiles (at most two workgroups per CU, no folded operand): the three-deep operand pipeline (k_gemm_x3q)
     else if (deep_pipe && p.tile == 2 && !a_stats && (n_planes == 3 || n_planes == 4) && K % XBK == 0 && p.k_chunk % XBK == 0 &&
              (long long)rg_cdiv(M, 64) * (N / 64) * p.splits <= 512) {
-        if (n_planes == 4) { if (stat_partial) k_gemm_x3q<true, 2, 1><<<grid, 256, 0, st>>>(g); else k_gemm_x3q<false, 2, 1><<<grid, 256, 0, st>>>(g); }
-        else { if (stat_partial) k_gemm_x3q<true, 3, 0><<<grid, 256, 0, st>>>(g); else k_gemm_x3q<false, 3, 0><<<grid, 256, 0, st>>>(g); }
+        if (n_planes == 4) kern = sout ? k_gemm_x3q<true, 2, 1> : k_gemm_x3q<false, 2, 1>;
+        else kern = sout ? k_gemm_x3q<true, 3, 0> : k_gemm_x3q<false, 3, 0>;
     }
-    else if (p.tile == 0) X3_LAUNCH(2, 4, 2, 1);     // 128 x 128, 8 waves of 64 x 32
-    else if (p.tile == 1) X3_LAUNCH(2, 2, 2, 1);     // 128 x 64, 4 waves of 64 x 32
-    else X3_LAUNCH(2, 2, 1, 1);                      // 64 x 64, 4 waves of 32 x 32
-#undef X3_LAUNCH
-#undef X3D_LAUNCH
+    else if (p.tile == 0) { kern = x3_tiled_kernel<2, 4, 2, 1>(n_planes, stats, sout); threads = 512; }     // 128 x 128, 8 waves of 64 x 32
+    else if (p.tile == 1) kern = x3_tiled_kernel<2, 2, 2, 1>(n_planes, stats, sout);                        // 128 x 64, 4 waves of 64 x 32
+    else kern = x3_tiled_kernel<2, 2, 1, 1>(n_planes, stats, sout);                                         // 64 x 64, 4 waves of 32 x 32
+    if (!kern) return RG_ERR_ARG;
+    kern<<<grid, threads, 0, st>>>(g);
     if (p.splits > 1 && stat_all) {
         X3Args gr = g;
         gr.stat_partial = (double2*)stat_all;

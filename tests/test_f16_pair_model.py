@@ -1,4 +1,5 @@
-"""CPU: a numpy model of the f16 pair operand format (regtr_amd/csrc/gemm_x3.hip FMT = 1, csrc/attention.hip precision 3) --
+"""CPU: a numpy model of the f16 pair operand format (defined in regtr_amd/csrc/mfma_operands.h: rg_split2_f16, RG_F16_SCALE,
+rg_fold_low; used by csrc/gemm_x3.hip FMT = 1 and csrc/attention.hip precision 3) --
 x = h0 + h1 / 2048 with h0 = f16(x), h1 = f16((x - h0) * 2048); a w = a0 w0 + (a0 w1 + a1 w0) / 2048 -- against float64, next to the
 bf16 splits it replaces.  Pins the two design decisions: (1) three f16 terms are float32-grade (the three-term bf16 split is not);
 (2) the 2048 scale is needed -- without it the residual plane of anything below 0.12 is an f16 subnormal, and hardware that flushes
