@@ -41,6 +41,7 @@
  *   regtr_infonce_rows / _bwd InfoNCELossFull forward + backward  models/losses/feature_loss.py:246-314
  *   regtr_gemm_tn             dW of InfoNCELossFull (G^T dP')     models/losses/feature_loss.py:295-297
  *   regtr_corr_l1_bwd         CorrCriterion('mae') backward       models/losses/corr_loss.py:24-37
+ *   regtr_mha_bwd             nn.MultiheadAttention core, backward   transformers.py:197-226
  */
 #ifndef REGTR_HIP_H
 #define REGTR_HIP_H
@@ -439,6 +440,25 @@ int regtr_gemm_tn(const float* a, int lda, const float* b, int ldb, int M, int N
  * (pose_stride 12 or 16); grad and den (the clamped weight sum) are ONE float each on the device.  Refused like regtr_se3_transform. */
 int regtr_corr_l1_bwd(const float* kp, const float* warped, const float* w, const int* seg_off, int n_clouds, int n, const float* pose,
                       int pose_stride, const float* grad, const float* den, float* d_warped, void* stream);
+
+/* Backward of regtr_mha_fwd's arithmetic on the same packed layout (head_dim = 32; cloud c's rows attend the rows of cloud kv_of[c]; any
+ * kv_of with entries in [0, n_clouds) is legal, several query clouds may share a key cloud).  With s_ij = scale q_i . k_j, P = softmax_j(s),
+ * dP_ij = d_out_i . v_j and delta_i = sum_j P_ij dP_ij, per head:
+ *   dv_j = sum_i P_ij d_out_i,   dS_ij = P_ij (dP_ij - delta_i),   dq_i = scale sum_j dS_ij k_j,   dk_j = scale sum_i dS_ij q_i.
+ * A function of (q, k, v, d_out) and the layout only: S and the row statistics are recomputed and the forward's output is not read, so
+ * the result is the same whichever forward precision produced it.  Two launches: a query-tile-owner pass writes dq and the per-(head,
+ * row) logsumexp and delta (delta from its own online accumulation) into ws; a key-tile-owner pass writes dk and dv, walking the query
+ * clouds in ascending order.  Every row of every cloud is written (a cloud nobody attends gets zero dk / dv rows, a cloud attending an
+ * empty cloud zero dq rows); rows outside every cloud are not.  Exact-f32 MFMA, float32 softmax statistics, one owner per output row,
+ * no atomics, bit-reproducible.  n_total = rows of the packed arrays (>= seg_off[n_clouds]); max_len >= every cloud's length (0:
+ * nothing to do, REGTR_OK).  Refused (REGTR_ERR_ARG, nothing launched): a NULL pointer with work to do, n_clouds < 1, a negative
+ * count, n_heads < 1, head_dim != 32, an ld that is not a multiple of 4 or is below n_heads * 32, a base pointer not 16-byte aligned.
+ * ws: regtr_mha_bwd_ws_bytes(n_total, n_heads) bytes (REGTR_ERR_WORKSPACE when smaller; 0 for a negative count). */
+size_t regtr_mha_bwd_ws_bytes(int n_total, int n_heads);
+int regtr_mha_bwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* d_out, int ld_do,
+                  float* dq, int ld_dq, float* dk, int ld_dk, float* dv, int ld_dv, const int* seg_off, const int* kv_of,
+                  int n_clouds, int n_total, int max_len, int n_heads, int head_dim, float scale, void* ws, size_t ws_bytes,
+                  void* stream);
 
 #ifdef __cplusplus
 }

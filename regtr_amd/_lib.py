@@ -113,6 +113,8 @@ SIGNATURES = {
     'regtr_gemm_tn_ws_bytes': (_Z, [_I, _I, _I]),
     'regtr_gemm_tn': (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _Z, _P]),
     'regtr_corr_l1_bwd': (_I, [_P, _P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _P]),
+    'regtr_mha_bwd_ws_bytes': (_Z, [_I, _I]),
+    'regtr_mha_bwd': (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _P, _Z, _P]),
 }
 
 COMPOSITE = ('regtr_encoder_fwd', 'regtr_cross_encoder_fwd')      # bound through a GIL-releasing handle (see _load)

@@ -576,6 +576,31 @@ def mha(q, k, v, seg_off, kv_of, max_len, n_heads, precision=0):
     return out
 
 
+def mha_bwd(q, k, v, d_out, seg_off, kv_of, max_len, n_heads, out=None):
+    """Backward of the attention core (regtr_mha_bwd): q, k, v, d_out (N, E) row-strided column views as ops.mha takes them -> (dq, dk,
+    dv), the three (N, E) column blocks of a packed (N, 3E) buffer -- the layout the in-projection's backward wants.  out: that buffer
+    (float32, contiguous), or None for a zero-filled new one; rows outside every cloud are not written.  A function of (q, k, v, d_out)
+    only: the forward's output and precision play no part.  Nothing here synchronises."""
+    L = _lib.lib()
+    N, E = q.shape
+    hd = E // n_heads
+    if out is None:
+        out = torch.zeros((N, 3 * E), dtype=torch.float32, device=q.device)
+    elif tuple(out.shape) != (N, 3 * E):
+        raise RuntimeError(f'mha_bwd: out must be ({N}, {3 * E}), got {tuple(out.shape)}')
+    for t in (q, k, v, d_out):
+        if tuple(t.shape) != (N, E) or (E > 1 and t.stride(1) != 1):
+            raise RuntimeError(f'mha_bwd: q, k, v and d_out must be ({N}, {E}) views with unit column stride')
+    base = ptr(out)
+    nb = L.regtr_mha_bwd_ws_bytes(N, n_heads)
+    ws = _ws(max(nb, 1), q.device)
+    ld = lambda t: t.stride(0) if N > 1 else E
+    check(L.regtr_mha_bwd(raw(q), ld(q), raw(k), ld(k), raw(v), ld(v), raw(d_out), ld(d_out),
+                          base, 3 * E, base + 4 * E if base else None, 3 * E, base + 8 * E if base else None, 3 * E,
+                          iptr(seg_off), iptr(kv_of), seg_off.numel() - 1, N, int(max_len), n_heads, hd, 1.0 / math.sqrt(hd),
+                          bptr(ws), nb, stream()), 'regtr_mha_bwd')
+    return out[:, :E], out[:, E:2 * E], out[:, 2 * E:]
+
 
 def attn_xyz(q, k, xyz, seg_off, kv_of, max_len):
     """CorrespondenceDecoder.simple_attention: q, k (L, N, D) contiguous, xyz (N, 3) -> (L, N, 3)."""
