@@ -42,6 +42,8 @@
  *   regtr_gemm_tn             dW of InfoNCELossFull (G^T dP')     models/losses/feature_loss.py:295-297
  *   regtr_corr_l1_bwd         CorrCriterion('mae') backward       models/losses/corr_loss.py:24-37
  *   regtr_mha_bwd             nn.MultiheadAttention core, backward   transformers.py:197-226
+ *   regtr_layernorm_bwd       nn.LayerNorm backward (+ the residual branch's gradient)   transformers.py:194-238
+ *   regtr_bias_relu_bwd       nn.Linear bias gradient, F.relu backward   transformers.py:194-238
  */
 #ifndef REGTR_HIP_H
 #define REGTR_HIP_H
@@ -459,6 +461,35 @@ int regtr_mha_bwd(const float* q, int ldq, const float* k, int ldk, const float*
                   float* dq, int ld_dq, float* dk, int ld_dk, float* dv, int ld_dv, const int* seg_off, const int* kv_of,
                   int n_clouds, int n_total, int max_len, int n_heads, int head_dim, float scale, void* ws, size_t ws_bytes,
                   void* stream);
+
+/* Backward of regtr_layernorm.  x [n, D] the forward's input, dy [n, D] the gradient of its output y (a caller that used y and y_plain
+ * passes the sum of their gradients; the gradient of `add` is dy itself), dres [n, D] optional: a gradient that reached x by another
+ * branch (the layer's residual), added into dx.  Mean and rstd are recomputed from x in the forward's operation order -- nothing is
+ * saved by the forward, and xh = (x - mean) rstd is the value it used.  With g = dy gamma:
+ *   dx = rstd (g - mean_c(g) - xh mean_c(g xh)) [+ dres],   dgamma_c = sum_rows dy xh,   dbeta_c = sum_rows dy.
+ * Two launches: one wave per row writes dx and adds its rows' dy xh and dy into per-workgroup partials over fixed row chunks (the chunk
+ * height depends on n only); a second launch adds the chunks of a column in a fixed order in float64.  One owner per output element, no
+ * atomics, bit-reproducible.  dx may be dres (not x or dy).  n = 0: nothing to do, REGTR_OK, nothing written.  Refused (REGTR_ERR_ARG,
+ * nothing launched): n < 0, D < 4, D % 4 != 0, D > 1024 (a lane keeps its column sums in registers), a NULL pointer other than dres
+ * with work to do, a pointer that is not 16-byte aligned.  ws: regtr_layernorm_bwd_ws_bytes(n, D) bytes (REGTR_ERR_WORKSPACE when
+ * smaller; 0 when there is nothing to do or the shape is refused). */
+size_t regtr_layernorm_bwd_ws_bytes(int n, int D);
+int regtr_layernorm_bwd(const float* x, int n, int D, const float* gamma, float eps, const float* dy, const float* dres, float* dx,
+                        float* dgamma, float* dbeta, void* ws, size_t ws_bytes, void* stream);
+
+/* Column sums of a gradient g [n, N] (row stride ldg), optionally through a ReLU mask:
+ *   h == NULL:  db_c = sum_rows g                                    (the bias gradient of a Linear whose output gradient is g)
+ *   h [n, N]:   dh = g where h > 0, else +0;  db_c = sum_rows dh     (h: what the forward stored AFTER its ReLU; h == 0 takes gradient 0,
+ *                                                                     as torch's ReLU backward does).  dh is optional and may be g.
+ * Two launches like regtr_layernorm_bwd's: per-workgroup partial sums over fixed row chunks (a function of n only), each thread adding
+ * its rows in row order, then the chunks of a column in a fixed order in float64.  One owner per output element, no atomics,
+ * bit-reproducible.  n = 0: nothing to do, REGTR_OK, nothing written.  Refused (REGTR_ERR_ARG, nothing launched): n < 0, N < 4,
+ * N % 4 != 0, a row stride below N or not a multiple of 4 (ldh / ld_dh are read only when h / dh is given), dh without h, g, db or ws
+ * NULL with work to do, a base pointer that is not 16-byte aligned.  ws: regtr_bias_relu_bwd_ws_bytes(n, N) bytes
+ * (REGTR_ERR_WORKSPACE when smaller). */
+size_t regtr_bias_relu_bwd_ws_bytes(int n, int N);
+int regtr_bias_relu_bwd(const float* g, int ldg, const float* h, int ldh, float* dh, int ld_dh, float* db, int n, int N, void* ws,
+                        size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -115,6 +115,10 @@ SIGNATURES = {
     'regtr_corr_l1_bwd': (_I, [_P, _P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _P]),
     'regtr_mha_bwd_ws_bytes': (_Z, [_I, _I]),
     'regtr_mha_bwd': (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _P, _Z, _P]),
+    'regtr_layernorm_bwd_ws_bytes': (_Z, [_I, _I]),
+    'regtr_layernorm_bwd': (_I, [_P, _I, _I, _P, _F, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    'regtr_bias_relu_bwd_ws_bytes': (_Z, [_I, _I]),
+    'regtr_bias_relu_bwd': (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _P, _Z, _P]),
 }
 
 COMPOSITE = ('regtr_encoder_fwd', 'regtr_cross_encoder_fwd')      # bound through a GIL-releasing handle (see _load)

@@ -9,7 +9,8 @@ nn.MultiheadAttention's parameters.
 Tokens are PACKED: rows [seg_off[c], seg_off[c + 1]) are cloud c, and cloud c attends cloud kv_of[c] (self: kv_of[c] = c; cross: the
 partner cloud of the pair; any map is legal).  The forward is ops.mha unchanged; the backward recomputes the probabilities from q, k, v
 (flash style), so only those three are saved and the gradients do not depend on the forward's precision.  Nothing here synchronises.
-Refused: CPU tensors, double backward.  Not wired into TransformerCrossEncoderLayer (the model's forward stays inference only).
+Refused: CPU tensors, double backward.  TransformerCrossEncoderLayer.forward_grad (regtr_amd/transformer_grad.py) is built on it; the
+model's forward stays inference only.
 """
 import torch
 import torch.nn as nn

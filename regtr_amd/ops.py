@@ -602,6 +602,47 @@ def mha_bwd(q, k, v, d_out, seg_off, kv_of, max_len, n_heads, out=None):
     return out[:, :E], out[:, E:2 * E], out[:, 2 * E:]
 
 
+def layernorm_bwd(x, gamma, dy, dres=None, eps=1e-5, out=None):
+    """Backward of ops.layernorm (regtr_layernorm_bwd): x, dy (n, D) contiguous, gamma (D,), dres (n, D) an optional gradient that
+    reached x through another branch (added into dx) -> (dx (n, D), dgamma (D,), dbeta (D,)).  Mean and rstd are recomputed from x.
+    out: the dx buffer (may be dres itself).  Nothing here synchronises."""
+    L = _lib.lib()
+    n, D = x.shape
+    for name, t in (('dy', dy), ('dres', dres), ('out', out)):
+        if t is not None and tuple(t.shape) != (n, D):
+            raise RuntimeError(f'layernorm_bwd: {name} must be ({n}, {D}), got {tuple(t.shape)}')
+    dx = torch.empty_like(x) if out is None else out
+    dgb = torch.zeros((2, D), dtype=torch.float32, device=x.device)       # n = 0: nothing is launched and the sums are 0
+    nb = L.regtr_layernorm_bwd_ws_bytes(n, D)
+    ws = _ws(max(nb, 1), x.device)
+    base = ptr(dgb)
+    check(L.regtr_layernorm_bwd(ptr(x), n, D, ptr(gamma), eps, ptr(dy), ptr(dres), ptr(dx), base, base + 4 * D, bptr(ws), nb, stream()),
+          'regtr_layernorm_bwd')
+    return dx, dgb[0], dgb[1]
+
+
+def bias_relu_bwd(g, h=None, inplace=False):
+    """Column sums of a gradient (regtr_bias_relu_bwd): g (n, N) float32, row-strided with unit column stride.  Without h -> db (N,) =
+    sum over rows of g: a Linear's bias gradient.  With h (n, N), the activation stored after the forward's ReLU -> (dh, db): dh = g
+    where h > 0 else 0, db its column sums; inplace=True writes dh over g.  Nothing here synchronises."""
+    L = _lib.lib()
+    n, N = g.shape
+    if N > 1 and g.stride(1) != 1:
+        raise RuntimeError('bias_relu_bwd: g must have unit column stride')
+    dh = None
+    if h is not None:
+        if tuple(h.shape) != (n, N) or (N > 1 and h.stride(1) != 1):
+            raise RuntimeError(f'bias_relu_bwd: h must be ({n}, {N}) with unit column stride, got {tuple(h.shape)}')
+        dh = g if inplace else torch.empty((n, N), dtype=torch.float32, device=g.device)
+    db = torch.zeros((N,), dtype=torch.float32, device=g.device)          # n = 0: nothing is launched and the sums are 0
+    nb = L.regtr_bias_relu_bwd_ws_bytes(n, N)
+    ws = _ws(max(nb, 1), g.device)
+    ld = lambda t: t.stride(0) if n > 1 else N
+    check(L.regtr_bias_relu_bwd(raw(g), ld(g), raw(h), ld(h) if h is not None else 0, raw(dh), ld(dh) if dh is not None else 0, ptr(db),
+                                n, N, bptr(ws), nb, stream()), 'regtr_bias_relu_bwd')
+    return (dh, db) if h is not None else db
+
+
 def attn_xyz(q, k, xyz, seg_off, kv_of, max_len):
     """CorrespondenceDecoder.simple_attention: q, k (L, N, D) contiguous, xyz (N, 3) -> (L, N, 3)."""
     Lyr, N, D = q.shape

@@ -25,7 +25,7 @@ class TransformerCrossEncoderLayer(nn.Module):
         if activation != 'relu':
             raise NotImplementedError('only the ReLU feed-forward of the shipped configs is implemented')
         if dropout != 0.0:
-            raise NotImplementedError('inference path: dropout must be 0 (as in both shipped configs)')
+            raise NotImplementedError('dropout must be 0 (as in both shipped configs): neither forward nor forward_grad implements it')
         # parameter containers with the reference's names; their torch forward is never called
         self.self_attn = nn.MultiheadAttention(d_model, nhead, dropout=dropout)
         self.multihead_attn = nn.MultiheadAttention(d_model, nhead, dropout=dropout)
@@ -106,6 +106,12 @@ class TransformerCrossEncoderLayer(nn.Module):
         h = self._gemm(x2, self._wt('l1', self.linear1.weight), bias=self.linear1.bias.detach(), relu=True)
         return self._gemm(h, self._wt('l2', self.linear2.weight), bias=self.linear2.bias.detach(), residual=x)  # :233-238
 
+    def forward_grad(self, x, pe, seg_off, kv_self, kv_cross, max_len):
+        """forward, differentiable in x, pe and every parameter (HIP backward, regtr_amd/transformer_grad.py): the same launches in the
+        same order, a bit-identical (N_total, D) result.  Pre-norm layers, pe None or carried by the values too."""
+        from . import transformer_grad
+        return transformer_grad.layer_forward_grad(self, x, pe, seg_off, kv_self, kv_cross, max_len)
+
 
 class TransformerCrossEncoder(nn.Module):
     def __init__(self, cross_encoder_layer, num_layers, norm=None, return_intermediate=False):
@@ -127,6 +133,12 @@ class TransformerCrossEncoder(nn.Module):
         if not self.return_intermediate:
             self._final(x, outs[0])
         return outs
+
+    def forward_grad(self, x, pe, seg_off, kv_self, kv_cross, max_len):
+        """forward's layer-by-layer path, differentiable in x, pe and every parameter (regtr_amd/transformer_grad.py): bit-identical
+        (L | 1, N_total, D), the final norm and return_intermediate included."""
+        from . import transformer_grad
+        return transformer_grad.encoder_forward_grad(self, x, pe, seg_off, kv_self, kv_cross, max_len)
 
     # ---- the whole stack through ONE C call (regtr_cross_encoder_fwd): the same 12 launches per layer, sequenced in C.  At one
     # pair per forward the host is the bound and these are 72 of its ~280 launches (csrc/cross_encoder.hip).
