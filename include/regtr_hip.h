@@ -44,6 +44,10 @@
  *   regtr_mha_bwd             nn.MultiheadAttention core, backward   transformers.py:197-226
  *   regtr_layernorm_bwd       nn.LayerNorm backward (+ the residual branch's gradient)   transformers.py:194-238
  *   regtr_bias_relu_bwd       nn.Linear bias gradient, F.relu backward   transformers.py:194-238
+ *   regtr_nbr_transpose       the neighbour table by support (what autograd's index backward scatters through)   kpconv_blocks.py:312,391
+ *   regtr_kpconv_gather_bwd   KPConv.forward backward, input features    kpconv_blocks.py:309-394
+ *   regtr_row_div             KPConv.forward backward, the neighbour-count normaliser   kpconv_blocks.py:409-412
+ *   regtr_gemm_tn_any         KPConv.forward backward, weights (WF^T g) at widths regtr_gemm_tn refuses   kpconv_blocks.py:401-406
  */
 #ifndef REGTR_HIP_H
 #define REGTR_HIP_H
@@ -490,6 +494,50 @@ int regtr_layernorm_bwd(const float* x, int n, int D, const float* gamma, float 
 size_t regtr_bias_relu_bwd_ws_bytes(int n, int N);
 int regtr_bias_relu_bwd(const float* g, int ldg, const float* h, int ldh, float* dh, int ld_dh, float* db, int n, int N, void* ws,
                         size_t ws_bytes, void* stream);
+
+/* ---- KPConv backward (regtr_amd/kpconv_grad.py: KPConv.forward_grad) ---------------------------------------------------------------- */
+
+/* The neighbour table by SUPPORT.  nbr [nq, H] int32 (rows of queries, entries = support indices, anything outside [0, ns) a shadow)
+ * -> a CSR table: row_off [ns + 1] and entries [nq H] (the first row_off[ns] live): support s's incoming entries q H + h with
+ * nbr[q, h] == s are entries[row_off[s] .. row_off[s + 1]), in ASCENDING order.  Shadow entries are dropped.  The in-degree of a
+ * support is not bounded by H.  Six launches: count (integer atomics, whose sums do not depend on their order), a three-launch
+ * exclusive scan, fill through atomic cursors into a scratch list, then one wave per support puts its list in ascending order (rank
+ * among the list's distinct entries; lists above 64 entries are ranked against memory, quadratic in the list length) -- so the table
+ * is a pure function of nbr, whatever the scheduling.  Nothing about it is KPConv's: a max-pool backward walks the same table.
+ * An empty table (nq = 0 or ns = 0) zeroes row_off and launches nothing else (nbr / entries / ws may then be NULL).  Refused
+ * (REGTR_ERR_ARG, nothing launched): a negative count, H < 1, nq H >= 2^31, row_off NULL, nbr / entries / ws NULL with work to do.
+ * ws: regtr_nbr_transpose_ws_bytes(nq, H, ns) bytes (REGTR_ERR_WORKSPACE when smaller; 0 for a refused shape). */
+size_t regtr_nbr_transpose_ws_bytes(int nq, int H, int ns);
+int regtr_nbr_transpose(const int* nbr, int nq, int H, int ns, int* row_off, int* entries, void* ws, size_t ws_bytes, void* stream);
+
+/* Backward of regtr_kpconv_gather with respect to the features: from dwf [nq, KP Cin] (the gradient of wf, row stride KP Cin),
+ *   dx[s, c] = sum over the entries e = q H + h of support s (row_off / entries of regtr_nbr_transpose(nbr, nq, H, ns)), ascending,
+ *              of sum_k infl(q, s, k) dwf[q, k Cin + c],
+ * infl = max(0, 1 - |s_xyz[s] - q_xyz[q] - kernel_points[k]| / extent) recomputed with regtr_kpconv_gather's own statements (uncontracted
+ * squared distance, hardware square root, precomputed 1 / extent), never stored.  The entry's column h plays no part, so nbr itself is
+ * not read.  One wave owns one row of dx: per-lane sums in (entry, k) order, lanes that walk entries side by side (Cin <= 32) combined
+ * by a fixed tree; no atomics, bit-reproducible.  A dwf row whose influence is exactly 0 is not read (so a non-finite value there does
+ * not propagate, unlike 0 x inf).  Every row of dx [ns, Cin] is written -- a support without entries gets +0 -- and nothing past it.
+ * Entries are clamped to [0, nq H): a table of another nbr cannot make a read leave the arrays.  Cin 1 ... 256 (any), KP <= 16,
+ * 1 <= H <= 448.  ns = 0: nothing to do, REGTR_OK.  Refused (REGTR_ERR_ARG, nothing launched): other shapes, a negative count,
+ * extent <= 0, nq H >= 2^31, s_xyz / kernel_points / row_off / dx NULL with work to do, dwf / q_xyz / entries NULL with nq > 0, dwf or
+ * dx not 16-byte aligned. */
+int regtr_kpconv_gather_bwd(const float* dwf, const float* q_xyz, int nq, const float* s_xyz, int ns, int H, int Cin,
+                            const float* kernel_points, int KP, float extent, const int* row_off, const int* entries, float* dx,
+                            void* stream);
+
+/* out[r, c] = x[r, c] / div[r] (IEEE division), r < n, c < N; row strides ldx, ldo >= N.  KPConv's backward through the neighbour count:
+ * g = dOut / num (num is an integer count and carries no gradient).  out may be x.  Refused: n < 0, N < 1, a stride below N, NULLs with
+ * work to do. */
+int regtr_row_div(const float* x, int ldx, const float* div, int n, int N, float* out, int ldo, void* stream);
+
+/* regtr_gemm_tn (no fold) for ANY positive widths: out [N1, N2] = a^T b, a [M, N1], b [M, N2].  The same split-K scheme with guarded
+ * tile edges -- exact-f32 MFMA partial sums over fixed row chunks (a function of M, N1, N2 only), added in chunk order in float64:
+ * bit-reproducible.  KPConv's weight gradient WF^T g at KP Cin = 480, Cout = 32 and the first block's 15-wide WF.  Refused: M < 0, a
+ * width < 1, N1 N2 >= 2^28, a stride below its width, NULLs.  ws: regtr_gemm_tn_any_ws_bytes(M, N1, N2) bytes. */
+size_t regtr_gemm_tn_any_ws_bytes(int M, int N1, int N2);
+int regtr_gemm_tn_any(const float* a, int lda, const float* b, int ldb, int M, int N1, int N2, float* out, int ldo, void* ws,
+                      size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -276,6 +276,14 @@ class KPConv(nn.Module):
         return ops.kpconv(q_pts, s_pts, neighb_inds, x, w, self.kernel_points.detach(), self.KP_extent,
                           x_stats=x_stats, s_seg_off=s_seg_off, q_seg_off=q_seg_off, want_stats=want_stats, xyzf=xyzf)
 
+    def forward_grad(self, q_pts, s_pts, neighb_inds, x, transposed=None):
+        """forward(q_pts, s_pts, neighb_inds, x), bit for bit, as a differentiable call: .backward() fills weights.grad and x.grad
+        through HIP kernels (regtr_amd/kpconv_grad.py).  transposed: ops.nbr_transpose(neighb_inds, Ns), for a caller that runs several
+        convolutions over one table (every resnet block of a level) and builds it once; None builds it in backward.  The fused forms of
+        forward (x_stats, xyzf, want_stats), deformable KPConv and coordinate gradients are not taken (NotImplementedError)."""
+        from .kpconv_grad import forward_grad
+        return forward_grad(self, q_pts, s_pts, neighb_inds, x, transposed)
+
 
 class UnaryBlock(nn.Module):
     """Linear(no bias) -> per-cloud InstanceNorm -> LeakyReLU(0.1) (kpconv_blocks.py:533-567)."""

@@ -780,3 +780,80 @@ def corr_l1_bwd(kp, warped, w, seg_off, pose, grad, den):
                                        seg_off.numel() - 1, n, ptr(pose), pose.shape[-2] * pose.shape[-1], ptr(grad.reshape(1)),
                                        ptr(den.reshape(1)), ptr(out) if n else None, stream()), 'regtr_corr_l1_bwd')
     return out
+
+
+# ------------------------------------------------------------------------------------------------ KPConv backward
+def kpconv_wf(q_xyz, s_xyz, nbr, x, kernel_points, extent):
+    """The gather half of a plain kpconv() call (no x_stats, no xyzf) on its own: -> (wf (Nq, KP Cin), num (Nq,)), the very values that
+    call contracts with the weights and divides by -- what KPConv's backward recomputes instead of keeping wf alive."""
+    L = _lib.lib()
+    nq, H = nbr.shape
+    ns, Cin = x.shape
+    KP = kernel_points.shape[0]
+    flag = None
+    if not (L.regtr_kpconv_gather_computes_flag(Cin, H) and x.data_ptr() % 16 == 0 and ns > 0 and ns * Cin < (1 << 29)):
+        flag = torch.empty(ns, dtype=torch.float32, device=x.device)
+        check(L.regtr_rowsum_positive(ptr(x), ns, Cin, None, None, 0, 0.1, ptr(flag), stream()), 'regtr_rowsum_positive')
+    wf = torch.empty((nq, KP * Cin), dtype=torch.float32, device=x.device)
+    num = torch.empty(nq, dtype=torch.float32, device=x.device)
+    check(L.regtr_kpconv_gather(ptr(q_xyz), nq, ptr(s_xyz), ns, iptr(nbr), H, ptr(x), Cin, ptr(flag), None, ptr(kernel_points), KP,
+                                float(extent), None, None, 0, 0.1, ptr(wf), 0, ptr(num), stream()), 'regtr_kpconv_gather')
+    return wf, num
+
+
+def nbr_transpose(nbr, ns):
+    """The neighbour table by support (regtr_nbr_transpose): nbr (Nq, H) int32, entries outside [0, ns) shadows -> (row_off (ns + 1,),
+    entries (Nq H,)) int32: support s's incoming entries q H + h are entries[row_off[s]:row_off[s + 1]], ascending; entries past
+    row_off[ns] are not written.  A pure function of nbr.  Nothing here synchronises."""
+    L = _lib.lib()
+    nq, H = nbr.shape
+    ns = int(ns)
+    row_off = torch.empty(ns + 1, dtype=torch.int32, device=nbr.device)
+    entries = torch.empty(max(nq * H, 1), dtype=torch.int32, device=nbr.device)
+    nb = L.regtr_nbr_transpose_ws_bytes(nq, H, ns)
+    ws = _ws(max(nb, 1), nbr.device)
+    check(L.regtr_nbr_transpose(iptr(nbr) if nq else None, nq, H, ns, iptr(row_off), iptr(entries), bptr(ws), nb, stream()),
+          'regtr_nbr_transpose')
+    return row_off, entries
+
+
+def kpconv_gather_bwd(dwf, q_xyz, s_xyz, H, kernel_points, extent, transposed, out=None):
+    """Backward of the KPConv gather with respect to the features (regtr_kpconv_gather_bwd): dwf (Nq, KP Cin) the gradient of the
+    weighted-feature rows, transposed = nbr_transpose(nbr, Ns) of the (Nq, H) table the forward gathered through -> dx (Ns, Cin).
+    out: the dx buffer, or None for a new one.  Bit-reproducible.  Nothing here synchronises."""
+    nq, ns, KP = q_xyz.shape[0], s_xyz.shape[0], kernel_points.shape[0]
+    if dwf.shape[0] != nq or dwf.shape[1] % KP:
+        raise RuntimeError(f'kpconv_gather_bwd: dwf must be ({nq}, {KP} Cin), got {tuple(dwf.shape)}')
+    Cin = dwf.shape[1] // KP
+    row_off, entries = transposed
+    if row_off.numel() != ns + 1 or entries.numel() < nq * H:
+        raise RuntimeError(f'kpconv_gather_bwd: the transposed table is not one of a ({nq}, {H}) table over {ns} supports')
+    dx = torch.empty((ns, Cin), dtype=torch.float32, device=dwf.device) if out is None else out
+    if out is not None and tuple(out.shape) != (ns, Cin):
+        raise RuntimeError(f'kpconv_gather_bwd: out must be ({ns}, {Cin}), got {tuple(out.shape)}')
+    check(_lib.lib().regtr_kpconv_gather_bwd(ptr(dwf) if nq else None, ptr(q_xyz) if nq else None, nq, ptr(s_xyz), ns, int(H), Cin,
+                                             ptr(kernel_points), KP, float(extent), iptr(row_off), iptr(entries), ptr(dx), stream()),
+          'regtr_kpconv_gather_bwd')
+    return dx
+
+
+def row_div(x, div):
+    """x (n, N) / div (n,)[:, None] (regtr_row_div): KPConv's backward through its neighbour-count normaliser."""
+    n, N = x.shape
+    out = torch.empty((n, N), dtype=torch.float32, device=x.device)
+    check(_lib.lib().regtr_row_div(ptr(x), N, ptr(div), n, N, ptr(out), N, stream()), 'regtr_row_div')
+    return out
+
+
+def gemm_tn_any(a, b):
+    """gemm_tn (no fold) for any widths (regtr_gemm_tn_any): a (M, N1)^T @ b (M, N2) -> (N1, N2), bit-reproducible."""
+    L = _lib.lib()
+    M, N1 = a.shape
+    N2 = b.shape[1]
+    out = torch.empty((N1, N2), dtype=torch.float32, device=a.device)
+    nb = L.regtr_gemm_tn_any_ws_bytes(M, N1, N2)
+    ws = _ws(max(nb, 1), a.device)
+    check(L.regtr_gemm_tn_any(ptr(a) if M else None, N1, ptr(b) if M else None, N2, M, N1, N2, ptr(out), N2, bptr(ws), nb, stream()),
+          'regtr_gemm_tn_any')
+    return out
+
