@@ -11,6 +11,11 @@ universes GATHER_KERNELS / MAXPOOL_KERNELS.  route_instnorm / route_finalize_til
 n_clouds C = 4096) and route_block_tail csrc/block_tail.hip; their cases are in tests/test_gpu_norm.py and their universes NORM_KERNELS
 ((C, rows) pairs), FINALIZE_KERNELS and TAIL_KERNELS.
 
+The backward launchers follow at the end: route_infonce / route_gemm_tn (csrc/losses.hip), route_layernorm_bwd / route_bias_relu_bwd
+(csrc/layer_bwd.hip, bwd_chunk_rows) and route_gather_bwd / route_nbr_transpose / route_gemm_tn_any (csrc/kpconv_bwd.hip); their cases are in
+tests/test_gpu_bwd_routes.py and the four tests/test_gpu_*_grads.py files, their universes LN_BWD_KERNELS, BIAS_RELU_KERNELS,
+GATHER_BWD_KERNELS, NBR_TRANSPOSE_KERNELS, GEMM_TN_KERNELS (+ TN_ANY_EDGES) and INFONCE_KERNELS.
+
 A route is '+'-joined kernel names: the product kernel, then for split-K its reduction ('reduce', 'reduce_stats/vec' or
 'reduce_stats/novec'), then 'stats_pass' when ops.gemm hands C to regtr_instnorm_stats for the statistics instead (split-K with N / 4 not a power of
 two <= 256, where that pass refuses the width as well: tests/test_gpu_dispatch.py asserts the error)."""
@@ -354,3 +359,159 @@ def route_block_tail(M, N, K1, K2):
 NORM_KERNELS = _norm_kernels()
 FINALIZE_KERNELS = {'fin_wave', 'fin_thread<64>', 'fin_thread<128>', 'fin_thread<256>'}
 TAIL_KERNELS = set().union(*(set(route_block_tail(1, N, K1, K2).split('+')) for N, K1, K2 in ((128, 32, 64), (64, 16, 0))))
+
+
+# ------------------------------------------------------------------------------------------------ backward launchers
+# (csrc/layer_bwd.hip, csrc/kpconv_bwd.hip, csrc/losses.hip; cases in tests/test_gpu_bwd_routes.py and the four *_grads files)
+LN_MAX_D = 1024
+TN_TILE = 64
+SCAN_ITEMS = 1024
+
+
+def bwd_chunk_rows(n):
+    """bwd_chunk_rows: rows per workgroup of both first passes of layer_bwd.hip, a function of n only."""
+    return max(32, 4 * cdiv(n if n > 0 else 1, 4096))
+
+
+def layernorm_bwd_ws_bytes(n, D):                                       # regtr_layernorm_bwd_ws_bytes
+    if n <= 0 or D < 4 or D % 4 or D > LN_MAX_D:
+        return 0
+    return cdiv(n, bwd_chunk_rows(n)) * 2 * D * 4
+
+
+def bias_relu_bwd_ws_bytes(n, N):                                       # regtr_bias_relu_bwd_ws_bytes
+    if n <= 0 or N < 4 or N % 4:
+        return 0
+    return cdiv(n, bwd_chunk_rows(n)) * N * 4
+
+
+def route_layernorm_bwd(n, D):
+    """regtr_layernorm_bwd: 'ln_bwd<NG>/{full|edge}/{rows32|rowsN}'.  NG float4 column groups per lane (256 columns each); 'edge' when
+    some lane's group lies outside the row (the `c < D` branches; 'full': D == 256 NG); 'rowsN' once bwd_chunk_rows leaves 32 rows per
+    workgroup (n > 32768).  The rows are a kernel argument, not an instantiation: the gate holds them to be reached on their own."""
+    if n < 0 or D < 4 or D % 4 or D > LN_MAX_D:
+        return 'refused'
+    if n == 0:
+        return 'none'
+    NG = 1 if D <= 256 else (2 if D <= 512 else 4)
+    return f"ln_bwd<{NG}>/{'full' if D == 256 * NG else 'edge'}/{'rows32' if bwd_chunk_rows(n) == 32 else 'rowsN'}"
+
+
+def bias_relu_cw(N):
+    return 64 if N // 4 >= 64 else (32 if N // 4 >= 32 else 16)
+
+
+def route_bias_relu_bwd(n, N, with_h):
+    """regtr_bias_relu_bwd: 'bias_relu<CW>/{full|edge}/{grouped|tail_only}/{sum|relu}'.  CW float4 columns per workgroup; 'edge' when the
+    last workgroup's columns are partly outside (N / 4 no multiple of CW); 'grouped' when the unrolled loop over four row groups runs its
+    body for at least one thread: row lane 0 of the first chunk has r + 3 TR < r1, TR = 256 / CW, i.e. min(n, chunk rows) > 3 TR."""
+    if n < 0 or N < 4 or N % 4:
+        return 'refused'
+    if n == 0:
+        return 'none'
+    CW = bias_relu_cw(N)
+    TR = 256 // CW
+    grouped = min(n, bwd_chunk_rows(n)) > 3 * TR
+    return (f"bias_relu<{CW}>/{'full' if (N // 4) % CW == 0 else 'edge'}/{'grouped' if grouped else 'tail_only'}/"
+            f"{'relu' if with_h else 'sum'}")
+
+
+def route_gather_bwd(Cin, KP):
+    """regtr_kpconv_gather_bwd: 'gather_bwd<LC,NC>/{full|edge}/{kp15|kp_lt|kp16}'.  LC lanes x NC channels per lane serve an entry; 'edge'
+    when some lane's channel is outside (Cin < LC NC: the dummy-address steering for c >= Cin); kp_lt: KP < 15 (more than one padding
+    lane of the 16 per entry), kp16: none."""
+    if not 1 <= Cin <= 256 or not 1 <= KP <= KP_PAD:
+        return 'refused'
+    LC, NC = (1, 1) if Cin == 1 else (32, 1) if Cin <= 32 else (64, 1) if Cin <= 64 else (64, 2) if Cin <= 128 else (64, 4)
+    return f"gather_bwd<{LC},{NC}>/{'full' if Cin == LC * NC else 'edge'}/{'kp15' if KP == 15 else ('kp16' if KP == 16 else 'kp_lt')}"
+
+
+def nbr_transpose_ws_bytes(nq, H, ns):                                  # regtr_nbr_transpose_ws_bytes
+    if nq < 0 or ns < 0 or H < 1 or nq * H >= 1 << 31:
+        return 0
+
+    def al(b):
+        return (b + 255) & ~255
+    return al(max(ns, 1) * 4) + al((cdiv(ns, SCAN_ITEMS) + 1) * 4) + al(max(nq, 1) * H * 4)
+
+
+def route_nbr_transpose(ns):
+    """regtr_nbr_transpose: 'scan/{per1|perN}' -- block sums per thread of the one-workgroup k_scan_bsums (256 threads over
+    cdiv(ns, 1024) sums: perN from ns > 262144).  The launcher has no other regime: its six kernels are not templated and every launch
+    size follows from (nq H, ns) alone.  'none' for an empty table (a memset only)."""
+    if ns == 0:
+        return 'none'
+    return 'scan/per1' if cdiv(cdiv(ns, SCAN_ITEMS), 256) <= 1 else 'scan/perN'
+
+
+def _tn_plan(M, tiles):
+    """gemm_tn_splits / tn_any_splits -> (splits, chunk): rows per split, a multiple of 4 and at least 64, aiming at 2048 workgroups."""
+    target = cdiv(2048, tiles) if tiles > 0 else 1
+    chunk = max(cdiv(cdiv(M if M > 0 else 1, target), 4) * 4, 64)
+    return (cdiv(M, chunk) if M > 0 else 1), chunk
+
+
+def gemm_tn_plan(M, N1, N2):
+    return _tn_plan(M, (N1 // TN_TILE) * (N2 // TN_TILE))
+
+
+def tn_any_plan(M, N1, N2):
+    return _tn_plan(M, cdiv(N1, TN_TILE) * cdiv(N2, TN_TILE))
+
+
+def gemm_tn_ws_bytes(M, N1, N2):                                        # regtr_gemm_tn_ws_bytes
+    if M < 0 or N1 <= 0 or N2 <= 0 or N1 % TN_TILE or N2 % TN_TILE:
+        return 0
+    return gemm_tn_plan(M, N1, N2)[0] * N1 * N2 * 4
+
+
+def gemm_tn_any_ws_bytes(M, N1, N2):                                    # regtr_gemm_tn_any_ws_bytes
+    if M < 0 or N1 <= 0 or N2 <= 0 or N1 * N2 >= 1 << 28:
+        return 0
+    return tn_any_plan(M, N1, N2)[0] * N1 * N2 * 4
+
+
+def _tn_regime(splits, chunk):
+    return 'one_split' if splits == 1 else ('chunk64' if chunk == 64 else 'chunk_scaled')
+
+
+def route_gemm_tn(M, N1, N2, fold):
+    """regtr_gemm_tn: 'tn/{one_split|chunk64|chunk_scaled}[/fold]' (M = 0 launches too: one split of no rows, a zero result)."""
+    if M < 0 or N1 <= 0 or N2 <= 0 or N1 % TN_TILE or N2 % TN_TILE or (fold and N1 != N2):
+        return 'refused'
+    return 'tn/' + _tn_regime(*gemm_tn_plan(M, N1, N2)) + ('/fold' if fold else '')
+
+
+def route_gemm_tn_any(M, N1, N2):
+    """regtr_gemm_tn_any: 'tn_any/{one_split|chunk64|chunk_scaled}[/edge_n1][/edge_n2]', an edge where the width is no multiple of the
+    64-wide tile (the a_ok / b_ok guards)."""
+    if M < 0 or N1 <= 0 or N2 <= 0 or N1 * N2 >= 1 << 28:
+        return 'refused'
+    return ('tn_any/' + _tn_regime(*tn_any_plan(M, N1, N2)) + ('/edge_n1' if N1 % TN_TILE else '') + ('/edge_n2' if N2 % TN_TILE else ''))
+
+
+def tn_last_chunk(M, plan):
+    """Rows of the last split."""
+    splits, chunk = plan
+    return M - (splits - 1) * chunk
+
+
+def route_infonce(D):
+    """regtr_infonce / regtr_infonce_rows (one kernel, k_infonce<D>) and regtr_infonce_bwd's two launches k_infonce_bwd<D, anchor rows>,
+    k_infonce_bwd<D, positive rows>: what InfoNCELossFull's forward + backward runs."""
+    if D <= 0 or D % 64 or D > 512:
+        return 'refused'
+    return f'infonce<{D}>+infonce_bwd<{D},anc>+infonce_bwd<{D},pos>'
+
+
+LN_BWD_KERNELS = {f'ln_bwd<{NG}>/{e}' for NG in (1, 2, 4) for e in ('full', 'edge')}
+BWD_ROW_REGIMES = {'rows32', 'rowsN'}
+BIAS_RELU_KERNELS = {f'bias_relu<{CW}>/{e}/{g}/{m}' for CW in (16, 32, 64) for e in ('full', 'edge') for g in ('grouped', 'tail_only')
+                     for m in ('sum', 'relu')}
+GATHER_BWD_KERNELS = {f'gather_bwd<{LC},{NC}>/{e}/{k}' for LC, NC in ((1, 1), (32, 1), (64, 1), (64, 2), (64, 4))
+                      for e in (('full',) if LC == 1 else ('full', 'edge')) for k in ('kp15', 'kp_lt', 'kp16')}
+NBR_TRANSPOSE_KERNELS = {'scan/per1', 'scan/perN'}
+GEMM_TN_KERNELS = ({f'tn/{r}{f}' for r in ('one_split', 'chunk64', 'chunk_scaled') for f in ('', '/fold')}
+                   | {f'tn_any/{r}' for r in ('one_split', 'chunk64', 'chunk_scaled')})
+TN_ANY_EDGES = {'tn_any', 'tn_any/edge_n1', 'tn_any/edge_n2', 'tn_any/edge_n1/edge_n2'}
+INFONCE_KERNELS = set().union(*(set(route_infonce(D).split('+')) for D in range(64, 513, 64)))

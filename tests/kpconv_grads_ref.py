@@ -177,7 +177,7 @@ def gather_bwd(q_pts, s_pts, nbr, kp, extent, dwf, ns):
     np.add.at(A, idx, np.einsum('qhk,qkc->qhc', w, np.abs(dwf)))
     np.add.at(E, idx, E_INFL * np.abs(dwf).sum(1)[:, None, :] * real[:, :, None])
     deg = np.bincount(idx.reshape(-1), minlength=ns + 1)[:ns]
-    return dx[:ns], (KP * deg[:, None] + C_DX) * U * A[:ns] + E[:ns]
+    return dx[:ns], (np.asarray(kp).shape[0] * deg[:, None] + C_DX) * U * A[:ns] + E[:ns]
 
 
 def torch_forward(q_pts, s_pts, nbr, x, weights, kp, extent):

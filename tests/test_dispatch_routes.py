@@ -5,7 +5,9 @@ The mirror is checked against the plan queries libregtr_hip.so exports (host-onl
 instantiation of the launch ladders (dispatch.X3_KERNELS / STREAM_KERNELS / MHA_KERNELS / ATTN_XYZ_KERNELS / GATHER_KERNELS /
 MAXPOOL_KERNELS) and fails when no parametrized GPU case of tests/test_gpu_dispatch.py, tests/test_gpu_ops.py, tests/test_gpu_pose.py or
 tests/test_gpu_gather.py routes to one -- e.g. after a planner retune moved a case off its branch.  The gather mirror is checked against the library's regtr_kpconv_gather_computes_flag only:
-a refusal is never probed by calling a launcher with stand-in pointers (a mirror wrong about it would launch on garbage)."""
+a refusal is never probed by calling a launcher with stand-in pointers (a mirror wrong about it would launch on garbage).  The backward
+launchers (losses, LayerNorm / bias-ReLU, KPConv) are mirrored and gated the same way at the end of the file: their planners against
+the workspace queries, their universes against tests/test_gpu_bwd_routes.py and the four *_grads files."""
 import itertools
 
 from tests import dispatch
@@ -308,3 +310,154 @@ def test_every_tail_instantiation_is_reached():
         routes += [dispatch.route_stream(M, N, K, fold) for fold in ((False, True) if K <= 64 else (False,))]
     _gate(dispatch.STREAM_KERNELS, routes)
     assert {li for li, _, _ in _params(gn.test_gemm_stream_vs_fp64, ['li', 'K', 'N'])} == set(range(len(test_gpu_ops.STREAM_LENS)))
+
+
+# ------------------------------------------------------------------------------------------------ the backward launchers
+BWD_NS = [0, 1, 31, 32, 33, 4099, 32767, 32768, 32769, 32772, 32773, 49151, 49152, 49153, 131072, 131073, 1000000, 2400000]
+
+
+def test_bwd_chunk_rows_mirror_matches_library():
+    """bwd_chunk_rows through the two workspace queries that reveal the chunk count: cdiv(n, rows) 2 D 4 and cdiv(n, rows) N 4 bytes,
+    0 for what the launchers refuse; 32 rows up to n = 32768, 36 from 32769, 48 up to 49152, 52 from 49153."""
+    from regtr_amd import _lib
+    from tests import cross_encoder_grads_ref as CR
+    L = _lib.lib()
+    for n, W in itertools.product(BWD_NS + [-1], [0, 2, 4, 6, 60, 64, 128, 252, 256, 260, 512, 516, 1020, 1024, 1028, 3072]):
+        assert L.regtr_layernorm_bwd_ws_bytes(n, W) == dispatch.layernorm_bwd_ws_bytes(n, W), (n, W)
+        assert L.regtr_bias_relu_bwd_ws_bytes(n, W) == dispatch.bias_relu_bwd_ws_bytes(n, W), (n, W)
+        assert dispatch.bwd_chunk_rows(n) == CR.chunk_rows(n)                 # the yardstick's own restatement agrees
+    assert [dispatch.bwd_chunk_rows(n) for n in (32768, 32769, 49152, 49153)] == [32, 36, 48, 52]
+    assert L.regtr_layernorm_bwd_ws_bytes(32769, 64) == -(-32769 // 36) * 2 * 64 * 4
+    assert dispatch.route_layernorm_bwd(5, 1028) == 'refused' and dispatch.route_layernorm_bwd(0, 64) == 'none'
+    assert dispatch.route_bias_relu_bwd(5, 6, False) == 'refused' and dispatch.route_bias_relu_bwd(0, 64, True) == 'none'
+    # 'grouped' from the chunk rows: the narrow kernel's 16 row lanes need 49 rows, which only a chunk beyond 48 rows has
+    assert dispatch.route_bias_relu_bwd(49152, 64, False) == 'bias_relu<16>/full/tail_only/sum'
+    assert dispatch.route_bias_relu_bwd(49153, 64, False) == 'bias_relu<16>/full/grouped/sum'
+    assert dispatch.route_bias_relu_bwd(24, 128, True) == 'bias_relu<32>/full/tail_only/relu'
+    assert dispatch.route_bias_relu_bwd(25, 128, True) == 'bias_relu<32>/full/grouped/relu'
+
+
+def _tn_thresholds(tiles):
+    """The row counts at which the split plan of a shape with this many tiles changes regime: one split up to 64 rows, 64-row chunks
+    up to 64 target rows (target = cdiv(2048, tiles)), scaled chunks beyond."""
+    t = 64 * -(-2048 // tiles)
+    return [0, 1, 3, 4, 63, 64, 65, 127, 128, 129, 203, t - 1, t, t + 1, t + 4, 2 * t + 5, 8197, 131077, 2400000]
+
+
+def test_gemm_tn_split_mirror_matches_library():
+    """gemm_tn_splits / tn_any_splits through the workspace queries (splits N1 N2 4 bytes), at each shape's thresholds +- 1."""
+    from regtr_amd import _lib
+    L = _lib.lib()
+    n = 0
+    for N1, N2 in [(64, 64), (256, 256), (64, 128), (512, 512), (1024, 1024), (15, 64), (64, 50), (480, 32), (480, 96), (70, 50),
+                   (130, 17), (1, 1), (3840, 256)]:
+        for M in _tn_thresholds((N1 // 64) * (N2 // 64) or 1) + _tn_thresholds(-(-N1 // 64) * -(-N2 // 64)) + [-1]:
+            assert L.regtr_gemm_tn_ws_bytes(M, N1, N2) == dispatch.gemm_tn_ws_bytes(M, N1, N2), (M, N1, N2)
+            assert L.regtr_gemm_tn_any_ws_bytes(M, N1, N2) == dispatch.gemm_tn_any_ws_bytes(M, N1, N2), (M, N1, N2)
+            n += 1
+    assert n > 400
+    assert L.regtr_gemm_tn_any_ws_bytes(4, 16384, 16384) == 0 and dispatch.route_gemm_tn_any(4, 16384, 16384) == 'refused'
+    assert dispatch.route_gemm_tn(4, 15, 64, False) == 'refused' and dispatch.route_gemm_tn(4, 64, 128, True) == 'refused'
+    # (256, 256): 16 tiles, 128 splits aimed at -- 64-row chunks up to 8192 rows, 68 from 8193
+    assert [dispatch.gemm_tn_plan(M, 256, 256) for M in (64, 65, 8192, 8193)] == [(1, 64), (2, 64), (128, 64), (121, 68)]
+    assert dispatch.tn_any_plan(131072, 15, 64) == (2048, 64) and dispatch.tn_any_plan(131073, 15, 64) == (1928, 68)
+
+
+def test_nbr_transpose_mirror_matches_library():
+    """The workspace of regtr_nbr_transpose (cursors | block sums | scratch list) and the one regime of its scan: k_scan_bsums takes
+    cdiv(cdiv(ns, 1024), 256) block sums per thread, one up to ns = 262144."""
+    from regtr_amd import _lib
+    L = _lib.lib()
+    for ns, (nq, H) in itertools.product([0, 1, 1023, 1024, 1025, 4096, 262143, 262144, 262145, 300001, 2400000],
+                                         [(0, 7), (1, 1), (3000, 5), (20000, 5), (2 ** 27, 16)]):
+        assert L.regtr_nbr_transpose_ws_bytes(nq, H, ns) == dispatch.nbr_transpose_ws_bytes(nq, H, ns), (nq, H, ns)
+    assert [dispatch.route_nbr_transpose(ns) for ns in (0, 1, 262144, 262145)] == ['none', 'scan/per1', 'scan/per1', 'scan/perN']
+
+
+def _bwd():
+    from tests import test_gpu_bwd_routes
+    return test_gpu_bwd_routes
+
+
+def test_every_infonce_bwd_instantiation_is_reached():
+    from tests import test_gpu_loss_grads as gl
+    routes = []
+    for D, route in _params(_bwd().test_infonce_widths_vs_float64, ['D', 'route']):
+        assert dispatch.route_infonce(D) == route, D
+        routes.append(route)
+    routes += [dispatch.route_infonce(D) for (D,) in _params(gl.test_infonce_grads_vs_float64, ['D'])]
+    _gate(dispatch.INFONCE_KERNELS, routes)
+    assert len(dispatch.INFONCE_KERNELS) == 24 and dispatch.route_infonce(576) == dispatch.route_infonce(96) == 'refused'
+
+
+def test_every_layernorm_bwd_instantiation_is_reached():
+    """Every k_layernorm_bwd<NG> with and without a partly outside column group; the rows per workgroup are a kernel argument that no
+    instantiation treats differently, and are held to be reached as a regime of their own (32 and beyond), as are many chunks."""
+    from tests import test_gpu_cross_encoder_grads as gc
+    routes = []
+    for n, D, route in _params(_bwd().test_layernorm_bwd_vs_float64, ['n', 'D', 'route']):
+        assert dispatch.route_layernorm_bwd(n, D) == route, (n, D)
+        routes.append(route)
+    routes += [dispatch.route_layernorm_bwd(n, D) for (D,) in _params(gc.test_layernorm_bwd_against_float64, ['D']) for n in gc.ROWS]
+    _gate(dispatch.LN_BWD_KERNELS, [r.rsplit('/', 1)[0] for r in routes])
+    _gate(dispatch.BWD_ROW_REGIMES, [r.rsplit('/', 1)[1] for r in routes])
+    cases = _params(_bwd().test_layernorm_bwd_vs_float64, ['n', 'D'])
+    assert any(n > 32 * 64 and D > 512 for n, D in cases)                     # more chunks than one lane of the final sum takes
+
+
+def test_every_bias_relu_bwd_instantiation_is_reached():
+    """Every case runs without h ('sum', its route) and with it ('relu'), as do the model's widths in the cross-encoder file."""
+    from tests import test_gpu_cross_encoder_grads as gc
+    routes = [dispatch.route_bias_relu_bwd(n, N, with_h) for (N,) in _params(gc.test_bias_relu_bwd_against_float64, ['N']) for n in gc.ROWS
+              for with_h in (False, True)]
+    for n, N, route in _params(_bwd().test_bias_relu_bwd_vs_float64, ['n', 'N', 'route']):
+        assert dispatch.route_bias_relu_bwd(n, N, False) == route, (n, N)
+        routes += [route, dispatch.route_bias_relu_bwd(n, N, True)]
+    _gate(dispatch.BIAS_RELU_KERNELS, routes)
+    assert {k for (k,) in _params(_bwd().test_bias_relu_bwd_vs_float64, ['kind'])} == {'normal', 'exact'}
+
+
+def test_every_gather_bwd_instantiation_is_reached():
+    from tests import kpconv_grads_ref as KR
+    from tests import test_gpu_kpconv_grads as gk
+    routes = []
+    for Cin, KP, route in _params(_bwd().test_gather_bwd_widths_vs_float64, ['Cin', 'KP', 'route']):
+        assert dispatch.route_gather_bwd(Cin, KP) == route, (Cin, KP)
+        routes.append(route)
+    routes += [dispatch.route_gather_bwd(KR.CASES[name]['Cin'], KR.KP) for (name,) in _params(gk.test_gather_bwd_vs_float64, ['name'])]
+    _gate(dispatch.GATHER_BWD_KERNELS, routes)
+    assert dispatch.route_gather_bwd(257, 15) == dispatch.route_gather_bwd(32, 17) == dispatch.route_gather_bwd(0, 15) == 'refused'
+
+
+def test_every_nbr_transpose_bwd_instantiation_is_reached():
+    routes = []
+    for ns, route in _params(_bwd().test_nbr_transpose_scan_regimes, ['ns', 'route']):
+        assert dispatch.route_nbr_transpose(ns) == route, ns
+        routes.append(route)
+    _gate(dispatch.NBR_TRANSPOSE_KERNELS, routes)
+    assert any(ns % 1024 == 0 for ns, _ in _params(_bwd().test_nbr_transpose_scan_regimes, ['ns', 'route']))
+
+
+def test_every_gemm_tn_bwd_instantiation_is_reached():
+    """Both entry points in every split regime (the fold in each); regtr_gemm_tn_any's two edge guards in every combination; the
+    scaled-chunk cases have chunks beyond 64 rows and a last split whose length is no multiple of 4; M = 0, M < 4 and M = 4 occur."""
+    routes, edges, scaled = [], [], 0
+    for kind, M, N1, N2, route in _params(_bwd().test_gemm_tn_vs_float64, 'kind M N1 N2 route'.split()):
+        if kind == 'tn_any':
+            assert dispatch.route_gemm_tn_any(M, N1, N2) == route, (M, N1, N2)
+            plan = dispatch.tn_any_plan(M, N1, N2)
+            regime = '/'.join(route.split('/')[:2])
+            routes.append(regime)
+            edges.append('tn_any' + route[len(regime):])
+        else:
+            assert dispatch.route_gemm_tn(M, N1, N2, kind == 'tn_fold') == route, (kind, M, N1, N2)
+            plan = dispatch.gemm_tn_plan(M, N1, N2)
+            routes.append(route)
+        if 'chunk_scaled' in route:
+            assert plan[1] > 64 and plan[0] > 1 and dispatch.tn_last_chunk(M, plan) % 4 != 0, (kind, M, N1, N2, plan)
+            scaled += 1
+    _gate(dispatch.GEMM_TN_KERNELS, routes)
+    _gate(dispatch.TN_ANY_EDGES, edges)
+    assert scaled >= 5
+    for kind in ('tn', 'tn_fold', 'tn_any'):
+        assert {0, 1, 3, 4} <= {M for k, M, _, _, _ in _params(_bwd().test_gemm_tn_vs_float64, 'kind M N1 N2 route'.split()) if k == kind}

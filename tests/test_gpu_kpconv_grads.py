@@ -4,8 +4,7 @@ tests/kpconv_grads_ref.py under its float32 error bounds AND the flat 1e-4 bar e
 the reference module's goldens; forward bit-identity with KPConv.forward; determinism; independence of the forward's operand format;
 one-sided requires_grad.
 
-Every comparison prints err / bound and the flat ratio per case; docs/PARITY.md is where the worst of each belongs (not taken yet:
-this file has not run on an MI355X)."""
+Every comparison prints err / bound and the flat ratio per case; docs/PARITY.md has the worst of each."""
 import os
 
 import numpy as np

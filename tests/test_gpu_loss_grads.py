@@ -67,15 +67,11 @@ def test_drop_ins_vs_reference_golden(case):
     print(case, f'loss rel {abs(loss - ref) / abs(ref):.1e}, feature grads worst rel {max(rep):.1e}, dW rel {err:.1e}')
 
 
-@pytest.mark.parametrize('D', [64, 256, 512])
-@pytest.mark.parametrize('layout', ['sizes', 'ragged'])
-def test_infonce_grads_vs_float64(D, layout):
+def infonce_grads_case(rng, sizes, D):
+    """InfoNCELossFull forward + backward on ragged pairs of these sizes plus _make_pairs' three special pairs, against the float64
+    restatement under its bounds: masks, lowest-index ties, exact zeros for the NaN pair, a strictly lower-triangular zero dW.
+    -> (number of pairs, worst err / bound).  Shared with tests/test_gpu_bwd_routes.py (the other D instantiations)."""
     from regtr_amd import ops
-    rng = np.random.default_rng(100 + D + (0 if layout == 'sizes' else 1))
-    if layout == 'sizes':
-        sizes = [(SIZES[i], SIZES[(7 * i + 3) % len(SIZES)]) for i in range(len(SIZES) - 1)] + [(1, 1), (1, 40), (40, 1)]
-    else:
-        sizes = [(int(rng.integers(1, 300)), int(rng.integers(1, 300))) for _ in range(13)]
     pairs = _make_pairs(rng, sizes, D)                    # + the NaN pair, the all-within-r_n pair, duplicated targets
     W = (rng.normal(0, 0.1, (D, D)) / np.sqrt(D / 64)).astype(F32)
     loss, dA, dG, dW = _run_infonce(pairs, W)
@@ -110,7 +106,19 @@ def test_infonce_grads_vs_float64(D, layout):
     nan_pair, zero_pair = len(pairs) - 3, len(pairs) - 2
     assert np.all(dA[nan_pair] == 0) and np.all(dG[nan_pair] == 0)          # exactly 0, as torch autograd of an empty mask
     assert np.all(np.tril(dW, -1) == 0)
-    print(f'infonce grads D={D} {layout}: {len(pairs)} pairs, worst err/bound {worst:.3f}')
+    return len(pairs), worst
+
+
+@pytest.mark.parametrize('D', [64, 256, 512])
+@pytest.mark.parametrize('layout', ['sizes', 'ragged'])
+def test_infonce_grads_vs_float64(D, layout):
+    rng = np.random.default_rng(100 + D + (0 if layout == 'sizes' else 1))
+    if layout == 'sizes':
+        sizes = [(SIZES[i], SIZES[(7 * i + 3) % len(SIZES)]) for i in range(len(SIZES) - 1)] + [(1, 1), (1, 40), (40, 1)]
+    else:
+        sizes = [(int(rng.integers(1, 300)), int(rng.integers(1, 300))) for _ in range(13)]
+    n_pairs, worst = infonce_grads_case(rng, sizes, D)
+    print(f'infonce grads D={D} {layout}: {n_pairs} pairs, worst err/bound {worst:.3f}')
 
 
 def test_forward_bit_identical_to_compute_loss_path():
