@@ -48,6 +48,9 @@
  *   regtr_kpconv_gather_bwd   KPConv.forward backward, input features    kpconv_blocks.py:309-394
  *   regtr_row_div             KPConv.forward backward, the neighbour-count normaliser   kpconv_blocks.py:409-412
  *   regtr_gemm_tn_any         KPConv.forward backward, weights (WF^T g) at widths regtr_gemm_tn refuses   kpconv_blocks.py:401-406
+ *   regtr_instnorm_bwd        BatchNormBlock (InstanceNorm1d) + LeakyReLU + shortcut, backward   kpconv_blocks.py:497-519,556-561,741
+ *   regtr_maxpool_argmax      max_pool: the index torch.max(dim) keeps for autograd   kpconv_blocks.py:142
+ *   regtr_maxpool_gather_bwd  max_pool backward                   kpconv_blocks.py:127-143
  */
 #ifndef REGTR_HIP_H
 #define REGTR_HIP_H
@@ -538,6 +541,54 @@ int regtr_row_div(const float* x, int ldx, const float* div, int n, int N, float
 size_t regtr_gemm_tn_any_ws_bytes(int M, int N1, int N2);
 int regtr_gemm_tn_any(const float* a, int lda, const float* b, int ldb, int M, int N1, int N2, float* out, int ldo, void* ws,
                       size_t ws_bytes, void* stream);
+
+/* ---- InstanceNorm and max-pool backward (regtr_amd/backbone_grad.py: instance_norm, max_pool) ----------------------------------------- */
+
+/* Backward of regtr_instnorm_apply taken together with regtr_instnorm_stats, i.e. of
+ *   y = act( (x - mean) rstd  [+ res | + (res - rmean) rrstd] ),   act 0 none / 1 LeakyReLU(slope),
+ * per cloud segment and channel, (mean, rstd) = stats and (rmean, rrstd) = res_stats being the biased-variance statistics of x and res
+ * (so the gradient flows through them too).  x, seg_off, n_clouds, max_len, C, stats, residual, res_stats, act and slope are exactly
+ * what the forward took (stats is required here); dy [N, C] is the gradient of y.  With z the activation's argument, recomputed with
+ * the forward's own arithmetic so that every element's LeakyReLU side is the forward's, g = dy (z > 0 ? 1 : slope), xh = (x - mean) rstd
+ * and means taken over the cloud's rows:
+ *   dx   = rstd (g - mean(g) - xh mean(g xh))
+ *   dres = g                                       (plain shortcut: res_stats NULL)
+ *        = rrstd (g - mean(g) - rh mean(g rh))     (normalised shortcut, rh = (res - rmean) rrstd)
+ * dx and dres are optional (NULL: not wanted), at least one is given, dres needs residual.  Three launches in regtr_instnorm_stats'
+ * thread mapping and chunking: per-(cloud, chunk, channel) sums of g, g xh and g rh in float64, one wave per (cloud, channel) adding
+ * the chunks in a fixed order, then the apply pass (the first two are skipped when only a plain shortcut's dres is wanted).  One owner
+ * per output element, no atomics, bit-reproducible.  Every row of every cloud is written and nothing else; an empty cloud does no
+ * work; a one-row cloud gets dx = 0 exactly.  max_len >= every cloud's length; max_len = 0: nothing to do, REGTR_OK.  Refused
+ * (REGTR_ERR_ARG, nothing launched): n_clouds < 1, max_len < 0, C not a multiple of 4 with C / 4 a power of two <= 256, act not 0 / 1,
+ * x / seg_off / stats / dy NULL, dx and dres both NULL, dres or res_stats without residual, a pointer that is not 16-byte aligned, ws
+ * NULL when the sums are needed.  ws: regtr_instnorm_bwd_ws_bytes(n_clouds, max_len, C) bytes (REGTR_ERR_WORKSPACE when smaller; 0 for
+ * a refused shape). */
+size_t regtr_instnorm_bwd_ws_bytes(int n_clouds, int max_len, int C);
+int regtr_instnorm_bwd(const float* x, const int* seg_off, int n_clouds, int max_len, int C, const float* stats, const float* residual,
+                       const float* res_stats, int act, float slope, const float* dy, float* dx, float* dres, void* ws, size_t ws_bytes,
+                       void* stream);
+
+/* The index regtr_maxpool_gather's maximum came from: for x [ns, C], nbr [nq, ld_nbr] and the first H columns of it (the forward's
+ * shapes and ld_nbr / H contract), arg [nq, C] int16: arg[q, c] = the column h whose row wins channel c of query q.  The shadow index
+ * ns, or anything outside [0, ns), stands for a zero row.  On equal values the LOWEST column wins (torch.max(dim)'s rule, to which
+ * autograd sends the whole gradient); arg = -1 when the winner is a shadow row, which has no gradient target.  x is expected finite (a
+ * NaN never wins).  Query owner; the feature rows are read from clamped indices.  nq = 0: nothing to do, REGTR_OK; ns = 0: every arg
+ * is -1.  Refused (REGTR_ERR_ARG, nothing launched): a negative count, H < 1, H > 32767, ld_nbr < H, C < 4 or not a multiple of 4,
+ * NULLs with work to do, x not 16-byte or arg not 8-byte aligned. */
+int regtr_maxpool_argmax(const float* x, int ns, int C, const int* nbr, int ld_nbr, int nq, int H, short* arg, void* stream);
+
+/* Backward of regtr_maxpool_gather: from dy [nq, C] and arg [nq, C] (regtr_maxpool_argmax),
+ *   dx[s, c] = sum over the entries e = q H + h of support s (row_off / entries of regtr_nbr_transpose(nbr, nq, H, ns)), ascending,
+ *              of (arg[q, c] == h ? dy[q, c] : +0).
+ * Support owner: one lane owns a float4 of channels of one dx row and takes its float32 sum SEQUENTIALLY in ascending entry order, so
+ * the result is a pure function of (dy, arg, table) that a float32 restatement reproduces bit for bit.  nbr itself is not read; arg is
+ * compared, never used as an index; entries are clamped to [0, nq H) and the list bounds to [0, nq H], so a table of another nbr
+ * cannot make a read leave the arrays.  The in-degree of a support is unbounded.  Every row of dx [ns, C] is written -- a support
+ * without entries gets +0 -- and nothing past it.  ns = 0: nothing to do, REGTR_OK; nq = 0: dx is all +0, REGTR_OK.  Refused
+ * (REGTR_ERR_ARG, nothing launched): a negative count, H < 1, H > 32767, C < 4 or not a multiple of 4, nq H >= 2^31, row_off / dx
+ * NULL with ns > 0, dy / arg / entries NULL with nq > 0 and ns > 0, dy / dx not 16-byte or arg not 8-byte aligned. */
+int regtr_maxpool_gather_bwd(const float* dy, const short* arg, int nq, int H, int C, const int* row_off, const int* entries, int ns,
+                             float* dx, void* stream);
 
 #ifdef __cplusplus
 }

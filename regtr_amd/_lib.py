@@ -125,6 +125,10 @@ SIGNATURES = {
     'regtr_row_div': (_I, [_P, _I, _P, _I, _I, _P, _I, _P]),
     'regtr_gemm_tn_any_ws_bytes': (_Z, [_I, _I, _I]),
     'regtr_gemm_tn_any': (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _Z, _P]),
+    'regtr_instnorm_bwd_ws_bytes': (_Z, [_I, _I, _I]),
+    'regtr_instnorm_bwd': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _F, _P, _P, _P, _P, _Z, _P]),
+    'regtr_maxpool_argmax': (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _P]),
+    'regtr_maxpool_gather_bwd': (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P, _P]),
 }
 
 COMPOSITE = ('regtr_encoder_fwd', 'regtr_cross_encoder_fwd')      # bound through a GIL-releasing handle (see _load)

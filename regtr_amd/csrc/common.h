@@ -42,6 +42,19 @@ static inline unsigned rg_next_pow2(unsigned x)
     return p;
 }
 
+// Rows of one cloud per workgroup of an InstanceNorm launch (norm.hip forward, norm_pool_bwd.hip backward) over clouds of at most max_len
+// rows.  128 everywhere a launch fills the chip anyway; a pair or two per forward leaves the deep levels with a handful of 128-row workgroups
+// (751 rows x 1024 channels: 8 workgroups, each thread walking 128 rows -- 35 us for 9 MB), so the chunk is halved until the launch has ~1000
+// workgroups or a workgroup is down to four row steps / 8 rows.  Host-side and a function of the launch geometry only (never of the data);
+// the statistics kernels add a cloud's chunks in chunk order whatever their length, so results stay run-to-run deterministic.
+static inline int rg_in_rows(int max_len, int n_clouds, int C)
+{
+    const int TR = 256 / (C >> 2);
+    int rows = 128;
+    while (rows > 4 * TR && rows > 8 && (long long)rg_cdiv(max_len > 0 ? max_len : 1, rows) * n_clouds < 1024) rows >>= 1;
+    return rows;
+}
+
 // carve a sub-buffer out of a caller-provided workspace (256-B aligned)
 struct RgCarver {
     char* base;

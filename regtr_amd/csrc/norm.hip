@@ -9,21 +9,6 @@
 
 namespace {
 
-constexpr int IN_ROWS = 128;   // rows of one cloud handled by one workgroup (large launches)
-
-// Rows per workgroup of a launch over clouds of at most max_len rows.  128 everywhere a launch fills the chip anyway; a pair or two per forward
-// leaves the deep levels with a handful of 128-row workgroups (751 rows x 1024 channels: 8 workgroups, each thread walking 128 rows -- 35 us
-// for 9 MB), so the chunk is halved until the launch has ~1000 workgroups or a workgroup is down to four row steps / 8 rows.  Host-side
-// and a function of the launch geometry only (never of the data); the statistics kernels add a cloud's chunks in chunk order whatever their
-// length, so results stay run-to-run deterministic.
-inline int in_rows(int max_len, int n_clouds, int C)
-{
-    const int TR = 256 / (C >> 2);
-    int rows = IN_ROWS;
-    while (rows > 4 * TR && rows > 8 && (long long)rg_cdiv(max_len > 0 ? max_len : 1, rows) * n_clouds < 1024) rows >>= 1;
-    return rows;
-}
-
 // Thread mapping shared by the InstanceNorm kernels: C4 = C/4 float4 columns (a power of two <= 256); thread
 // (tx = t % C4, ty = t / C4) owns column group tx for rows ty, ty + TR, ... so that every row is one contiguous read and
 // the per-channel statistics a thread needs stay in registers for the whole tile.
@@ -281,7 +266,7 @@ extern "C" {
 size_t regtr_instnorm_ws_bytes(int n_clouds, int max_len, int C)
 {
     if (n_clouds < 1 || C < 4 || C % 4 || C > 1024 || 256 % (C / 4)) return 256;
-    const size_t nchunk = (size_t)rg_cdiv(max_len > 0 ? max_len : 1, in_rows(max_len, n_clouds, C));
+    const size_t nchunk = (size_t)rg_cdiv(max_len > 0 ? max_len : 1, rg_in_rows(max_len, n_clouds, C));
     return nchunk * n_clouds * C * sizeof(double2) + 256;
 }
 
@@ -294,7 +279,7 @@ int regtr_instnorm_stats(const float* x, const int* seg_off, int n_clouds, int m
     if (ws_bytes < regtr_instnorm_ws_bytes(n_clouds, max_len, C)) return RG_ERR_WORKSPACE;
     if (max_len == 0) return RG_OK;
     hipStream_t st = (hipStream_t)stream;
-    const int rows = in_rows(max_len, n_clouds, C);
+    const int rows = rg_in_rows(max_len, n_clouds, C);
     const int nchunk = rg_cdiv(max_len, rows);
     k_instnorm_partial<<<dim3(nchunk, n_clouds), 256, 0, st>>>(x, seg_off, C, nchunk, rows, (double2*)ws);
     k_instnorm_finalize<<<dim3(rg_cdiv(C, 4), n_clouds), 256, 0, st>>>((const double2*)ws, seg_off, C, nchunk, rows, eps,
@@ -332,7 +317,7 @@ int regtr_instnorm_apply(const float* x, const int* seg_off, int n_clouds, int m
     if (C > 1024 || 256 % (C / 4) || (row_positive && C > 256) || (row_xyz && (!row_positive || (uintptr_t)row_positive % 16)))
         return RG_ERR_ARG;
     if (max_len == 0) return RG_OK;
-    const int rows = in_rows(max_len, n_clouds, C);
+    const int rows = rg_in_rows(max_len, n_clouds, C);
     k_instnorm_apply<<<dim3(rg_cdiv(max_len, rows), n_clouds), 256, 0, (hipStream_t)stream>>>(
         x, seg_off, C, (const float2*)stats, residual, (const float2*)res_stats, act, slope, y, row_xyz, row_positive, rows);
     RG_RETURN_IF_LAUNCH_FAILED();

@@ -837,6 +837,63 @@ def kpconv_gather_bwd(dwf, q_xyz, s_xyz, H, kernel_points, extent, transposed, o
     return dx
 
 
+def instnorm_bwd(x, seg_off, max_len, stats, dy, residual=None, res_stats=None, lrelu=False, slope=0.1, want_dx=True, want_dres=False,
+                 out_dx=None, out_dres=None):
+    """Backward of instnorm_apply(x, seg_off, max_len, instnorm_stats(x), residual, res_stats [= instnorm_stats(residual)], lrelu, slope)
+    (regtr_instnorm_bwd): the forward's own arguments plus dy (N, C), the gradient of its output -> (dx, dres), None where not wanted.
+    out_dx / out_dres: the buffers to write, or None for new ones.  Bit-reproducible.  Nothing here synchronises."""
+    L = _lib.lib()
+    n_clouds = seg_off.numel() - 1
+    N, C = x.shape
+    if tuple(dy.shape) != (N, C) or (residual is not None and tuple(residual.shape) != (N, C)):
+        raise RuntimeError(f'instnorm_bwd: dy and residual must be ({N}, {C}) like x')
+    if want_dres and residual is None:
+        raise RuntimeError('instnorm_bwd: want_dres needs the residual the forward took')
+    dx = dres = None
+    if want_dx:
+        dx = torch.empty_like(x) if out_dx is None else out_dx
+    if want_dres:
+        dres = torch.empty_like(x) if out_dres is None else out_dres
+    for o in (dx, dres):
+        if o is not None and tuple(o.shape) != (N, C):
+            raise RuntimeError(f'instnorm_bwd: an output buffer must be ({N}, {C}), got {tuple(o.shape)}')
+    nb = L.regtr_instnorm_bwd_ws_bytes(n_clouds, int(max_len), C)
+    ws = _ws(max(nb, 1), x.device)
+    check(L.regtr_instnorm_bwd(ptr(x), iptr(seg_off), n_clouds, int(max_len), C, ptr(stats), ptr(residual), ptr(res_stats),
+                               1 if lrelu else 0, slope, ptr(dy), ptr(dx), ptr(dres), bptr(ws), nb, stream()), 'regtr_instnorm_bwd')
+    return dx, dres
+
+
+def maxpool_argmax(x, nbr, width=None, out=None):
+    """The column of nbr (of the first `width`) each maximum of maxpool(x, nbr, width) came from (regtr_maxpool_argmax): (Nq, C) int16, the
+    lowest column on equal values, -1 where the zero shadow row won.  out: the buffer to write, or None for a new one."""
+    ns, C = x.shape
+    nq, ld = nbr.shape
+    arg = torch.empty((nq, C), dtype=torch.int16, device=x.device) if out is None else out
+    if tuple(arg.shape) != (nq, C):
+        raise RuntimeError(f'maxpool_argmax: out must be ({nq}, {C}), got {tuple(arg.shape)}')
+    check(_lib.lib().regtr_maxpool_argmax(ptr(x) if ns else None, ns, C, iptr(nbr) if nq else None, ld, nq, ld if width is None else int(width),
+                                          ptr(arg, torch.int16) if nq else None, stream()), 'regtr_maxpool_argmax')
+    return arg
+
+
+def maxpool_bwd(dy, arg, H, transposed, out=None):
+    """Backward of maxpool (regtr_maxpool_gather_bwd): dy (Nq, C) the gradient of the pooled rows, arg = maxpool_argmax(...) of the same
+    call, transposed = nbr_transpose(the (Nq, H) table the forward pooled through, Ns) -> dx (Ns, C).  out: the dx buffer, or None for a
+    new one.  A float32 sum in ascending entry order per element: bit-reproducible.  Nothing here synchronises."""
+    nq, C = dy.shape
+    row_off, entries = transposed
+    ns = row_off.numel() - 1
+    if tuple(arg.shape) != (nq, C) or entries.numel() < nq * H:
+        raise RuntimeError(f'maxpool_bwd: arg must be ({nq}, {C}) and the transposed table one of a ({nq}, {H}) table')
+    dx = torch.empty((ns, C), dtype=torch.float32, device=dy.device) if out is None else out
+    if tuple(dx.shape) != (ns, C):
+        raise RuntimeError(f'maxpool_bwd: out must be ({ns}, {C}), got {tuple(dx.shape)}')
+    check(_lib.lib().regtr_maxpool_gather_bwd(ptr(dy) if nq else None, ptr(arg, torch.int16) if nq else None, nq, int(H), C, iptr(row_off),
+                                              iptr(entries) if nq else None, ns, ptr(dx) if ns else None, stream()), 'regtr_maxpool_gather_bwd')
+    return dx
+
+
 def row_div(x, div):
     """x (n, N) / div (n,)[:, None] (regtr_row_div): KPConv's backward through its neighbour-count normaliser."""
     n, N = x.shape
