@@ -16,6 +16,11 @@ The backward launchers follow at the end: route_infonce / route_gemm_tn (csrc/lo
 tests/test_gpu_bwd_routes.py and the four tests/test_gpu_*_grads.py files, their universes LN_BWD_KERNELS, BIAS_RELU_KERNELS,
 GATHER_BWD_KERNELS, NBR_TRANSPOSE_KERNELS, GEMM_TN_KERNELS (+ TN_ANY_EDGES) and INFONCE_KERNELS.
 
+The preprocessing section (csrc/preprocess.hip) closes the file: live_table / table_capacity, the two workspace carvers, route_scan,
+route_subsample, route_cellgrid, radius_cap, route_radius_query, route_radius_self, and the regimes of one query row (rank_path, shrinks
+-- which needs K beside the capacity --, staged, row_labels); cases in tests/test_gpu_preprocess_routes.py, universe PREPROCESS_KERNELS =
+PREPROCESS_SHAPE_KERNELS (from launch sizes) | PREPROCESS_ROW_KERNELS (from a reference's counts).
+
 A route is '+'-joined kernel names: the product kernel, then for split-K its reduction ('reduce', 'reduce_stats/vec' or
 'reduce_stats/novec'), then 'stats_pass' when ops.gemm hands C to regtr_instnorm_stats for the statistics instead (split-K with N / 4 not a power of
 two <= 256, where that pass refuses the width as well: tests/test_gpu_dispatch.py asserts the error)."""
@@ -515,3 +520,172 @@ GEMM_TN_KERNELS = ({f'tn/{r}{f}' for r in ('one_split', 'chunk64', 'chunk_scaled
                    | {f'tn_any/{r}' for r in ('one_split', 'chunk64', 'chunk_scaled')})
 TN_ANY_EDGES = {'tn_any', 'tn_any/edge_n1', 'tn_any/edge_n2', 'tn_any/edge_n1/edge_n2'}
 INFONCE_KERNELS = set().union(*(set(route_infonce(D).split('+')) for D in range(64, 513, 64)))
+
+
+# ------------------------------------------------------------------------------------------------ preprocessing (csrc/preprocess.hip)
+# The grid subsample, the cell grid and both radius-search kernels.  Their regimes are chosen by launch sizes (capacities, known to the
+# host) and by live sizes and ball contents (known to the device only): the shape routes take both, the row regimes take numbers a
+# reference supplies.  Cases in tests/test_gpu_preprocess_routes.py, universe PREPROCESS_KERNELS.
+PRE_SCAN_TILE = 1024                  # SCAN_THREADS * SCAN_ITEMS
+SCAN_CHAIN_TILES = 64
+QUERY_WAVES = 4
+SELF_CAND = 256
+RQ_MAX_GRID = 256 * 64
+SELF_MAX_GRID = 256 * 32
+RADIUS_MAX_K = 448
+
+
+def live_table(n):
+    """rg_live_table: the power of two >= 1.5 n, at least 64 -- the hash-table length the kernels size on the device."""
+    want = max(n + (n >> 1), 64)
+    return 1 << (want - 1).bit_length()
+
+
+def table_capacity(n_cap):
+    """rg_table_capacity: the host twin over the capacity (the allocated table)."""
+    return live_table(n_cap)
+
+
+def _carve(sizes):
+    """RgCarver: every array starts on a 256-byte boundary; the total is rounded up to 256 bytes."""
+    off = 0
+    for b in sizes:
+        off = (off + 255) & ~255
+        off += b
+    return (off + 255) & ~255
+
+
+def cellgrid_ws_bytes(ns_cap):                                          # regtr_cellgrid_ws_bytes (carve_grid + 4096)
+    n = max(ns_cap, 1)
+    T = table_capacity(n)
+    return _carve([8 * n, 4 * n, 4 * n, 4 * T, 4 * T, 4 * T, 8 * T, 4 * T, 8 * T, 8 * T, 8 * (cdiv(T, PRE_SCAN_TILE) + 2), 16 * n,
+                   32 * T]) + 4096
+
+
+def umap_before_offset(base, c):                                        # rg_umap_before_offset
+    return base * 11 // 5 + 16 * c
+
+
+def grid_subsample_ws_bytes(n_cap, n_clouds, row_order):                # regtr_grid_subsample_ordered_ws_bytes (carve_subsample + 4096)
+    n, nc = max(n_cap, 1), max(n_clouds, 1)
+    T = table_capacity(n)
+    sizes = [8 * n, 8 * n, 8 * n, 4 * n, 4 * n, 4 * n, 4 * T, 4 * T, 4 * T, 4 * T, 8 * (cdiv(n, PRE_SCAN_TILE) + 1), 4 * 6 * nc]
+    if row_order == 1:
+        sizes += [8 * n, 4 * (n + nc), 4 * (umap_before_offset(n, nc) + 16), 4 * n, 4 * n]
+    return _carve(sizes) + 4096
+
+
+def route_scan(items_cap):
+    """scan_u64 over a capacity of items: the one-launch chained scan up to 64 tiles of 1024 ('scan/chained1': one tile, no look-back),
+    else reduce / block sums / apply, k_scan_bsums taking one sum per thread ('per1', up to 256 tiles) or looping with a carry."""
+    nb = cdiv(items_cap, PRE_SCAN_TILE)
+    if nb <= SCAN_CHAIN_TILES:
+        return 'scan/chained1' if nb <= 1 else 'scan/chained'
+    return 'scan/three/per1' if nb <= 256 else 'scan/three/perN'
+
+
+def route_subsample(n_cap, row_order=0):
+    """regtr_grid_subsample_ordered: its scan runs over the point capacity; row_order 1 adds k_rank_keys + k_umap_order."""
+    assert n_cap >= 1 and row_order in (0, 1)
+    return 'sub/' + route_scan(n_cap) + ('+sub/ref_order' if row_order else '')
+
+
+def route_cellgrid(ns_cap):
+    """regtr_cellgrid_build: its scan runs over the allocated table (the live length stays on the device)."""
+    return 'grid/' + route_scan(table_capacity(max(ns_cap, 1)))
+
+
+def radius_cap(K):
+    """The LDS list capacity of both radius kernels: 2 K rounded up to 64, held in [256, 512]; K + 64 must fit (K <= 448)."""
+    if K < 1 or K > RADIUS_MAX_K:
+        return 'refused'
+    cap = min(max((2 * K + 63) // 64 * 64, 256), 512)
+    assert cap >= K + 64
+    return cap
+
+
+def xcd_grid(nblocks):
+    return (nblocks + 7) // 8 * 8
+
+
+def route_radius_query(nq_cap, nq_live):
+    """regtr_radius_query -> (label, trailing waves empty): min(xcd_grid(cdiv(nq_cap, 4)), 16384) workgroups of 4 waves, every wave a
+    contiguous run of cdiv(nq_live, waves) queries.  Trailing waves are empty when the runs of the first waves cover the live queries."""
+    assert nq_cap >= 1 and 0 <= nq_live <= nq_cap
+    waves = min(xcd_grid(cdiv(nq_cap, QUERY_WAVES)), RQ_MAX_GRID) * QUERY_WAVES
+    per_wave = cdiv(nq_live, waves)
+    label = 'rq/per_wave1' if per_wave <= 1 else 'rq/per_waveN'
+    return label, per_wave * (waves - 1) >= nq_live
+
+
+def self_plan(ns_cap, ns_live):
+    """k_radius_query_self -> (slots per wave and step, steps): the launch has waves for 16 slots each of the allocated table (at most
+    8192 workgroups); the kernel sizes the chunk for the live table, 4 .. 64, and loops when 64 slots per wave do not cover it."""
+    assert ns_cap >= 1 and 0 <= ns_live <= ns_cap
+    chunks = cdiv(table_capacity(ns_cap), 16)
+    waves = min(cdiv(chunks, QUERY_WAVES), SELF_MAX_GRID) * QUERY_WAVES
+    T = live_table(ns_live)
+    spw = 4
+    while spw < 64 and spw * waves < T:
+        spw <<= 1
+    return spw, cdiv(T, spw * waves)
+
+
+def route_radius_self(ns_cap, ns_live):
+    spw, steps = self_plan(ns_cap, ns_live)
+    return f"self/spw{spw}/pass{'1' if steps <= 1 else 'N'}"
+
+
+# ---- the regimes of one query row, from numbers a reference supplies
+def rank_path(n_listed):
+    """for_each_ranked over the n keys left in the list -> (label, n % 8 == 0): two lanes per key up to 32 keys, else the general
+    path over the list padded to a multiple of 8."""
+    return ('rank/two_lane' if n_listed <= 32 else 'rank/general'), n_listed % 8 == 0
+
+
+def shrinks(count_sequence, cap, K):
+    """How often a row's list is cut back to the K best: count_sequence[i] supports of candidate round i (64 candidates) lie in the
+    ball; after a round the list shrinks when it has no room for 64 more."""
+    n = times = 0
+    for add in count_sequence:
+        n += add
+        if n + 64 > cap:
+            n = min(n, K)
+            times += 1
+    return times, n
+
+
+def cell_index(x, radius):
+    """cell_of, per axis: floor(double(x) * inv), inv = 1 / (double(float32 radius) * (1 + 1e-6)); a support's cell key is
+    (cloud, cx, cy, cz).  Takes a scalar or a numpy array.  The tests use it to LABEL cases only, never for a result."""
+    import numpy as np
+    inv = 1.0 / (float(np.float32(radius)) * (1.0 + 1e-6))
+    return np.floor(np.asarray(x, np.float64) * inv).astype(np.int64)
+
+
+def staged(total_candidates):
+    """k_radius_query_self stages the 27-cell candidates of a cell in LDS when there are at most 256 of them."""
+    return 'cand/staged' if total_candidates <= SELF_CAND else 'cand/unstaged'
+
+
+def row_labels(n_candidates, count_sequence, K):
+    """Every data-dependent label of one row: staged or not (self kernel), shrink count with the capacity class, final rank path."""
+    cap = radius_cap(K)
+    times, n = shrinks(count_sequence, cap, K)
+    path, mult8 = rank_path(n)
+    out = {path + ('' if path == 'rank/two_lane' else ('/pad0' if mult8 else '/pad')), staged(n_candidates)}
+    if times:
+        capc = 'cap_limit' if cap == K + 64 else ('cap256' if cap == 256 else ('cap512' if cap == 512 else 'cap_mid'))
+        out.add(f"shrink{min(times, 2)}/{capc}")
+        if n_candidates > SELF_CAND:
+            out.add('cand/unstaged/shrink')
+    return out
+
+
+_SCANS = ('scan/chained1', 'scan/chained', 'scan/three/per1', 'scan/three/perN')
+PREPROCESS_SHAPE_KERNELS = ({f'sub/{s}' for s in _SCANS} | {f'grid/{s}' for s in _SCANS} | {'sub/ref_order'}
+                            | {'rq/per_wave1', 'rq/per_waveN', 'rq/empty_waves'}
+                            | {f'self/spw{s}/pass1' for s in (4, 8, 16, 32, 64)} | {'self/spw64/passN'})
+PREPROCESS_ROW_KERNELS = ({'rank/two_lane', 'rank/general/pad0', 'rank/general/pad', 'cand/staged', 'cand/unstaged', 'cand/unstaged/shrink'}
+                          | {f'shrink{t}/{c}' for t in (1, 2) for c in ('cap256', 'cap_mid', 'cap512', 'cap_limit')})
+PREPROCESS_KERNELS = PREPROCESS_SHAPE_KERNELS | PREPROCESS_ROW_KERNELS

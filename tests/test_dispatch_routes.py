@@ -461,3 +461,166 @@ def test_every_gemm_tn_bwd_instantiation_is_reached():
     assert scaled >= 5
     for kind in ('tn', 'tn_fold', 'tn_any'):
         assert {0, 1, 3, 4} <= {M for k, M, _, _, _ in _params(_bwd().test_gemm_tn_vs_float64, 'kind M N1 N2 route'.split()) if k == kind}
+
+
+# ------------------------------------------------------------------------------------------------ preprocessing (csrc/preprocess.hip)
+def _pre():
+    from tests import test_gpu_preprocess_routes
+    return test_gpu_preprocess_routes
+
+
+def _around(xs, hi=3000000):
+    return sorted({min(max(x + d, 1), hi) for x in xs for d in (-1, 0, 1)})
+
+
+# capacities around every boundary: 1, 42, 43 and 64 tiles of the table and of the points, 256 tiles, the self kernel's chunk sizes
+PRE_CAPS = _around([1, 42, 43, 64, 682, 683, 1024, 28672, 29355, 43008, 43690, 43691, 44032, 65536, 87381, 174762, 174763, 262144, 349525,
+                    349526, 524288, 699050, 699051, 1048576, 1398101, 1398102, 2097152, 2796202, 3000000]) + [0, -5]
+
+
+def test_preprocess_workspace_mirror_matches_library():
+    """cellgrid_ws_bytes / grid_subsample_ws_bytes (carve_grid, carve_subsample, the 256-byte carver, + 4096) against the library's
+    queries: SCAN_TILE, the 1.5 x table rule and the tile counts are what the scan routes are derived from."""
+    from regtr_amd import _lib
+    L = _lib.lib()
+    for cap in PRE_CAPS:
+        for nc in (1, 2, 130):
+            assert L.regtr_cellgrid_ws_bytes(cap, nc) == dispatch.cellgrid_ws_bytes(cap), (cap, nc)
+            for ro in (0, 1):
+                assert L.regtr_grid_subsample_ordered_ws_bytes(cap, nc, ro) == dispatch.grid_subsample_ws_bytes(cap, nc, ro), (cap, nc, ro)
+            assert L.regtr_grid_subsample_ws_bytes(cap, nc) == dispatch.grid_subsample_ws_bytes(cap, nc, 0)
+    assert len(PRE_CAPS) > 70
+    assert [dispatch.live_table(n) for n in (0, 43, 44, 683, 684, 43690, 43691, 43692)] == [64, 64, 128, 1024, 2048, 65536, 65536, 131072]
+    assert [dispatch.route_scan(n) for n in (1, 1024, 1025, 65536, 65537, 262144, 262145)] == [
+        'scan/chained1', 'scan/chained1', 'scan/chained', 'scan/chained', 'scan/three/per1', 'scan/three/per1', 'scan/three/perN']
+    assert [dispatch.route_cellgrid(n) for n in (683, 684, 43691, 43692, 174763, 174764)] == [
+        'grid/scan/chained1', 'grid/scan/chained', 'grid/scan/chained', 'grid/scan/three/per1', 'grid/scan/three/per1', 'grid/scan/three/perN']
+    # the self kernel's chunk: 16 slots per wave at capacity = live until the launch is capped at 8192 workgroups, then 32, 64, two steps
+    assert [dispatch.route_radius_self(n, n) for n in (262144, 349525, 349526, 699051, 699052, 1398101, 1398102)] == [
+        'self/spw16/pass1', 'self/spw16/pass1', 'self/spw32/pass1', 'self/spw32/pass1', 'self/spw64/pass1', 'self/spw64/pass1',
+        'self/spw64/passN']
+    assert [dispatch.radius_cap(K) for K in (0, 1, 40, 128, 129, 160, 224, 225, 300, 448, 449)] == [
+        'refused', 256, 256, 256, 320, 320, 448, 512, 512, 512, 'refused']
+    assert dispatch.shrinks([64] * 8, 512, 448) == (1, 448) and dispatch.shrinks([64] * 9, 512, 448) == (2, 448)
+    assert dispatch.shrinks([64, 64, 64, 63], 256, 40) == (1, 40) and dispatch.shrinks([64, 64, 64], 256, 40) == (0, 192)
+    assert dispatch.route_radius_query(65536, 65536) == ('rq/per_wave1', False)
+    assert dispatch.route_radius_query(65537, 65537) == ('rq/per_waveN', True)
+
+
+def test_preprocess_refusals():
+    """Argument and workspace refusals of the radius queries and the ordered subsample; stand-in pointers, nothing is launched."""
+    from regtr_amd import _lib
+    L = _lib.lib()
+    FAKE = 0x10000
+    big = 1 << 30
+
+    def rq(K=16, order=0, ws_bytes=big):
+        return L.regtr_radius_query(FAKE, FAKE, 100, FAKE, 100, 2, 0.1, K, order, FAKE, ws_bytes, FAKE, None, None, None)
+
+    def rs(K=16, order=0, ws_bytes=big):
+        return L.regtr_radius_query_self(FAKE, 100, 2, 0.1, K, order, FAKE, ws_bytes, FAKE, None, None, None)
+
+    for f in (rq, rs):
+        assert f(K=0) == -2 and f(K=449) == -2 and f(order=2) == -2 and f(K=-3) == -2
+        assert f(ws_bytes=dispatch.cellgrid_ws_bytes(100) - 1) == -3 and f(ws_bytes=0) == -3
+
+    def sub(row_order=0, key_mode=0, out_cap=100, ws_bytes=big, n_cap=100):
+        return L.regtr_grid_subsample_ordered(FAKE, FAKE, 2, n_cap, 0.05, row_order, key_mode, out_cap, FAKE, FAKE, FAKE, ws_bytes, None)
+
+    assert sub(row_order=1, out_cap=99) == -2                       # the container order is replayed over whole clouds
+    assert sub(row_order=1, key_mode=1) == -2 and sub(row_order=1, key_mode=2) == -2
+    assert sub(row_order=2) == -2 and sub(key_mode=3) == -2
+    for ro in (0, 1):
+        assert sub(row_order=ro, ws_bytes=dispatch.grid_subsample_ws_bytes(100, 2, ro) - 1) == -3
+
+
+def test_binned_reference_equals_the_oracle():
+    """tests/preprocess_ref.py: the linear-time restatement equals the brute-force oracle element for element on every small case of the
+    GPU file -- the row-regime case (duplicates, lattice ties, an empty cloud, empty rows) at every K and both orders, with bins of the
+    default side and of a coarser one, the many-cloud cases, and uniform clouds."""
+    import numpy as np
+    from tests import preprocess_ref as PR
+    c = PR.row_case()
+    assert 0 in c['s_lens']
+    for order in (0, 1):
+        for q, ql in ((c['q'], c['q_lens']), (c['s'], c['s_lens'])):
+            full = PR.oracle_radius(q, c['s'], ql, c['s_lens'], c['r'], max(PR.ROW_KS), order)      # a row at K is a prefix of the row at 448
+            assert full[1].max() > max(PR.ROW_KS)
+            for K in PR.ROW_KS:
+                for side in ((None, 0.17) if K in (16, 448) else (None,)):
+                    got = PR.binned_radius(q, c['s'], ql, c['s_lens'], c['r'], K, order, cell=side)
+                    assert np.array_equal(got[0], full[0][:, :K]) and np.array_equal(got[1], full[1]), (K, order, side)
+    for n_clouds in (130, 260):
+        pts, lens, r, _ = PR.many_clouds(n_clouds)
+        for order in (0, 1):
+            ref = PR.oracle_radius(pts, pts, lens, lens, r, 16, order)
+            got = PR.binned_radius(pts, pts, lens, lens, r, 16, order)
+            assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1]), (n_clouds, order)
+    pts, lens, r = PR.uniform_clouds(8000, 44)
+    rows = np.arange(5, 8000, 3)
+    ql = np.array([(rows < lens[0]).sum(), (rows >= lens[0]).sum()], np.int32)
+    ref = PR.oracle_radius(pts[rows], pts, ql, lens, r, 16)
+    got = PR.binned_radius(pts, pts, lens, lens, r, 16, q_rows=rows)
+    assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1])
+
+
+def _preprocess_labels():
+    """Every label the parametrized cases of tests/test_gpu_preprocess_routes.py reach: the shape labels from the parameters, the row
+    labels from the case generator's reference counts."""
+    from tests import preprocess_ref as PR
+    g = _pre()
+    labels = set()
+    for n_cap, n_live, route in _params(g.test_subsample_scan_forms, ['n_cap', 'n_live', 'route']):
+        assert dispatch.route_subsample(n_cap) == route and n_live <= n_cap
+        labels.add(route)
+    for ns, route in _params(g.test_cellgrid_scan_forms, ['ns', 'route']):
+        assert dispatch.route_cellgrid(ns) == route
+        labels.add(route)
+        labels.add(dispatch.route_radius_query(ns, ns)[0])                        # the general kernel over every support
+    for ns_cap, ns, route in _params(g.test_self_query_chunking, ['ns_cap', 'ns', 'route']):
+        assert dispatch.route_radius_self(ns_cap, ns) == route
+        labels.add(route)
+    for nq_cap, nq, route, empty in _params(g.test_radius_query_wave_runs, ['nq_cap', 'nq', 'route', 'empty']):
+        assert dispatch.route_radius_query(nq_cap, nq) == (route, empty)
+        labels.add(route)
+        if empty and nq_cap >= 16 * nq:
+            labels.add('rq/empty_waves')
+    for (n_clouds,) in _params(g.test_many_clouds, ['n_clouds']):
+        n = len(PR.many_clouds(n_clouds)[0])
+        labels |= set(dispatch.route_subsample(n, 1).split('+')) | {dispatch.route_cellgrid(n)}
+    rows = _params(g.test_row_regimes, ['kernel', 'K', 'order'])
+    assert {(k, o) for k, _, o in rows} == {(k, o) for k in ('rq', 'self') for o in (0, 1)}
+    for kernel, K, _ in rows:
+        labels |= PR.row_case_labels(K, kernel)[0]
+    return labels
+
+
+def test_every_preprocess_regime_is_reached():
+    labels = _preprocess_labels()
+    assert labels <= dispatch.PREPROCESS_KERNELS, sorted(labels - dispatch.PREPROCESS_KERNELS)
+    assert not dispatch.PREPROCESS_KERNELS - labels, f'regimes no GPU case reaches: {sorted(dispatch.PREPROCESS_KERNELS - labels)}'
+
+
+def test_preprocess_edges_are_reached():
+    """Around the labels: both sides of every scan boundary, live counts far below the capacity in the chained and in the three-launch
+    scan, the self kernel's last two regimes at their first size, the limit K = 448, every listed length the row case must produce."""
+    from tests import preprocess_ref as PR
+    g = _pre()
+    sub = _params(g.test_subsample_scan_forms, ['n_cap', 'n_live', 'route'])
+    assert {65536, 65537, 262144, 262145} <= {c for c, _, _ in sub}
+    assert {dispatch.route_scan(c) for c, n, _ in sub if n * 8 <= c} >= {'scan/chained', 'scan/three/per1'}
+    assert {43690, 43692, 174762, 174764} <= {n for n, _ in _params(g.test_cellgrid_scan_forms, ['ns', 'route'])}
+    self_cases = _params(g.test_self_query_chunking, ['ns_cap', 'ns', 'route'])
+    assert {(c // n) for c, n, r in self_cases if r in ('self/spw4/pass1', 'self/spw8/pass1')} == {4, 2}
+    assert {(349526, 349526), (699052, 699052), (1398102, 1398102)} <= {(c, n) for c, n, _ in self_cases}
+    # labels that other tests reach as well keep their dedicated cases: the last chained subsample, the query runs beyond one per wave
+    assert (65536, 65536, 'sub/scan/chained') in sub
+    rq = _params(g.test_radius_query_wave_runs, ['nq_cap', 'nq', 'route', 'empty'])
+    assert {(c, e) for c, n, r, e in rq if r == 'rq/per_waveN' and c == n} == {(70001, True), (131072, False)}
+    assert any(c >= 16 * n for c, n, _, _ in rq)
+    assert {K for _, K, _ in _params(g.test_row_regimes, ['kernel', 'K', 'order'])} >= {40, 300, 448}
+    assert dispatch.radius_cap(448) == 448 + 64
+    for kernel in ('rq', 'self'):
+        listed = PR.row_case_labels(16, kernel)[1]
+        assert {1, 31, 32, 33, 40, 64, 65, 72} <= listed and (kernel == 'self' or 0 in listed)
+    assert {n for (n,) in _params(g.test_many_clouds, ['n_clouds'])} == {130, 260}
