@@ -138,3 +138,29 @@ __device__ __forceinline__ float rg_wave_max(float v)
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, RG_WAVE));
     return v;
 }
+
+// Exclusive scan over the THREADS values of the calling workgroup (every thread calls it; any integer type); *total = their sum.
+// sh: THREADS / RG_WAVE values of LDS, free for reuse when the call returns.
+template <int THREADS, typename T>
+__device__ __forceinline__ T rg_block_exclusive_scan(T v, T* total, T* sh)
+{
+    const int lane = rg_lane(), wave = threadIdx.x >> 6;
+    T inc = v;      // wave inclusive scan
+#pragma unroll
+    for (int o = 1; o < RG_WAVE; o <<= 1) {
+        const T t = __shfl_up(inc, o, RG_WAVE);
+        if (lane >= o) inc += t;
+    }
+    if (lane == RG_WAVE - 1) sh[wave] = inc;
+    __syncthreads();
+    T wave_off = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < THREADS / RG_WAVE; w++) {
+        const T s = sh[w];
+        if (w < wave) wave_off += s;
+        tot += s;
+    }
+    __syncthreads();
+    *total = tot;
+    return wave_off + inc - v;
+}

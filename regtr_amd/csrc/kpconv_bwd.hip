@@ -39,28 +39,6 @@ __global__ void __launch_bounds__(256) k_nbrt_count(const int* __restrict__ nbr,
     if ((unsigned)idx < (unsigned)ns) atomicAdd(&cnt[idx], 1);
 }
 
-// exclusive scan of the calling workgroup's 256 values; *total = their sum
-__device__ __forceinline__ int block_exclusive_scan(int v, int* sh /*[4]*/, int* total)
-{
-    const int lane = rg_lane(), wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < RG_WAVE; o <<= 1) {
-        const int t = __shfl_up(inc, o, RG_WAVE);
-        if (lane >= o) inc += t;
-    }
-    if (lane == RG_WAVE - 1) sh[wave] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int w = 0; w < 4; w++) {
-        if (w < wave) base += sh[w];
-        tot += sh[w];
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
-
 __global__ void __launch_bounds__(256) k_scan_sums(const int* __restrict__ cnt, int n, int* __restrict__ bsum)
 {
     __shared__ int sh[4];
@@ -68,7 +46,7 @@ __global__ void __launch_bounds__(256) k_scan_sums(const int* __restrict__ cnt, 
     int s = 0;
     for (int u = 0; u < 4; u++) s += i0 + u < n ? cnt[i0 + u] : 0;
     int tot;
-    block_exclusive_scan(s, sh, &tot);
+    rg_block_exclusive_scan<256>(s, &tot, sh);
     if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
 }
 
@@ -80,7 +58,7 @@ __global__ void __launch_bounds__(256) k_scan_bsums(int* __restrict__ bsum, int 
     int s = 0;
     for (int b = b0; b < b1; b++) s += bsum[b];
     int tot;
-    int run = block_exclusive_scan(s, sh, &tot);
+    int run = rg_block_exclusive_scan<256>(s, &tot, sh);
     for (int b = b0; b < b1; b++) {
         const int v = bsum[b];
         bsum[b] = run;
@@ -99,7 +77,7 @@ __global__ void __launch_bounds__(256) k_scan_apply(int* __restrict__ cnt, int n
         s += v[u];
     }
     int tot;
-    int run = block_exclusive_scan(s, sh, &tot) + bsum[blockIdx.x];
+    int run = rg_block_exclusive_scan<256>(s, &tot, sh) + bsum[blockIdx.x];
     for (int u = 0; u < 4; u++) {
         if (i0 + u < n) {
             cnt[i0 + u] = run;

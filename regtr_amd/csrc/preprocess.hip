@@ -31,30 +31,6 @@ constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_ITEMS = 4;
 constexpr int SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;
 
-__device__ __forceinline__ uint64_t block_exclusive_scan(uint64_t v, uint64_t* total, uint64_t* sh /*[SCAN_THREADS/64 + 1]*/)
-{
-    // wave inclusive scan
-    const int lane = rg_lane(), wave = threadIdx.x >> 6;
-    uint64_t inc = v;
-#pragma unroll
-    for (int o = 1; o < RG_WAVE; o <<= 1) {
-        uint64_t t = __shfl_up(inc, o, RG_WAVE);
-        if (lane >= o) inc += t;
-    }
-    if (lane == RG_WAVE - 1) sh[wave] = inc;
-    __syncthreads();
-    uint64_t wave_off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < SCAN_THREADS / RG_WAVE; w++) {
-        uint64_t s = sh[w];
-        if (w < wave) wave_off += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return wave_off + inc - v;
-}
-
 __global__ void __launch_bounds__(SCAN_THREADS) k_scan_reduce(const uint64_t* __restrict__ in, const int* __restrict__ n_ptr,
                                                              uint64_t* __restrict__ bsum)
 {
@@ -66,7 +42,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_scan_reduce(const uint64_t* __
     for (int k = 0; k < SCAN_ITEMS; k++)
         if (base + k < n) s += in[base + k];
     uint64_t tot;
-    block_exclusive_scan(s, &tot, sh);
+    rg_block_exclusive_scan<SCAN_THREADS>(s, &tot, sh);
     if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
 }
 
@@ -78,7 +54,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_scan_bsums(uint64_t* __restric
     for (int base = 0; base < nblocks; base += SCAN_THREADS) {
         const int i = base + threadIdx.x;
         uint64_t v = i < nblocks ? bsum[i] : 0, tot;
-        uint64_t ex = block_exclusive_scan(v, &tot, sh);
+        uint64_t ex = rg_block_exclusive_scan<SCAN_THREADS>(v, &tot, sh);
         if (i < nblocks) bsum[i] = carry + ex;
         carry += tot;
     }
@@ -97,7 +73,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_scan_apply(const uint64_t* __r
         s += v[k];
     }
     uint64_t tot;
-    uint64_t ex = block_exclusive_scan(s, &tot, sh) + bsum[blockIdx.x];
+    uint64_t ex = rg_block_exclusive_scan<SCAN_THREADS>(s, &tot, sh) + bsum[blockIdx.x];
 #pragma unroll
     for (int k = 0; k < SCAN_ITEMS; k++) {
         if (base + k < n) out[base + k] = ex;
@@ -132,7 +108,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_scan_chained(const uint64_t* _
         s += v[k];
     }
     uint64_t tot;
-    uint64_t ex = block_exclusive_scan(s, &tot, sh);
+    uint64_t ex = rg_block_exclusive_scan<SCAN_THREADS>(s, &tot, sh);
     if (threadIdx.x < RG_WAVE) {                                      // wave 0: publish, look back
         const int lane = threadIdx.x;
         uint64_t* desc = state + 1;
@@ -638,42 +614,20 @@ __device__ __forceinline__ void for_each_ranked(uint64_t* list, int n, F&& f)
 }
 #undef RG_LT
 
-__global__ void __launch_bounds__(QUERY_WAVES * RG_WAVE)
-k_radius_query(const float* __restrict__ q_xyz, const int* __restrict__ q_seg_off, const int* __restrict__ s_seg_off,
-               int n_clouds, GridView g, float radius, int K, int cap, int by_index, int* __restrict__ out_idx,
-               int* __restrict__ out_count, int* __restrict__ out_max_count)
+// ---- the per-query body, shared by k_radius_query and k_radius_query_self: one definition each of the run table, the run lookup, the
+// ball test, the candidate sweep (with its shrink) and the row write-out, so the two kernels' tables are bit-identical by construction ----
+
+// Run table of a neighbourhood: lane l < 27 holds the (my_cnt, my_start) run of cell l in the cell-sorted supports.  Writes runs[0..26]
+// (exclusive prefix of the run lengths) and runs[32..58] (run start minus that prefix) and returns the wave-uniform candidate total:
+// run r covers candidates [runs[r], runs[r + 1]) and candidate t of it is support row t + runs[32 + r].
+// (DPP row shifts: Hillis-Steele inside each 16-lane row, then row 0's total is added to row 1 -- the 27 runs live in
+//  lanes 0..26; five dependent ds_bpermute shuffles would cost five LDS-crossbar round trips)
+// (Measured and dropped: the table in 54 SGPRs with 26 compare/selects per lane instead of the 5-step LDS binary
+//  search: 17 % slower; two queries per wave, one per 32-lane half, with per-half DPP scans / ballots: 17 % slower too,
+//  bit-identical tables in both cases.)
+__device__ __forceinline__ int build_run_table(int my_cnt, int my_start, int* runs)
 {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int wave = threadIdx.x >> 6, lane = rg_lane();
-    // per-wave LDS: list[cap] u64, then 27 run offsets + 27 run deltas (64 ints)
-    uint64_t* list = (uint64_t*)smem + (size_t)wave * (cap + 32);
-
-    const int nq = q_seg_off[n_clouds];
-    const int ns = s_seg_off[n_clouds];
-    const unsigned mask = rg_live_table(ns) - 1u;      // the table was built for ns supports
-    // Grid-stride over the LIVE queries: the launch is sized for the level-0 capacity (live counts exist only on the
-    // device), and a level with 1/64 of the rows must not pay for 63/64 empty workgroups.
-    // (every wave takes a CONTIGUOUS run of queries, and every XCD -- own L2 -- a contiguous eighth of them: neighbouring queries
-    //  read the same cell runs)
-    const int per_wave = (nq + gridDim.x * QUERY_WAVES - 1) / (gridDim.x * QUERY_WAVES);
-    const int q_first = (rg_xcd_block(blockIdx.x, gridDim.x) * QUERY_WAVES + wave) * per_wave;
-    const int q_last = min(nq, q_first + per_wave);
-    for (int q = q_first; q < q_last; q++) {   // wave-uniform
-    const int cid = rg_find_segment_wave(q_seg_off, n_clouds, q);    // q is wave-uniform: one round trip, not log2(n) dependent loads
-    const float qx = q_xyz[3 * (size_t)q], qy = q_xyz[3 * (size_t)q + 1], qz = q_xyz[3 * (size_t)q + 2];
-    const float r2 = __fmul_rn(radius, radius);  // neighbors.cpp:226
-
-    // 27 candidate cells, one per lane
-    int64_t cx, cy, cz;
-    cell_of(qx, qy, qz, g.inv_cs, cx, cy, cz);
-    int my_cnt = 0, my_start = 0;
-    if (lane < 27) {
-        const int dx = lane % 3 - 1, dy = (lane / 3) % 3 - 1, dz = lane / 9 - 1;
-        slot_find(g.slots, mask, cell_key(cx + dx, cy + dy, cz + dz), cid, my_cnt, my_start);
-    }
-    // exclusive prefix of the run lengths over lanes
-    // (DPP row shifts: Hillis-Steele inside each 16-lane row, then row 0's total is added to row 1 -- the 27 runs live in
-    //  lanes 0..26; five dependent ds_bpermute shuffles would cost five LDS-crossbar round trips)
+    const int lane = rg_lane();
     int inc = my_cnt;
     inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xf, 0xf, true);     // row_shr:1, out-of-row reads 0
     inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xf, 0xf, true);     // row_shr:2
@@ -681,32 +635,49 @@ k_radius_query(const float* __restrict__ q_xyz, const int* __restrict__ q_seg_of
     inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xf, 0xf, true);     // row_shr:8
     inc += (lane >= 16 && lane < 32) ? __builtin_amdgcn_readlane(inc, 15) : 0;
     const int total = __builtin_amdgcn_readlane(inc, 26);
-    // run table in LDS: run r covers candidates [runs[r], runs[r + 1]) and candidate t of it is support row t + runs[32 + r].
-    // (Measured and dropped: the table in 54 SGPRs with 26 compare/selects per lane instead of the 5-step LDS binary
-    //  search: 17 % slower; two queries per wave, one per 32-lane half, with per-half DPP scans / ballots: 17 % slower too,
-    //  bit-identical tables in both cases.)
-    int* runs = (int*)(list + cap);
     if (lane < 27) { runs[lane] = inc - my_cnt; runs[32 + lane] = my_start - (inc - my_cnt); }
     __builtin_amdgcn_wave_barrier();
+    return total;
+}
 
-    int n = 0;          // entries currently in the list
-    int n_total = 0;    // all supports inside the ball (untruncated count)
+// record (x, y, z, index-as-bits) of candidate t < total: the last run with offset <= t, then its support row
+__device__ __forceinline__ float4 run_candidate(const GridView& g, const int* runs, int t)
+{
+    int c = 0;
+#pragma unroll
+    for (int step = 16; step > 0; step >>= 1) { const int c2 = c + step; if (c2 < 27 && runs[c2] <= t) c = c2; }
+    return g.sorted[t + runs[32 + c]];
+}
+
+// is support sp inside the ball of the query, and its list key: (d2 bits << 32 | index), order 1 (by_index): the support index alone
+__device__ __forceinline__ bool ball_test(float qx, float qy, float qz, const float4& sp, float r2, int by_index, uint64_t& key)
+{
+    const float dx = __fsub_rn(qx, sp.x), dy = __fsub_rn(qy, sp.y), dz = __fsub_rn(qz, sp.z);
+    // nanoflann.hpp:432-440 : ((0 + dx*dx) + dy*dy) + dz*dz, strict '<' (nanoflann.hpp:249-251)
+    const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+    key = (by_index ? 0ULL : ((uint64_t)__float_as_uint(d2) << 32)) | (uint32_t)__float_as_int(sp.w);
+    return d2 < r2;
+}
+
+struct BallCount {
+    int n;          // entries in the list (at most K once a shrink has run)
+    int n_total;    // all supports inside the ball (untruncated count)
+};
+
+// Tests the `total` candidates of a neighbourhood 64 at a time (fetch(t) = the record of candidate t) and compacts the keys of those
+// inside the ball into the LDS list (cap entries; cap >= K + 64).  A round that would not leave room for the next one keeps only the K
+// best so far.
+template <typename Fetch>
+__device__ __forceinline__ BallCount sweep_candidates(float qx, float qy, float qz, float r2, int total, int K, int cap, int by_index,
+                                                      uint64_t* list, Fetch&& fetch)
+{
+    const int lane = rg_lane();
+    int n = 0, n_total = 0;
     for (int t0 = 0; t0 < total; t0 += RG_WAVE) {
         const int t = t0 + lane;
         bool in = false;
         uint64_t key = 0;
-        if (t < total) {
-            int c = 0;  // last run with offset <= t
-#pragma unroll
-            for (int step = 16; step > 0; step >>= 1) { const int c2 = c + step; if (c2 < 27 && runs[c2] <= t) c = c2; }
-            const int d = runs[32 + c];
-            const float4 sp = g.sorted[t + d];
-            const float dx = __fsub_rn(qx, sp.x), dy = __fsub_rn(qy, sp.y), dz = __fsub_rn(qz, sp.z);
-            // nanoflann.hpp:432-440 : ((0 + dx*dx) + dy*dy) + dz*dz, strict '<' (nanoflann.hpp:249-251)
-            float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-            in = d2 < r2;
-            key = (by_index ? 0ULL : ((uint64_t)__float_as_uint(d2) << 32)) | (uint32_t)__float_as_int(sp.w);   // order 1: by support index alone
-        }
+        if (t < total) in = ball_test(qx, qy, qz, fetch(t), r2, by_index, key);
         const unsigned long long bal = __ballot(in);
         if (in) list[n + __popcll(bal & ((1ULL << lane) - 1ULL))] = key;
         const int add = __popcll(bal);
@@ -734,14 +705,60 @@ k_radius_query(const float* __restrict__ q_xyz, const int* __restrict__ q_seg_of
             __builtin_amdgcn_wave_barrier();
         }
     }
+    return {n, n_total};
+}
+
+// row q of the table: the list's indices in ascending key order, padded with the shadow index ns (neighbors.cpp:323-324), and the count
+__device__ __forceinline__ void write_row(uint64_t* list, BallCount c, int q, int K, int ns, int* __restrict__ out_idx,
+                                          int* __restrict__ out_count)
+{
+    const int lane = rg_lane();
     int* row = out_idx + (size_t)q * K;
-    for_each_ranked(list, n, [&](int rank, uint64_t k) { if (rank < K) row[rank] = (int)(uint32_t)k; });
-    for (int k = n + lane; k < K; k += RG_WAVE) row[k] = ns;  // shadow index (neighbors.cpp:323-324)
-    if (lane == 0) {
-        if (out_count) out_count[q] = n_total;
-        if (out_max_count) atomicMax(out_max_count, n_total);
-    }
+    for_each_ranked(list, c.n, [&](int rank, uint64_t k) { if (rank < K) row[rank] = (int)(uint32_t)k; });
+    for (int k = c.n + lane; k < K; k += RG_WAVE) row[k] = ns;
+    if (lane == 0 && out_count) out_count[q] = c.n_total;
     __builtin_amdgcn_wave_barrier();      // the LDS list is reused by the wave's next query
+}
+
+__global__ void __launch_bounds__(QUERY_WAVES * RG_WAVE)
+k_radius_query(const float* __restrict__ q_xyz, const int* __restrict__ q_seg_off, const int* __restrict__ s_seg_off,
+               int n_clouds, GridView g, float radius, int K, int cap, int by_index, int* __restrict__ out_idx,
+               int* __restrict__ out_count, int* __restrict__ out_max_count)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int wave = threadIdx.x >> 6, lane = rg_lane();
+    // per-wave LDS: list[cap] u64, then 27 run offsets + 27 run deltas (64 ints)
+    uint64_t* list = (uint64_t*)smem + (size_t)wave * (cap + 32);
+    int* runs = (int*)(list + cap);
+
+    const int nq = q_seg_off[n_clouds];
+    const int ns = s_seg_off[n_clouds];
+    const unsigned mask = rg_live_table(ns) - 1u;      // the table was built for ns supports
+    // Grid-stride over the LIVE queries: the launch is sized for the level-0 capacity (live counts exist only on the
+    // device), and a level with 1/64 of the rows must not pay for 63/64 empty workgroups.
+    // (every wave takes a CONTIGUOUS run of queries, and every XCD -- own L2 -- a contiguous eighth of them: neighbouring queries
+    //  read the same cell runs)
+    const int per_wave = (nq + gridDim.x * QUERY_WAVES - 1) / (gridDim.x * QUERY_WAVES);
+    const int q_first = (rg_xcd_block(blockIdx.x, gridDim.x) * QUERY_WAVES + wave) * per_wave;
+    const int q_last = min(nq, q_first + per_wave);
+    for (int q = q_first; q < q_last; q++) {   // wave-uniform
+        const int cid = rg_find_segment_wave(q_seg_off, n_clouds, q);    // q is wave-uniform: one round trip, not log2(n) dependent loads
+        const float qx = q_xyz[3 * (size_t)q], qy = q_xyz[3 * (size_t)q + 1], qz = q_xyz[3 * (size_t)q + 2];
+        const float r2 = __fmul_rn(radius, radius);  // neighbors.cpp:226
+
+        // 27 candidate cells, one per lane
+        int64_t cx, cy, cz;
+        cell_of(qx, qy, qz, g.inv_cs, cx, cy, cz);
+        int my_cnt = 0, my_start = 0;
+        if (lane < 27) {
+            const int dx = lane % 3 - 1, dy = (lane / 3) % 3 - 1, dz = lane / 9 - 1;
+            slot_find(g.slots, mask, cell_key(cx + dx, cy + dy, cz + dz), cid, my_cnt, my_start);
+        }
+        const int total = build_run_table(my_cnt, my_start, runs);
+        const BallCount c = sweep_candidates(qx, qy, qz, r2, total, K, cap, by_index, list,
+                                             [&](int t) { return run_candidate(g, runs, t); });
+        write_row(list, c, q, K, ns, out_idx, out_count);
+        if (lane == 0 && out_max_count) atomicMax(out_max_count, c.n_total);
     }
 }
 
@@ -750,8 +767,8 @@ k_radius_query(const float* __restrict__ q_xyz, const int* __restrict__ q_seg_of
 // support runs ONCE into LDS (one more round trip), and then answers every query of the cell -- the cell's own points, which
 // are among the staged candidates -- from LDS: distance tests, ballot compaction and the rank sort never touch memory again.
 // The per-query kernel above pays those two dependent round trips per QUERY (its waves spend two thirds of their cycles in
-// s_waitcnt); a cell holds ~6 queries on 3DMatch-density surfaces.  Same float32 arithmetic, same (d2, index) keys, same
-// shrink rule: the tables are bit-identical to k_radius_query's.
+// s_waitcnt); a cell holds ~6 queries on 3DMatch-density surfaces.  The per-query body is the one above (same float32 arithmetic,
+// same (d2, index) keys, same shrink rule), so the tables are bit-identical to k_radius_query's.
 constexpr int SELF_CAND = 256;        // staged candidates per cell (cells whose 27-neighbourhood holds more read from global)
 
 __global__ void __launch_bounds__(QUERY_WAVES * RG_WAVE)
@@ -799,76 +816,21 @@ k_radius_query_self(const int* __restrict__ s_seg_off, int n_clouds, GridView g,
                 if (lane == 13) { my_cnt = c_cnt; my_start = c_start; }
                 else slot_find(g.slots, mask, cell_key(cx + dx, cy + dy, cz + dz), cid, my_cnt, my_start);
             }
-            int inc = my_cnt;
-            inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xf, 0xf, true);
-            inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xf, 0xf, true);
-            inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xf, 0xf, true);
-            inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xf, 0xf, true);
-            inc += (lane >= 16 && lane < 32) ? __builtin_amdgcn_readlane(inc, 15) : 0;
-            const int total = __builtin_amdgcn_readlane(inc, 26);
             __builtin_amdgcn_wave_barrier();                                  // previous cell's LDS reads are done
-            if (lane < 27) { runs[lane] = inc - my_cnt; runs[32 + lane] = my_start - (inc - my_cnt); }
-            __builtin_amdgcn_wave_barrier();
-            auto cand_global = [&](int t) -> float4 {
-                int c = 0;
-#pragma unroll
-                for (int step = 16; step > 0; step >>= 1) { const int c2 = c + step; if (c2 < 27 && runs[c2] <= t) c = c2; }
-                return g.sorted[t + runs[32 + c]];
-            };
+            const int total = build_run_table(my_cnt, my_start, runs);
             const bool staged = total <= SELF_CAND;                           // wave-uniform
             if (staged) {
-                for (int t = lane; t < total; t += RG_WAVE) cand[t] = cand_global(t);
+                for (int t = lane; t < total; t += RG_WAVE) cand[t] = run_candidate(g, runs, t);
                 __builtin_amdgcn_wave_barrier();
             }
             // ---- the cell's queries, one after another (wave-uniform loop)
             for (int qi = 0; qi < c_cnt; qi++) {
                 // the query is one of the staged candidates (the centre cell is run 13); LDS broadcast instead of a global load
                 const float4 qp = staged ? cand[runs[13] + qi] : g.sorted[c_start + qi];
-                const int q = __float_as_int(qp.w);
-                int n = 0, n_total = 0;
-                for (int t0 = 0; t0 < total; t0 += RG_WAVE) {
-                    const int t = t0 + lane;
-                    bool in = false;
-                    uint64_t key = 0;
-                    if (t < total) {
-                        const float4 sp = staged ? cand[t] : cand_global(t);
-                        const float dx = __fsub_rn(qp.x, sp.x), dy = __fsub_rn(qp.y, sp.y), dz = __fsub_rn(qp.z, sp.z);
-                        const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-                        in = d2 < r2;
-                        key = (by_index ? 0ULL : ((uint64_t)__float_as_uint(d2) << 32)) | (uint32_t)__float_as_int(sp.w);   // order 1: by support index alone
-                    }
-                    const unsigned long long bal = __ballot(in);
-                    if (in) list[n + __popcll(bal & ((1ULL << lane) - 1ULL))] = key;
-                    const int add = __popcll(bal);
-                    n += add;
-                    n_total += add;
-                    __builtin_amdgcn_wave_barrier();
-                    if (n + RG_WAVE > cap) {                                  // keep only the K best so far (as k_radius_query)
-                        uint64_t keep_key[8];
-                        int keep_rank[8];
-#pragma unroll
-                        for (int a = 0; a < 8; a++) {
-                            const int e = a * RG_WAVE + lane;
-                            keep_key[a] = e < n ? list[e] : ~0ULL;
-                            int rank = 0;
-                            if (a * RG_WAVE < n)
-                                for (int j = 0; j < n; j++) rank += list[j] < keep_key[a] ? 1 : 0;
-                            keep_rank[a] = e < n ? rank : INT_MAX;
-                        }
-                        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                        for (int a = 0; a < 8; a++)
-                            if (keep_rank[a] < K) list[keep_rank[a]] = keep_key[a];
-                        n = n < K ? n : K;
-                        __builtin_amdgcn_wave_barrier();
-                    }
-                }
-                int* row = out_idx + (size_t)q * K;
-                for_each_ranked(list, n, [&](int rank, uint64_t k) { if (rank < K) row[rank] = (int)(uint32_t)k; });
-                for (int k = n + lane; k < K; k += RG_WAVE) row[k] = ns;
-                if (lane == 0 && out_count) out_count[q] = n_total;
-                wave_max = n_total > wave_max ? n_total : wave_max;
-                __builtin_amdgcn_wave_barrier();                              // the list is reused by the next query
+                const BallCount c = sweep_candidates(qp.x, qp.y, qp.z, r2, total, K, cap, by_index, list,
+                                                     [&](int t) { return staged ? cand[t] : run_candidate(g, runs, t); });
+                write_row(list, c, __float_as_int(qp.w), K, ns, out_idx, out_count);
+                wave_max = c.n_total > wave_max ? c.n_total : wave_max;
             }
         }
     }
@@ -977,6 +939,21 @@ SubsampleBuffers carve_subsample(void* ws, size_t ws_bytes, int n_cap, int n_clo
     return b;
 }
 
+// 1 / cell size of the grid a radius is searched on: cells of radius * (1 + 1e-6), so a ball never reaches past its 27 cells
+inline double grid_inv_cell(float radius) { return 1.0 / ((double)radius * (1.0 + 1e-6)); }
+
+// what the query kernels read of a carved grid workspace built (regtr_cellgrid_build) with `radius`
+GridView grid_view(const GridBuffers& b, float radius) { return GridView{b.slots, b.sorted, grid_inv_cell(radius)}; }
+
+// LDS list capacity per query: room for the K survivors of a shrink plus one 64-candidate round; RG_ERR_ARG when K has no such capacity
+int query_list_cap(int K)
+{
+    int cap = (2 * K + 63) / 64 * 64;
+    if (cap < 256) cap = 256;
+    if (cap > 512) cap = 512;          // 8 register-staged chunks of 64 in the shrink path
+    return cap < K + RG_WAVE ? RG_ERR_ARG : cap;   // K <= 448
+}
+
 }  // namespace
 
 extern "C" {
@@ -1055,7 +1032,7 @@ int regtr_cellgrid_build(const float* s_xyz, const int* s_seg_off, int n_clouds,
     const int cap = ns_cap > 0 ? ns_cap : 1;
     GridBuffers b = carve_grid(ws, ws_bytes, cap);
     const int* n_ptr = s_seg_off + n_clouds;
-    const double inv_cs = 1.0 / ((double)radius * (1.0 + 1e-6));
+    const double inv_cs = grid_inv_cell(radius);
     const int n_state = rg_cdiv(b.T, SCAN_TILE) + 1;
     k_clear_tables<<<rg_cdiv(b.T, 256), 256, 0, st>>>(n_ptr, b.rep, b.cnt, b.fill, nullptr, n_state <= SCAN_CHAIN_TILES + 1 ? b.bsum : nullptr,
                                                       n_state <= SCAN_CHAIN_TILES + 1 ? n_state : 0, nullptr, 0);
@@ -1089,13 +1066,9 @@ int regtr_radius_query(const float* q_xyz, const int* q_seg_off, int nq_cap, con
     if (ws_bytes < regtr_cellgrid_ws_bytes(ns_cap, n_clouds)) return RG_ERR_WORKSPACE;
     if (nq_cap <= 0) return RG_OK;
     hipStream_t st = (hipStream_t)stream;
-    GridBuffers b = carve_grid((void*)grid_ws, ws_bytes, ns_cap > 0 ? ns_cap : 1);
-    GridView g{b.slots, b.sorted, 1.0 / ((double)radius * (1.0 + 1e-6))};
-    // LDS list capacity per query: room for the K survivors of a shrink plus one 64-candidate round
-    int cap = (2 * K + 63) / 64 * 64;
-    if (cap < 256) cap = 256;
-    if (cap > 512) cap = 512;          // 8 register-staged chunks of 64 in the shrink path
-    if (cap < K + RG_WAVE) return RG_ERR_ARG;   // K <= 448
+    const GridView g = grid_view(carve_grid((void*)grid_ws, ws_bytes, ns_cap > 0 ? ns_cap : 1), radius);
+    const int cap = query_list_cap(K);
+    if (cap < 0) return cap;
     const size_t lds = (size_t)QUERY_WAVES * (cap + 32) * sizeof(uint64_t);
     const int grid = rg_cdiv(nq_cap, QUERY_WAVES) < 256 * 64 ? rg_xcd_grid(rg_cdiv(nq_cap, QUERY_WAVES)) : 256 * 64;   // query runs inside
     k_radius_query<<<grid, QUERY_WAVES * RG_WAVE, lds, st>>>(
@@ -1112,12 +1085,10 @@ int regtr_radius_query_self(const int* s_seg_off, int ns_cap, int n_clouds, floa
     if (!s_seg_off || !out_idx || !grid_ws || n_clouds < 1 || K < 1 || K > 448 || !(radius > 0.f) || (order != 0 && order != 1)) return RG_ERR_ARG;
     if (ws_bytes < regtr_cellgrid_ws_bytes(ns_cap, n_clouds)) return RG_ERR_WORKSPACE;
     if (ns_cap <= 0) return RG_OK;
-    GridBuffers b = carve_grid((void*)grid_ws, ws_bytes, ns_cap);
-    GridView g{b.slots, b.sorted, 1.0 / ((double)radius * (1.0 + 1e-6))};
-    int cap = (2 * K + 63) / 64 * 64;
-    if (cap < 256) cap = 256;
-    if (cap > 512) cap = 512;
-    if (cap < K + RG_WAVE) return RG_ERR_ARG;
+    const GridBuffers b = carve_grid((void*)grid_ws, ws_bytes, ns_cap);
+    const GridView g = grid_view(b, radius);
+    const int cap = query_list_cap(K);
+    if (cap < 0) return cap;
     const size_t lds = (size_t)QUERY_WAVES * (SELF_CAND * 16 + (size_t)cap * 8 + 256);
     // waves for 16 slots each of the table's capacity, at most 32 workgroups per CU; the kernel sizes the chunks for the live table
     const long long chunks = ((long long)b.T + 15) / 16;
@@ -1139,8 +1110,7 @@ int regtr_nearest_in_radius(const float* q_xyz, const int* q_seg_off, int nq_cap
         return RG_ERR_ARG;
     if (ws_bytes < regtr_cellgrid_ws_bytes(ns_cap, n_clouds)) return RG_ERR_WORKSPACE;
     if (nq_cap <= 0) return RG_OK;
-    GridBuffers b = carve_grid((void*)grid_ws, ws_bytes, ns_cap > 0 ? ns_cap : 1);
-    GridView g{b.slots, b.sorted, 1.0 / ((double)grid_radius * (1.0 + 1e-6))};
+    const GridView g = grid_view(carve_grid((void*)grid_ws, ws_bytes, ns_cap > 0 ? ns_cap : 1), grid_radius);
     const int blocks = rg_cdiv(nq_cap, 256) < 4096 ? rg_cdiv(nq_cap, 256) : 4096;
     k_nearest_in_radius<<<blocks, 256, 0, (hipStream_t)stream>>>(q_xyz, q_seg_off, s_seg_off, n_clouds, g, radius * radius, out_idx);
     RG_RETURN_IF_LAUNCH_FAILED();
