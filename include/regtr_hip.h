@@ -147,7 +147,8 @@ int regtr_nearest_in_radius(const float* q_xyz, const int* q_seg_off, int nq_cap
                             void* stream);
 
 /* models/backbone_kpconv/kpconv.py:553-562 compute_overlaps, one pyramid level: out[q] = clamp(mean of ov over the valid
- * (< ns) entries of the first H columns of row q of nbr, 0, 1); a row without a valid entry gives NaN as in the reference. */
+ * (0 <= i < ns) entries of the first H columns of row q of nbr, 0, 1); a row without a valid entry gives NaN as in the reference.
+ * The library's own tables pad with ns; a negative entry of a caller's table counts as padding too (it is never used as an index). */
 int regtr_overlap_avgpool(const float* ov, int ns, const int* nbr, int ld_nbr, int nq, int H, float* out, void* stream);
 
 /* (Parity mode's neighbour tables in the reference's KD-tree / std::sort row order: include/regtr_hip_parity.h, libregtr_parity.so --
@@ -279,6 +280,8 @@ int regtr_instnorm_finalize_tiles(const double* partial, const int* seg_off, int
 /* out = a + b over n floats (16-byte aligned pointers): with_pos_embed of the post-norm layer, transformers.py:118-119 */
 int regtr_add_f32(const float* a, const float* b, size_t n, float* out, void* stream);
 
+/* y = LayerNorm(x) gamma + beta (+ add); y_plain (optional) the value before add.  Refused (REGTR_ERR_ARG, nothing launched): D < 4,
+ * D % 4 != 0, n < 0, a NULL x / gamma / beta / y, a non-null pointer that is not 16-byte aligned (every access is a float4). */
 int regtr_layernorm(const float* x, int n, int D, const float* gamma, const float* beta, float eps, const float* add,
                     float* y, float* y_plain, void* stream);
 

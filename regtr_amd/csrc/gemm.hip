@@ -1,5 +1,6 @@
 // C[M,N] = epilogue( A[M,K] * B[K,N] )   float32 in / float32 accumulate on the CDNA4 matrix cores
-// (v_mfma_f32_32x32x2_f32: exact f32, bit-for-bit an fmaf chain in k order).
+// (v_mfma_f32_32x32x2_f32: exact f32, bit-for-bit an fmaf chain in k order -- per split-K chunk one chain from zero, the chunks then added in
+//  float32 in split order; tests/test_gpu_f32_routes.py holds the bit patterns of every instantiation equal to that restatement).
 //
 // Serves every dense contraction of the RegTR hot path: KPConv's [Nq,15*Cin] x [15*Cin,Cout] kernel-point
 // contraction (kpconv_blocks.py:401-406), the unary / shortcut linears (kpconv_blocks.py:557), feat_proj

@@ -336,7 +336,6 @@ static __global__ void __launch_bounds__(256) k_add(const float* __restrict__ a,
     }
 }
 
-// y = LayerNorm(x) * gamma + beta (+ add) ; y_plain (optional) receives the value before `add`.
 int regtr_add_f32(const float* a, const float* b, size_t n, float* out, void* stream)
 {
     if (!a || !b || !out || (((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) % 16)) return RG_ERR_ARG;
@@ -346,10 +345,13 @@ int regtr_add_f32(const float* a, const float* b, size_t n, float* out, void* st
     return RG_OK;
 }
 
+// y = LayerNorm(x) * gamma + beta (+ add) ; y_plain (optional) receives the value before `add`.  Every non-null pointer 16-byte aligned.
 int regtr_layernorm(const float* x, int n, int D, const float* gamma, const float* beta, float eps, const float* add,
                     float* y, float* y_plain, void* stream)
 {
     if (!x || !gamma || !beta || !y || n < 0 || D < 4 || D % 4) return RG_ERR_ARG;
+    // (float4 loads and stores of every operand: D % 4 == 0 keeps the rows aligned only when the bases are)
+    if ((((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)add | (uintptr_t)y | (uintptr_t)y_plain) % 16)) return RG_ERR_ARG;
     if (n == 0) return RG_OK;
     k_layernorm<<<rg_cdiv(n, 4), 256, 0, (hipStream_t)stream>>>(x, n, D, gamma, beta, eps, add, y, y_plain);
     RG_RETURN_IF_LAUNCH_FAILED();

@@ -879,7 +879,7 @@ __global__ void __launch_bounds__(256) k_overlap_avgpool(const float* __restrict
     float sum = 0.f, cnt = 0.f;
     for (int h = 0; h < H; h++) {
         const int i = nbr[(size_t)q * ld + h];
-        if (i < ns) { sum += ov[i]; cnt += 1.f; }
+        if ((unsigned)i < (unsigned)ns) { sum += ov[i]; cnt += 1.f; }      // (a caller's table may pad with -1: never an address)
     }
     const float v = sum / cnt;
     out[q] = fminf(fmaxf(v, 0.f), 1.f);       // torch.clamp propagates NaN; fminf/fmaxf would not:

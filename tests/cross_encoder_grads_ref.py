@@ -243,6 +243,53 @@ def chunk_rows(n):
     return max(32, 4 * -(-max(n, 1) // 4096))
 
 
+def layernorm_fwd(x, gamma, beta, add=None, eps=1e-5):
+    """regtr_layernorm in float64 numpy -> dict 'y' (with add), 'plain' (before it) and the bounds 'b_y', 'b_plain' on |float32 kernel -
+    float64|.  The kernel (csrc/norm.hip, k_layernorm: one wave per row, two passes for the moments, a third for the output):
+      * a row sum: a lane adds its ceil(D / 256) float4 groups (3 additions each), six shuffle levels follow, then the division by D:
+        d = ceil(D / 256) + 9 roundings, each at most gamma_d = d U / (1 - d U) of the sum of magnitudes in all;
+      * mean^ = sum / D:                     e_mean = gamma_d mean|x|
+      * xc^ = x - mean^ (U):                  e_xc = e_mean + U (|xc| + e_mean)
+      * var^ = sum xc^2 / D: the squares of the perturbed xc^ (U each, or none where the compiler fuses), the sum as above:
+                                              e_var = mean(2 |xc| e_xc + e_xc^2) + gamma_(d + 1) mean((|xc| + e_xc)^2)
+      * rstd^ = 1 / sqrtf(var^ + eps): the addition, the square root and the division are correctly rounded (U each, the radicand's U
+        halved by the root: 3 U covers them); the radicand's absolute error e_var moves rstd into [rstd(var + e_var), rstd(max(var - e_var, 0))]
+        -- taken exactly, not to first order: the stress case is a constant row, var = 0,
+        where rstd = 1 / sqrt(eps) and a first-order quotient e_var / (var + eps) is all there is;
+      * y = xc^ rstd^ gamma + beta (+ add): the error of the product xc rstd, |gamma| times it, then one U per operation on the
+        magnitude at hand (two products, the addition of beta; the addition of `add` for y).
+    The amplification of the mean's error by rstd |gamma| is the term that matters: a row offset by 100 with unit spread loses
+    100 d U rstd |gamma| however exact the rest is."""
+    x, gamma, beta = (np.asarray(a, dtype=np.float64) for a in (x, gamma, beta))
+    n, D = x.shape
+    d = -(-D // 256) + 9
+    gam = lambda k: k * U / (1 - k * U)
+    m = lambda a: a.mean(1, keepdims=True)
+    mean = m(x)
+    xc = x - mean
+    var = m(xc * xc)
+    rstd = 1.0 / np.sqrt(var + eps)
+    e_mean = gam(d) * m(np.abs(x))
+    e_xc = e_mean + U * (np.abs(xc) + e_mean)
+    e_var = m(2 * np.abs(xc) * e_xc + e_xc * e_xc) + gam(d + 1) * m((np.abs(xc) + e_xc) ** 2)
+    r_hi = 1.0 / np.sqrt(np.maximum(var - e_var, 0.0) + eps)
+    r_lo = 1.0 / np.sqrt(var + e_var + eps)
+    e_rstd = np.maximum(r_hi - rstd, rstd - r_lo) + 3 * U * r_hi
+    t = xc * rstd
+    e_t = e_xc * r_hi + np.abs(xc) * e_rstd
+    ag = np.abs(gamma)[None, :]
+    plain = t * gamma + beta
+    e_plain = e_t * ag + 2 * U * (np.abs(t) + e_t) * ag + U * (np.abs(plain) + e_t * ag)
+    e_plain = e_plain * (1 + 4 * U)                             # (the second-order products of the three U above)
+    out = {'plain': plain, 'b_plain': e_plain, 'rstd': rstd}
+    if add is None:
+        out['y'], out['b_y'] = plain, e_plain
+    else:
+        y = plain + np.asarray(add, dtype=np.float64)
+        out['y'], out['b_y'] = y, e_plain + U * (np.abs(y) + e_plain)
+    return out
+
+
 def layernorm_bwd(x, gamma, dy, dres=None, eps=1e-5):
     """regtr_layernorm_bwd in float64 numpy -> dict 'dx', 'dgamma', 'dbeta' and the bounds 'b_dx', 'b_dgamma', 'b_dbeta' on
     |float32 kernel - float64|, first order in U.  The kernel, per row (one wave, D / 4 float4 column groups dealt to 64 lanes):

@@ -21,6 +21,10 @@ route_subsample, route_cellgrid, radius_cap, route_radius_query, route_radius_se
 -- which needs K beside the capacity --, staged, row_labels); cases in tests/test_gpu_preprocess_routes.py, universe PREPROCESS_KERNELS =
 PREPROCESS_SHAPE_KERNELS (from launch sizes) | PREPROCESS_ROW_KERNELS (from a reference's counts).
 
+The exact-f32 GEMM (csrc/gemm.hip: choose_splits, the alignment ladder of regtr_gemm_f32) follows the preprocessing section:
+gemm_f32_splits, gemm_f32_ws_bytes, route_gemm_f32 (instantiation + regime tags), universe F32_KERNELS; cases in
+tests/test_gpu_f32_routes.py.
+
 A route is '+'-joined kernel names: the product kernel, then for split-K its reduction ('reduce', 'reduce_stats/vec' or
 'reduce_stats/novec'), then 'stats_pass' when ops.gemm hands C to regtr_instnorm_stats for the statistics instead (split-K with N / 4 not a power of
 two <= 256, where that pass refuses the width as well: tests/test_gpu_dispatch.py asserts the error)."""
@@ -169,7 +173,7 @@ def route_mha(lens, precision, min_wg=4096, heads=8):
 
 def kernels(route):
     """The instantiations of a route: a gather kernel's '/qpw<n>' or '/g<n>' suffix (queries or groups per wave) is a launch argument."""
-    return {k.split('/')[0] if k.startswith(('mfma<', 'c1p<')) else k for k in route.split('+')}
+    return {k.split('/')[0] if k.startswith(('mfma<', 'c1p<', 'f32<')) else k for k in route.split('+')}
 
 
 def _x3_kernels():
@@ -689,3 +693,94 @@ PREPROCESS_SHAPE_KERNELS = ({f'sub/{s}' for s in _SCANS} | {f'grid/{s}' for s in
 PREPROCESS_ROW_KERNELS = ({'rank/two_lane', 'rank/general/pad0', 'rank/general/pad', 'cand/staged', 'cand/unstaged', 'cand/unstaged/shrink'}
                           | {f'shrink{t}/{c}' for t in (1, 2) for c in ('cap256', 'cap_mid', 'cap512', 'cap_limit')})
 PREPROCESS_KERNELS = PREPROCESS_SHAPE_KERNELS | PREPROCESS_ROW_KERNELS
+
+
+# ------------------------------------------------------------------------------------------------ the exact-f32 GEMM (csrc/gemm.hip)
+F32_BK = 32
+
+
+def gemm_f32_tile(N):
+    """(bm, bn): the 4 x 1 wave tile for thin outputs (N <= 32), else 2 x 2."""
+    return (128, 32) if N <= 32 else (64, 64)
+
+
+def gemm_f32_splits(M, N, K):
+    """choose_splits: the K splits asked for (1 = none): none from 384 tiles or below K = 512, else towards 768 workgroups with at least
+    128 of K per split, 16 at most."""
+    bm, bn = gemm_f32_tile(N)
+    tiles = cdiv(M, bm) * cdiv(N, bn)
+    if tiles >= 384 or K < 512:
+        return 1
+    s = min(cdiv(768, tiles), K // 128, 16)
+    return 1 if s < 2 else s
+
+
+def gemm_f32_ws_bytes(M, N, K):                                         # regtr_gemm_f32_ws_bytes
+    s = gemm_f32_splits(M, N, K)
+    return s * M * N * 4 if s > 1 else 0
+
+
+def gemm_f32_plan(M, N, K):
+    """-> (S asked, k_chunk, S_eff): the chunk is rounded up to 32, so fewer chunks than splits may cover K."""
+    S = gemm_f32_splits(M, N, K)
+    k_chunk = cdiv(cdiv(K, S), F32_BK) * F32_BK if S > 1 else K
+    return S, k_chunk, cdiv(K, k_chunk)
+
+
+def gemm_f32_fold_tags(M, N, lens):
+    """Which row tiles of a folded launch lie in one cloud (one wave-parallel lookup serves the tile) and which straddle clouds (a search
+    per row).  A row's cloud is the last one that starts at or before it: empty clouds own no row."""
+    bm, _ = gemm_f32_tile(N)
+    starts = [0]
+    for n in lens:
+        starts.append(starts[-1] + n)
+    assert starts[-1] == M
+    seg = lambda i: max(b for b in range(len(lens)) if starts[b] <= i)
+    tags = set()
+    for m0 in range(0, M, bm):
+        tags.add('fold_one_cloud' if seg(m0) == seg(min(m0 + bm, M) - 1) else 'fold_straddle')
+    return tags
+
+
+def route_gemm_f32(M, N, K, lda=None, ldb=None, a_aligned16=True, b_aligned16=True, lens=None):
+    """regtr_gemm_f32's launch: 'f32<ALIGNED_A,ALIGNED_B,WMW,WNW>/tag/..' and '+splitk_reduce' after a split launch; 'none' for M = 0,
+    'refused' for what the launcher refuses.  Tags (regimes of one instantiation, none of them a template argument):
+      nosplit | split [split_short: S_eff < S]          the launch; a split launch writes raw partials and reduces them in split order
+      nk1, nk_odd, nk_even                              32-deep tiles of a chunk, over all chunks: the two-stage pipeline leaves its loop
+                                                        after the even or after the odd half, and never enters the second for one tile
+      ktail [ktail_lt4]                                 a chunk whose length is no multiple of 32 [its last tile holds fewer than 4 k]
+      fold_one_cloud, fold_straddle                     (lens given: the folded InstanceNorm operand) see gemm_f32_fold_tags"""
+    lda = K if lda is None else lda
+    ldb = N if ldb is None else ldb
+    if M < 0 or N < 1 or K < 1 or lda < K or ldb < N:
+        return 'refused'
+    if M == 0:
+        return 'none'
+    S, k_chunk, S_eff = gemm_f32_plan(M, N, K)
+    aligned_a = K % 4 == 0 and lda % 4 == 0 and a_aligned16 and k_chunk % 4 == 0
+    aligned_b = N % 4 == 0 and ldb % 4 == 0 and b_aligned16
+    if N <= 32:
+        k = 'f32<1,1,4,1>' if aligned_a and aligned_b else ('f32<1,0,4,1>' if aligned_a else 'f32<0,0,4,1>')
+    else:
+        k = 'f32<1,1,2,2>' if aligned_a and aligned_b else 'f32<0,0,2,2>'
+    tags = ['nosplit'] if S_eff == 1 else (['split', 'split_short'] if S_eff < S else ['split'])
+    chunks = sorted({min(k_chunk, K - s * k_chunk) for s in range(S_eff)})
+    nks = {cdiv(c, F32_BK) for c in chunks}
+    tags += [t for t, hit in (('nk1', 1 in nks), ('nk_odd', any(n > 1 and n % 2 for n in nks)), ('nk_even', any(n % 2 == 0 for n in nks))) if hit]
+    tails = [c % F32_BK for c in chunks if c % F32_BK]
+    if tails:
+        tags.append('ktail')
+        if any(t < 4 for t in tails):
+            tags.append('ktail_lt4')
+    if lens is not None:
+        tags += sorted(gemm_f32_fold_tags(M, N, lens))
+    return '/'.join([k] + tags) + ('+splitk_reduce' if S_eff > 1 else '')
+
+
+def f32_tags(route):
+    """(instantiation, set of regime tags) of a route_gemm_f32 route."""
+    parts = route.split('+')[0].split('/')
+    return parts[0], set(parts[1:])
+
+
+F32_KERNELS = {'f32<1,1,4,1>', 'f32<1,0,4,1>', 'f32<0,0,4,1>', 'f32<1,1,2,2>', 'f32<0,0,2,2>', 'splitk_reduce'}

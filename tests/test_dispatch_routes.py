@@ -7,7 +7,9 @@ MAXPOOL_KERNELS) and fails when no parametrized GPU case of tests/test_gpu_dispa
 tests/test_gpu_gather.py routes to one -- e.g. after a planner retune moved a case off its branch.  The gather mirror is checked against the library's regtr_kpconv_gather_computes_flag only:
 a refusal is never probed by calling a launcher with stand-in pointers (a mirror wrong about it would launch on garbage).  The backward
 launchers (losses, LayerNorm / bias-ReLU, KPConv) are mirrored and gated the same way at the end of the file: their planners against
-the workspace queries, their universes against tests/test_gpu_bwd_routes.py and the four *_grads files."""
+the workspace queries, their universes against tests/test_gpu_bwd_routes.py and the four *_grads files.  The exact-f32 GEMM closes the
+file: choose_splits against regtr_gemm_f32_ws_bytes, dispatch.F32_KERNELS and its regimes against tests/test_gpu_f32_routes.py, and the
+alignment refusals of regtr_layernorm / regtr_add_f32."""
 import itertools
 
 from tests import dispatch
@@ -624,3 +626,96 @@ def test_preprocess_edges_are_reached():
         listed = PR.row_case_labels(16, kernel)[1]
         assert {1, 31, 32, 33, 40, 64, 65, 72} <= listed and (kernel == 'self' or 0 in listed)
     assert {n for (n,) in _params(g.test_many_clouds, ['n_clouds'])} == {130, 260}
+
+
+# ------------------------------------------------------------------------------------------------ the exact-f32 GEMM (csrc/gemm.hip)
+F32_NS = NS + [1, 3, 15, 31, 33, 50]
+
+
+def test_gemm_f32_split_mirror_matches_library():
+    """choose_splits through the workspace query (splits M N 4 bytes, 0 without a split) over the grid of the split kernel's mirror and
+    the thin / unaligned widths; the shapes whose plan the GPU cases lean on, by hand: S asked, chunk (rounded up to 32), S_eff, last chunk."""
+    from regtr_amd import _lib
+    L = _lib.lib()
+    n = 0
+    for M, N, K in itertools.product(MS, F32_NS, KS + [515, 640, 1030]):
+        assert L.regtr_gemm_f32_ws_bytes(M, N, K) == dispatch.gemm_f32_ws_bytes(M, N, K), (M, N, K)
+        n += dispatch.gemm_f32_splits(M, N, K) > 1
+    assert n > 500
+    last = lambda M, N, K: K - (dispatch.gemm_f32_plan(M, N, K)[2] - 1) * dispatch.gemm_f32_plan(M, N, K)[1]
+    assert dispatch.gemm_f32_plan(300, 32, 1030) == (8, 160, 7) and last(300, 32, 1030) == 70
+    assert dispatch.gemm_f32_plan(300, 32, 1024) == (8, 128, 8)
+    assert dispatch.gemm_f32_plan(300, 3, 640) == (5, 128, 5)
+    assert dispatch.gemm_f32_plan(130, 50, 515) == (4, 160, 4) and last(130, 50, 515) == 35
+    assert dispatch.gemm_f32_plan(130, 1024, 3840) == (16, 256, 15)
+    assert dispatch.gemm_f32_plan(129, 64, 511) == (1, 511, 1) and dispatch.gemm_f32_plan(64 * 384, 64, 3840) == (1, 3840, 1)
+    assert dispatch.route_gemm_f32(300, 32, 1030) == 'f32<0,0,4,1>/split/split_short/nk_odd/ktail+splitk_reduce'
+    assert dispatch.route_gemm_f32(300, 3, 640) == 'f32<1,0,4,1>/split/nk_even+splitk_reduce'
+    assert dispatch.route_gemm_f32(129, 64, 64, lda=68, a_aligned16=False) == 'f32<0,0,2,2>/nosplit/nk_even'
+    assert dispatch.route_gemm_f32(129, 32, 64, ldb=33) == 'f32<1,0,4,1>/nosplit/nk_even'
+    assert dispatch.route_gemm_f32(5, 32, 64, lda=63) == 'refused' and dispatch.route_gemm_f32(0, 32, 64) == 'none'
+    assert dispatch.gemm_f32_fold_tags(305, 32, [33, 1, 0, 64, 7, 200]) == {'fold_one_cloud', 'fold_straddle'}
+    assert dispatch.gemm_f32_fold_tags(128, 32, [0, 128, 0]) == {'fold_one_cloud'}
+
+
+def test_every_gemm_f32_instantiation_is_reached():
+    """All five k_gemm_f32 instantiations, each unsplit and split (no split is unreachable: every instantiation has a shape with fewer than
+    384 tiles and K >= 512), each with one, an odd and an even number of k tiles per chunk and with a k tail (the unaligned ones with a tail
+    shorter than a float4); S_eff < S; the fold on one-cloud and on straddling tiles of both tile shapes, unsplit and split; M = 0 and
+    M = 1; the row-tile edges bm - 1, bm, bm + 1 of both tiles."""
+    from tests import test_gpu_f32_routes as gf
+    plain = _params(gf.test_gemm_f32_vs_fp64_and_chain, 'M N K view route'.split())
+    fold = _params(gf.test_gemm_f32_fold_vs_fp64_and_chain, 'N K route'.split())
+    routes, seen = [], {}
+    for M, N, K, view, route in plain:
+        assert gf._r(M, N, K, view) == route, (M, N, K, view)
+        routes.append(route)
+        seen.setdefault(dispatch.f32_tags(route)[0], set()).update(dispatch.f32_tags(route)[1])
+    _gate(dispatch.F32_KERNELS, routes)
+    for k in sorted(dispatch.F32_KERNELS - {'splitk_reduce'}):
+        want = {'nosplit', 'split', 'nk1', 'nk_odd', 'nk_even', 'ktail'} | ({'ktail_lt4'} if k.startswith('f32<0') else set())
+        assert want <= seen[k], (k, sorted(want - seen[k]))
+        # a split exists for every instantiation, so none is exempt
+        assert any(dispatch.f32_tags(r)[0] == k and 'split' in dispatch.f32_tags(r)[1] for r in routes)
+    assert any('split_short' in dispatch.f32_tags(r)[1] for r in routes)
+    views = {(dispatch.f32_tags(r)[0], v) for _, _, _, v, r in plain}
+    assert {('f32<0,0,4,1>', 'off1'), ('f32<0,0,2,2>', 'off1'), ('f32<1,1,4,1>', 'strided'), ('f32<1,1,2,2>', 'strided'),
+            ('f32<1,0,4,1>', 'strided')} <= views
+    assert any(v == 'strided' and '+splitk_reduce' in r for _, _, _, v, r in plain)          # ldc > N through the reduction too
+    for thin, bm in ((True, 128), (False, 64)):
+        Ms = {M for M, N, _, _, _ in plain if (N <= 32) == thin}
+        assert {1, bm - 1, bm, bm + 1} <= Ms, (bm, sorted(Ms))
+    assert dispatch.route_gemm_f32(0, 32, 64) == 'none' and callable(gf.test_gemm_f32_no_rows)
+    for N in (32, 64):
+        for split in (False, True):
+            tags = set().union(*(dispatch.f32_tags(r)[1] for n, K, r in fold if n == N and ('split' in dispatch.f32_tags(r)[1]) == split))
+            assert {'fold_one_cloud', 'fold_straddle'} <= tags, (N, split)
+    for N, K, route in fold:
+        assert gf._r(gf.FOLD_M, N, K, lens=gf.FOLD_LENS) == route
+    assert 0 in gf.FOLD_LENS and 1 in gf.FOLD_LENS
+    assert {dispatch.f32_tags(r)[0] for _, _, r in fold} >= {'f32<1,1,4,1>', 'f32<0,0,4,1>', 'f32<1,1,2,2>', 'f32<0,0,2,2>'}
+
+
+def test_layernorm_and_add_refuse_misaligned_pointers():
+    """regtr_layernorm and regtr_add_f32 read and write float4: every non-null pointer must be 16-byte aligned.  Stand-in pointers, only
+    calls the host refuses: nothing is launched."""
+    from regtr_amd import _lib
+    L = _lib.lib()
+    FAKE = 0x10000
+    names = ['x', 'gamma', 'beta', 'add', 'y', 'y_plain']
+
+    def ln(n=8, D=64, **off):
+        p = {k: None if k in off and off[k] is None else FAKE + off.get(k, 0) for k in names}
+        return L.regtr_layernorm(p['x'], n, D, p['gamma'], p['beta'], 1e-5, p['add'], p['y'], p['y_plain'], None)
+
+    for name in names:
+        for o in (4, 8, 12):
+            assert ln(**{name: o}) == -2, (name, o)
+            assert ln(n=0, **{name: o}) == -2, (name, o)                 # refused before the empty-input return
+    assert ln(add=None, y_plain=None, x=4) == -2 and ln(add=None, y=12) == -2
+    assert ln(D=6, x=4) == -2 and ln(D=2) == -2 and ln(n=-1) == -2 and ln(x=None) == -2 and ln(y=None) == -2
+    assert ln(n=0) == 0 and ln(n=0, add=None, y_plain=None) == 0           # aligned and empty: accepted, nothing to launch
+    for o in (4, 8, 12):
+        assert L.regtr_add_f32(FAKE + o, FAKE, 16, FAKE, None) == -2 and L.regtr_add_f32(FAKE, FAKE + o, 16, FAKE, None) == -2
+        assert L.regtr_add_f32(FAKE, FAKE, 16, FAKE + o, None) == -2
+    assert L.regtr_add_f32(FAKE, FAKE, 0, FAKE, None) == 0
