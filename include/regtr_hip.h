@@ -51,6 +51,8 @@
  *   regtr_instnorm_bwd        BatchNormBlock (InstanceNorm1d) + LeakyReLU + shortcut, backward   kpconv_blocks.py:497-519,556-561,741
  *   regtr_maxpool_argmax      max_pool: the index torch.max(dim) keeps for autograd   kpconv_blocks.py:142
  *   regtr_maxpool_gather_bwd  max_pool backward                   kpconv_blocks.py:127-143
+ *   regtr_head_tail_bwd       CorrespondenceRegressor backward, the 3-wide and 1-wide output Linears   models/regtr.py:432-441
+ *   regtr_bce_logits_bwd      nn.BCEWithLogitsLoss backward (the overlap loss)   models/regtr.py:250-257
  */
 #ifndef REGTR_HIP_H
 #define REGTR_HIP_H
@@ -69,7 +71,8 @@ extern "C" {
 /* ABI version of THIS header.  Entry points have gained arguments between versions (regtr_maxpool_gather, regtr_radius_query,
  * regtr_kpconv_gather, regtr_instnorm_apply, regtr_mha_fwd, regtr_gemm_x3): a binding generated from another version of the header
  * would pass shifted arguments, so every binding must compare regtr_abi_version() with the REGTR_ABI_VERSION it was written against
- * before its first call (regtr_amd/_lib.py does).  Bumped on any signature change. */
+ * before its first call (regtr_amd/_lib.py does).  Bumped on any signature change; a new entry point shifts nobody's
+ * arguments and does not bump it. */
 #define REGTR_ABI_VERSION 11
 int regtr_abi_version(void);
 
@@ -592,6 +595,30 @@ int regtr_maxpool_argmax(const float* x, int ns, int C, const int* nbr, int ld_n
  * NULL with ns > 0, dy / arg / entries NULL with nq > 0 and ns > 0, dy / dx not 16-byte or arg not 8-byte aligned. */
 int regtr_maxpool_gather_bwd(const float* dy, const short* arg, int nq, int H, int C, const int* row_off, const int* entries, int ns,
                              float* dx, void* stream);
+
+/* ---- correspondence head and overlap loss backward (regtr_amd/head_grad.py) ----------------------------------------------------------- */
+
+/* Backward of CorrespondenceRegressor's two narrow outputs, corr = h2 W4^T + b4 [m, 3] and logit = f wc^T + bc [m], in one pass over
+ * the rows.  dcorr [m, 3] and dlogit [m] are the outputs' gradients (either may be NULL: its outputs are then written as +0), h2 [m, D]
+ * what coor_mlp[2] stored AFTER its ReLU, f [m, D] the head's input, W4 [3, D], wc [D]:
+ *   g2 [m, D] = h2 > 0 ? (dcorr_0 W4_0 + dcorr_1 W4_1) + dcorr_2 W4_2 : +0     (the gradient in front of coor_mlp[2]'s ReLU)
+ *   r  [m, D] = dlogit wc                                                     (the logit branch's share of df: the `residual` of the dX GEMM)
+ *   dW4 [3, D] = dcorr^T h2,  db4 [3] = sum_rows dcorr,  dwc [D] = dlogit^T f,  dbc [1] = sum_rows dlogit,  db2 [D] = sum_rows g2 (optional)
+ * Two launches like regtr_bias_relu_bwd's: per-workgroup partial sums over fixed row chunks (a function of m only), each thread adding
+ * its rows in row order, then the chunks of a column in a fixed order in float64.  One owner per output element, no atomics,
+ * bit-reproducible.  Rows >= m of g2 / r are not written.  m = 0: nothing to do, REGTR_OK, nothing written.  Refused (REGTR_ERR_ARG,
+ * nothing launched): m < 0, D < 64 or not a multiple of 64, a NULL pointer other than dcorr / dlogit / db2 with work to do, h2 / f / W4 /
+ * wc / g2 / r / ws not 16-byte aligned, g2 or r aliasing each other or an input.  ws: regtr_head_tail_bwd_ws_bytes(m, D) bytes
+ * (REGTR_ERR_WORKSPACE when smaller; 0 when there is nothing to do or the shape is refused). */
+size_t regtr_head_tail_bwd_ws_bytes(int m, int D);
+int regtr_head_tail_bwd(const float* dcorr, const float* dlogit, const float* h2, const float* f, const float* W4, const float* wc, int m,
+                        int D, float* g2, float* r, float* dW4, float* db4, float* dwc, float* dbc, float* db2, void* ws, size_t ws_bytes,
+                        void* stream);
+
+/* Backward of mean_i BCEWithLogits(logit_i, target_i) over n points: dlogit_i = (grad / n) (sigmoid(logit_i) - target_i), grad ONE
+ * float on the device.  The sigmoid is formed from exp(-|logit|) (no overflow, no cancellation for large |logit|).  n = 0: nothing to
+ * do.  Refused: n < 0, NULLs with work to do. */
+int regtr_bce_logits_bwd(const float* logit, const float* target, const float* grad, int n, float* dlogit, void* stream);
 
 #ifdef __cplusplus
 }

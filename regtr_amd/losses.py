@@ -1,13 +1,15 @@
-"""Differentiable drop-ins for the reference's training losses: InfoNCELossFull (models/losses/feature_loss.py:246-314) and
-CorrCriterion (models/losses/corr_loss.py:9-40), with the same constructors, parameter names and forward signatures, so that
+"""Differentiable drop-ins for the reference's training losses: InfoNCELossFull (models/losses/feature_loss.py:246-314),
+CorrCriterion (models/losses/corr_loss.py:9-40) and OverlapCriterion (nn.BCEWithLogitsLoss, models/regtr.py:84,250-252), with the same
+constructors, parameter names and forward signatures, so that
 
     model.feature_criterion = InfoNCELossFull(cfg.d_embed, cfg.r_p, cfg.r_n)
     model.feature_criterion_un = InfoNCELossFull(cfg.d_embed, cfg.r_p, cfg.r_n)
     model.corr_criterion = CorrCriterion(metric='mae')
+    model.overlap_criterion = OverlapCriterion()
 
 drop into the reference model's training step ("Training-loss drop-in").  Forward and backward run on the HIP kernels
-of csrc/losses.hip (regtr_infonce_rows / regtr_infonce_bwd / regtr_gemm_tn, regtr_loss_terms / regtr_corr_l1_bwd) and the exact-f32
-GEMM; torch only packs the per-pair lists and forms the scalar means.  Nothing here synchronises with the host.
+of csrc/losses.hip (regtr_infonce_rows / regtr_infonce_bwd / regtr_gemm_tn, regtr_loss_terms / regtr_corr_l1_bwd), csrc/head_bwd.hip
+(regtr_bce_logits_bwd) and the exact-f32 GEMM; torch only packs the per-pair lists and forms the scalar means.  Nothing here synchronises with the host.
 
 Reference semantics are kept: a pair without an anchor inside r_p gives NaN (0 / 0), and its gradient contributions are exactly 0.
 Refused: metric='mse', overlap_weights=None, coordinates / poses / weights that require grad, double backward, tensors off the GPU.
@@ -155,3 +157,51 @@ class CorrCriterion(nn.Module):
         warped = torch.cat(list(kp_warped_pred)).contiguous()
         w = torch.cat([x.reshape(-1) for x in overlap_weights]).contiguous()
         return _CorrL1.apply(warped, kp, w, seg, seg2, pose_gt.contiguous())
+
+
+class _OverlapBCE(torch.autograd.Function):
+    """mean_i BCEWithLogits(logit_i, gt_i): the BCE sums of regtr_loss_terms (per pair, float64 inside), added and divided as
+    RegTR.compute_loss does -- the same bits on the same tensors.  kp, warped, pose only feed that kernel's other columns."""
+
+    @staticmethod
+    def forward(ctx, logit, gt, seg2, kp, warped, pose):
+        with context.forward(logit.device, f16_pair=False, status=None):
+            terms = ops.loss_terms(logit, gt, kp, warped, seg2, pose)
+        ctx.save_for_backward(logit, gt)
+        return terms[:, 0].sum() / logit.shape[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        logit, gt = ctx.saved_tensors
+        g = g.detach().to(torch.float32).contiguous()
+        with context.forward(logit.device, f16_pair=False, status=None):
+            d = ops.bce_logits_bwd(logit, gt, g)
+        return d, None, None, None, None, None
+
+
+def overlap_bce(logit, gt, seg2, kp, warped, pose):
+    """_OverlapBCE on the tensors RegTR.compute_loss hands regtr_loss_terms (seg2 (2B+1,): src clouds, then tgt clouds)."""
+    return _OverlapBCE.apply(logit, gt, seg2, kp, warped, pose)
+
+
+class OverlapCriterion(nn.Module):
+    """nn.BCEWithLogitsLoss() (mean reduction, no weights) on packed (N,) logits and float targets in [0, 1], forward and backward on
+    the HIP kernels.  forward(logit, target, seg_off=None): seg_off (2B+1,) int32 on the GPU, the (src clouds, tgt clouds) offsets of a
+    pair batch -- the sum is then taken pair by pair as RegTR.compute_loss takes it (bit-equal to its overlap term); None: one sum over
+    all points.  Gradients go to logit."""
+
+    def forward(self, logit, target, seg_off=None):
+        _on_gpu('OverlapCriterion', [logit, target] + ([] if seg_off is None else [seg_off]))
+        _no_grad_inputs('OverlapCriterion', [target])
+        if logit.dtype != torch.float32 or target.dtype != torch.float32:
+            raise RuntimeError('OverlapCriterion: float32 logits and targets only')
+        if logit.dim() != 1 or target.shape != logit.shape or logit.shape[0] < 1:
+            raise RuntimeError(f'OverlapCriterion: logit and target must be (N,) with N >= 1, got {tuple(logit.shape)}, {tuple(target.shape)}')
+        n, dev = logit.shape[0], logit.device
+        if seg_off is None:
+            seg_off = torch.tensor([0, n, n], dtype=torch.int32).to(dev, non_blocking=True)
+        B = seg_off.numel() // 2
+        zeros = torch.zeros((n, 3), dtype=torch.float32, device=dev)
+        pose = torch.eye(3, 4, dtype=torch.float32, device=dev).expand(B, 3, 4).contiguous()
+        return _OverlapBCE.apply(logit.contiguous(), target.contiguous(), seg_off, zeros, zeros, pose)

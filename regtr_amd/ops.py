@@ -914,3 +914,45 @@ def gemm_tn_any(a, b):
           'regtr_gemm_tn_any')
     return out
 
+
+
+# ------------------------------------------------------------------------------------------------ correspondence head / overlap loss backward
+def head_tail_bwd(dcorr, dlogit, h2, f, w4, wc, out_g2=None, out_r=None):
+    """Backward of CorrespondenceRegressor's narrow outputs corr = h2 w4^T + b4 and logit = f wc^T + bc in one pass (regtr_head_tail_bwd):
+    dcorr (M, 3) | None, dlogit (M,) | None, h2 (M, D) the activation stored after coor_mlp[2]'s ReLU, f (M, D) the head's input, w4
+    (3, D), wc (D,) or (1, D) -> (g2 (M, D) = (dcorr w4) where h2 > 0 else 0, r (M, D) = dlogit wc, dw4 (3, D), db4 (3,), dwc (D,), dbc
+    (1,), db2 (D,) = the column sums of g2).  An absent gradient's outputs are zeros.  out_g2 / out_r: the buffers to write, or None
+    for new ones.  D a multiple of 64.  Bit-reproducible.  Nothing here synchronises."""
+    L = _lib.lib()
+    M, D = h2.shape
+    wc = wc.reshape(-1)
+    if tuple(f.shape) != (M, D) or tuple(w4.shape) != (3, D) or wc.numel() != D:
+        raise RuntimeError(f'head_tail_bwd: f must be ({M}, {D}), w4 (3, {D}) and wc ({D},), got {tuple(f.shape)}, {tuple(w4.shape)}, {tuple(wc.shape)}')
+    if dcorr is not None and tuple(dcorr.shape) != (M, 3):
+        raise RuntimeError(f'head_tail_bwd: dcorr must be ({M}, 3), got {tuple(dcorr.shape)}')
+    if dlogit is not None and dlogit.numel() != M:
+        raise RuntimeError(f'head_tail_bwd: dlogit must have {M} elements, got {tuple(dlogit.shape)}')
+    g2 = torch.empty((M, D), dtype=torch.float32, device=h2.device) if out_g2 is None else out_g2
+    r = torch.empty((M, D), dtype=torch.float32, device=h2.device) if out_r is None else out_r
+    for o in (g2, r):
+        if tuple(o.shape) != (M, D):
+            raise RuntimeError(f'head_tail_bwd: an output buffer must be ({M}, {D}), got {tuple(o.shape)}')
+    sums = torch.zeros(5 * D + 4, dtype=torch.float32, device=h2.device)        # M = 0: nothing is launched and the sums are 0
+    nb = L.regtr_head_tail_bwd_ws_bytes(M, D)
+    ws = _ws(max(nb, 1), h2.device)
+    base = ptr(sums)
+    check(L.regtr_head_tail_bwd(ptr(dcorr), ptr(dlogit), ptr(h2), ptr(f), ptr(w4), ptr(wc), M, D, ptr(g2), ptr(r), base, base + 16 * D,
+                                base + 12 * D, base + 16 * D + 12, base + 16 * D + 16, bptr(ws), nb, stream()), 'regtr_head_tail_bwd')
+    return (g2, r, sums[:3 * D].view(3, D), sums[4 * D:4 * D + 3], sums[3 * D:4 * D], sums[4 * D + 3:4 * D + 4], sums[4 * D + 4:])
+
+
+def bce_logits_bwd(logit, gt, grad):
+    """Backward of nn.BCEWithLogitsLoss() (mean) on packed points (regtr_bce_logits_bwd): logit, gt (n,), grad a 0-dim float32 device
+    tensor -> d logit (n,) = grad (sigmoid(logit) - gt) / n."""
+    n = logit.numel()
+    if gt.numel() != n:
+        raise RuntimeError(f'bce_logits_bwd: logit and gt must have the same number of elements, got {n} and {gt.numel()}')
+    out = torch.empty(logit.shape, dtype=torch.float32, device=logit.device)
+    check(_lib.lib().regtr_bce_logits_bwd(ptr(logit) if n else None, ptr(gt) if n else None, ptr(grad.reshape(1)), n,
+                                          ptr(out) if n else None, stream()), 'regtr_bce_logits_bwd')
+    return out

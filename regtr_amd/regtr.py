@@ -5,7 +5,9 @@ same `forward(batch) -> dict` contract (input lists batch['src_xyz'] / batch['tg
 batch['kpconv_meta'], output keys of regtr.py:218-235), same `state_dict` names and shapes, so a reference checkpoint
 loads with `load_state_dict(state['state_dict'])` (demo.py:165).  `compute_loss(pred, batch)` gives the reference's validation /
 test losses (regtr.py:237-294) without gradients: the InfoNCE feature terms on regtr_infonce, the overlap and correspondence terms on
-regtr_loss_terms.  Training (autograd, optimiser) is not implemented.
+regtr_loss_terms.  `training_step(batch)` trains everything above a frozen KPConv backbone (feat_proj, the cross-encoder, the
+correspondence head, the InfoNCE W) with HIP backward kernels: forward_grad / compute_loss_grad / trainable_parameters; the backbone's
+backward and an optimiser loop are not implemented.
 
 The forward enqueues every stage on the current HIP stream with ONE host synchronisation (the data-dependent level
 sizes after preprocessing): preprocess -> KPConv encoder -> feat_proj -> 6 cross-encoder layers on packed tokens ->
@@ -54,16 +56,26 @@ class CorrespondenceRegressor(nn.Module):
         self.conf_logits_decoder = nn.Linear(d_embed, 1)
         self._cache = {}
 
+    def _mlp(self, f):
+        """f (M, D) -> (h1, h2, corr (M, 3), logit (M, 1)): the four Linears, the ReLUs in the first two's epilogues."""
+        wt = lambda k, lin: _prepared(self._cache, k, lin.weight, lambda w: ops.SplitWeight(w, 'nk'))
+        h1 = ops.gemm(f, wt('0', self.coor_mlp[0]), bias=self.coor_mlp[0].bias.detach(), relu=True)
+        h2 = ops.gemm(h1, wt('2', self.coor_mlp[2]), bias=self.coor_mlp[2].bias.detach(), relu=True)
+        corr = ops.gemm(h2, wt('4', self.coor_mlp[4]), bias=self.coor_mlp[4].bias.detach())
+        logit = ops.gemm(f, wt('c', self.conf_logits_decoder), bias=self.conf_logits_decoder.bias.detach())
+        return h1, h2, corr, logit
+
     def forward(self, feats):
         """feats (L, N, D) -> corr (L, N, 3), logit (L, N)."""
         Lyr, N, D = feats.shape
-        f = feats.view(Lyr * N, D)
-        wt = lambda k, lin: _prepared(self._cache, k, lin.weight, lambda w: ops.SplitWeight(w, 'nk'))
-        h = ops.gemm(f, wt('0', self.coor_mlp[0]), bias=self.coor_mlp[0].bias.detach(), relu=True)
-        h = ops.gemm(h, wt('2', self.coor_mlp[2]), bias=self.coor_mlp[2].bias.detach(), relu=True)
-        corr = ops.gemm(h, wt('4', self.coor_mlp[4]), bias=self.coor_mlp[4].bias.detach())
-        logit = ops.gemm(f, wt('c', self.conf_logits_decoder), bias=self.conf_logits_decoder.bias.detach())
+        _, _, corr, logit = self._mlp(feats.view(Lyr * N, D))
         return corr.view(Lyr, N, 3), logit.view(Lyr, N)
+
+    def forward_grad(self, feats):
+        """forward(feats), bit for bit, differentiable in feats and in all eight parameters, with a HIP backward
+        (regtr_amd/head_grad.py).  Refused: CPU tensors, double backward, d_embed not a multiple of 64."""
+        from . import head_grad
+        return head_grad.regressor_forward_grad(self, feats)
 
 
 class CorrespondenceDecoder(nn.Module):
@@ -81,6 +93,10 @@ class CorrespondenceDecoder(nn.Module):
         self.k_proj = nn.Linear(d_embed, d_embed)
         self.conf_logits_decoder = nn.Linear(d_embed, 1)
         self._cache = {}
+
+    def forward_grad(self, *args, **kwargs):
+        raise NotImplementedError('CorrespondenceDecoder.forward_grad: the attention-valued head (direct_regress_coor: false) has no '
+                                  'backward (regtr_attn_xyz); only CorrespondenceRegressor is differentiable')
 
     def forward(self, feats, pe, xyz, seg_off, kv_cross, max_len):
         """feats (L, N, D) conditioned features of all clouds, pe (N, D), xyz (N, 3) -> corr (L, N, 3), logit (L, N)."""
@@ -302,12 +318,16 @@ class RegTR(nn.Module):
         with context.forward(dev, f16_pair=False, force_x3=True, status=None):
             return self._forward(batch, dev)
 
-    def _forward(self, batch, dev):
-        B = len(batch['src_xyz'])
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if _TIMEIT else None
-        if ev: ev[0].record()
+    def _kv_tables(self, B, dev):
+        """(kv_self, kv_cross) (2B,) int32: the cloud each cloud's self- / cross-attention reads (its own; its pair's partner)."""
+        kv_self = _prepared(self._cache, ('kv_self', B, dev), self.feat_proj.bias,
+                            lambda _: torch.arange(2 * B, dtype=torch.int32, device=dev))
+        kv_cross = _prepared(self._cache, ('kv_cross', B, dev), self.feat_proj.bias,
+                             lambda _: torch.cat([torch.arange(B, 2 * B), torch.arange(0, B)]).to(torch.int32).to(dev))
+        return kv_self, kv_cross
 
-        # ---- preprocess (regtr.py:117-122) + KPConv encoder (regtr.py:136)
+    def _backbone(self, batch, dev, ev=None):
+        """preprocess (regtr.py:117-122) + KPConv encoder (regtr.py:136) -> (feats_un, kpconv_meta); sets batch['kpconv_meta']."""
         clouds = batch['src_xyz'] + batch['tgt_xyz']
         n0 = sum(int(p.shape[0]) for p in clouds)
         n_l0 = self.kpf_encoder.level0_blocks()
@@ -343,6 +363,13 @@ class RegTR(nn.Module):
             feats0 = self._ones(kpconv_meta['points'][0].shape[0], dev)
             if ev: ev[1].record()
             feats_un, _ = self.kpf_encoder(feats0, kpconv_meta)
+        return feats_un, kpconv_meta
+
+    def _forward(self, batch, dev):
+        B = len(batch['src_xyz'])
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if _TIMEIT else None
+        if ev: ev[0].record()
+        feats_un, kpconv_meta = self._backbone(batch, dev, ev)
         slens_c = kpconv_meta['_lens_host'][-1]
         src_slens_c, tgt_slens_c = slens_c[:B], slens_c[B:]
         if ev: ev[2].record()
@@ -353,10 +380,7 @@ class RegTR(nn.Module):
         xyz_c = kpconv_meta['points'][-1]
         seg_c = kpconv_meta['_seg_off'][-1]
         pe = self.pos_embed(xyz_c) if self.cfg.transformer_encoder_has_pos_emb else None
-        kv_self = _prepared(self._cache, ('kv_self', B, dev), self.feat_proj.bias,
-                            lambda _: torch.arange(2 * B, dtype=torch.int32, device=dev))
-        kv_cross = _prepared(self._cache, ('kv_cross', B, dev), self.feat_proj.bias,
-                             lambda _: torch.cat([torch.arange(B, 2 * B), torch.arange(0, B)]).to(torch.int32).to(dev))
+        kv_self, kv_cross = self._kv_tables(B, dev)
         feats_cond = self.transformer_encoder(both_feats_un, pe, seg_c, kv_self, kv_cross, max(slens_c))   # (L, N, D)
 
         # ---- correspondence head (regtr.py:168) and pose (regtr.py:185-203)
@@ -394,6 +418,154 @@ class RegTR(nn.Module):
             'pose': pose,
         }
         return outputs
+
+    # ------------------------------------------------------------------------------------------ training above a frozen backbone
+    def _check_trainable(self, what):
+        """Everything the differentiable path refuses, before any launch."""
+        if not isinstance(self.correspondence_decoder, CorrespondenceRegressor):
+            raise NotImplementedError(f'{what}: the attention-valued head (direct_regress_coor: false) has no backward; only '
+                                      'CorrespondenceRegressor configs can be trained')
+        if self.cfg.get('feature_loss_type', 'infonce') != 'infonce':
+            raise NotImplementedError(f"{what}: feature_loss_type {self.cfg.feature_loss_type!r} (CircleLossFull) is not implemented")
+        missing = [k for k in ('r_p', 'r_n', 'wt_overlap', 'wt_feature', 'wt_feature_un', 'wt_corr') if k not in self.cfg]
+        if missing:
+            raise KeyError(f'{what} needs the losses section of the config (regtr_amd/conf/*.yaml); missing: {missing}')
+
+    def head_layers(self):
+        """The decoder layers a loss reads the head's outputs of: cfg.overlap_loss_on | cfg.corr_loss_on, ascending."""
+        return sorted(set(self.cfg.overlap_loss_on) | set(self.cfg.corr_loss_on))
+
+    def forward_grad(self, batch, backbone_grad=False):
+        """forward(batch) as a differentiable call above a FROZEN backbone: the preprocessor and kpf_encoder run under torch.no_grad()
+        as in forward; feat_proj, the cross-encoder and the correspondence head run through head_grad.stack_forward_grad with a HIP
+        backward, the head on the decoder layers of head_layers() only.  The arithmetic is that of forward's range fallback
+        (compute_dtype 'fp32x3': six-term bf16 splits, float32's operand range), so there is no status word, no end-of-forward wait
+        and no re-run.  Returns the reference's dict as forward does, every entry forward also computes bit-identical to it under
+        that arithmetic, with two differences:
+          * '*_kp_warped' / '*_overlap': per pair a dict {decoder layer: (n, 3) / (n, 1)} over head_layers() -- indexed [b][i] like
+            forward's (L, n, .) tensors, the layers no loss reads absent;
+          * 'pose': (1, B, 3, 4), the LAST decoder layer's, computed without gradient (the reference's loss never reads it); absent
+            when the last layer is not in head_layers().
+        backbone_grad=True: feats_un, the backbone's output, becomes a leaf that requires grad and is returned as pred['_feats_un'];
+        its .grad after backward() is what a backbone backward starts from."""
+        from . import head_grad
+        self._check_trainable('forward_grad')
+        dev = batch['src_xyz'][0].device
+        if dev.type != 'cuda':
+            raise RuntimeError('regtr_amd.RegTR runs on an MI355X (HIP) device only; there is no CPU path')
+        bad = [n for n, p in self.named_parameters() if p.dtype != torch.float32 or p.device != dev]
+        if bad or any(p.device != dev for p in batch['src_xyz'] + batch['tgt_xyz']):
+            raise RuntimeError(f'RegTR.forward_grad: float32 parameters and every input cloud must live on one GPU ({dev}); offending: {bad[:3]}')
+        B = len(batch['src_xyz'])
+        layers = self.head_layers()
+        with context.forward(dev, f16_pair=False, force_x3=True, status=None):
+            with torch.no_grad():
+                feats_un, meta = self._backbone(batch, dev)
+            if backbone_grad:
+                feats_un = feats_un.detach().requires_grad_()
+            slens_c = meta['_lens_host'][-1]
+            xyz_c, seg_c = meta['points'][-1], meta['_seg_off'][-1]
+            kv_self, kv_cross = self._kv_tables(B, dev)
+            both_feats_un, feats_cond, corr, logit = head_grad.stack_forward_grad(
+                self.feat_proj, self.pos_embed if self.cfg.transformer_encoder_has_pos_emb else None, self.transformer_encoder,
+                self.correspondence_decoder, feats_un, xyz_c, seg_c, kv_self, kv_cross, max(slens_c), layers, cache=self._cache)
+            pose = None
+            if layers[-1] == self.cfg.num_encoder_layers - 1:
+                with torch.no_grad():
+                    pose = ops.weighted_procrustes(xyz_c, corr[-1:].detach(), logit[-1:].detach(), seg_c, B)
+        off = [0]
+        for n in slens_c:
+            off.append(off[-1] + n)
+        sl = lambda c: slice(off[c], off[c + 1])
+        logit3 = logit.unsqueeze(-1)
+        per_layer = lambda t, c: {l: t[j, sl(c)] for j, l in enumerate(layers)}
+        pred = {
+            'src_feat_un': tuple(both_feats_un[sl(b)] for b in range(B)),
+            'tgt_feat_un': tuple(both_feats_un[sl(B + b)] for b in range(B)),
+            'src_feat': [feats_cond[:, sl(b)] for b in range(B)],
+            'tgt_feat': [feats_cond[:, sl(B + b)] for b in range(B)],
+            'src_kp': tuple(xyz_c[sl(b)] for b in range(B)),
+            'src_kp_warped': [per_layer(corr, b) for b in range(B)],
+            'tgt_kp': tuple(xyz_c[sl(B + b)] for b in range(B)),
+            'tgt_kp_warped': [per_layer(corr, B + b) for b in range(B)],
+            'src_overlap': [per_layer(logit3, b) for b in range(B)],
+            'tgt_overlap': [per_layer(logit3, B + b) for b in range(B)],
+        }
+        if pose is not None:
+            pred['pose'] = pose
+        if backbone_grad:
+            pred['_feats_un'] = feats_un
+        return pred
+
+    def compute_loss_grad(self, pred, batch):
+        """compute_loss(pred, batch) -- the same keys and reference semantics (regtr.py:237-294) -- as differentiable 0-dim tensors, built
+        from the training criteria of regtr_amd/losses.py: the overlap terms on OverlapCriterion's Function (bit-equal to compute_loss's),
+        the feature terms on InfoNCELossFull's with this model's feature_criterion.W / feature_criterion_un.W, the correspondence terms
+        on CorrCriterion's in both directions (the inverse GT pose for tgt), the total weighted by loss_weight_dict(cfg).  Gradients go
+        to the features, the warped points, the overlap logits and the two W.  No host wait, forward or backward."""
+        from . import losses as L
+        self._check_trainable('compute_loss_grad')
+        cfg = self.cfg
+        meta = batch['kpconv_meta']
+        B = len(pred['src_kp'])
+        dev = pred['src_kp'][0].device
+        lens = [int(n) for n in meta['_lens_host'][-1]]
+        N, n_src = sum(lens), sum(lens[:B])
+        seg_c = meta['_seg_off'][-1]
+        wd = loss_weight_dict(cfg)
+        def rows(key, i=None):
+            """pred's per-pair views of one quantity as ONE packed tensor (src clouds, then tgt clouds).  With a gradient to carry they are
+            concatenated (autograd splits it back); _packed_rows' zero-copy view is a function of its first view only."""
+            views = [x if i is None else x[i] for x in list(pred['src_' + key]) + list(pred['tgt_' + key])]
+            return torch.cat(views, dim=0) if any(v.requires_grad for v in views) else _packed_rows(views)
+        with torch.no_grad(), context.forward(dev, f16_pair=False, status=None):
+            pose = batch['pose']
+            if isinstance(pose, (list, tuple)):
+                pose = torch.stack(list(pose))
+            pose = pose.to(device=dev, dtype=torch.float32).contiguous()
+            batch['overlap_pyr'] = overlap.compute_overlaps(batch)                               # :242-245
+            gt_c = batch['overlap_pyr'][f'pyr_{len(meta["points"]) - 1}']
+            xyz = rows('kp')
+            # T^-1 = [R^T | -R^T t], rounded per operation in regtr_loss_terms' order
+            R, t = pose[:, :3, :3], pose[:, :3, 3]
+            ti = -((R[:, 0, :] * t[:, 0:1] + R[:, 1, :] * t[:, 1:2]) + R[:, 2, :] * t[:, 2:3])
+            pose_inv = torch.cat([R.transpose(1, 2), ti.unsqueeze(-1)], dim=2).contiguous()
+            # the segment tables of the criteria's Functions, derived on the device (regtr_loss_terms' layout with empty tgt clouds)
+            seg_s = seg_c[:B + 1]
+            seg_t = seg_c[B:] - seg_c[B]
+            seg2_s = torch.cat([seg_s, seg_s[-1:].expand(B)])
+            seg2_t = torch.cat([seg_t, seg_t[-1:].expand(B)])
+            anc_xyz = ops.se3_transform(xyz[:n_src], seg_s, pose)                                 # :259 se3_transform_list(pose_gt, src_kp)
+        losses = {}
+        for i in cfg.overlap_loss_on:                                                             # :249-252
+            warped = rows('kp_warped', i)
+            losses[f'overlap_{i}'] = L.overlap_bce(rows('overlap', i).reshape(N), gt_c, seg_c, xyz, warped.detach().contiguous(), pose)
+        feat_sets = [(f'feature_{i}', self.feature_criterion, rows('feat', i)) for i in cfg.feature_loss_on]
+        feat_sets.append(('feature_un', self.feature_criterion_un, rows('feat_un')))
+        for key, crit, feats in feat_sets:                                                        # :255-265
+            losses[key] = L._InfoNCE.apply(feats[:n_src], feats[n_src:], crit.W, anc_xyz, xyz[n_src:], seg_s, seg_t, max(lens[:B]),
+                                           max(lens[B:]), float(cfg.r_p), float(cfg.r_n))
+        for i in cfg.corr_loss_on:                                                                # :268-281
+            warped = rows('kp_warped', i)
+            losses[f'corr_{i}'] = (L._CorrL1.apply(warped[:n_src], xyz[:n_src], gt_c[:n_src], seg_s, seg2_s, pose) +
+                                   L._CorrL1.apply(warped[n_src:], xyz[n_src:], gt_c[n_src:], seg_t, seg2_t, pose_inv))
+        losses['total'] = torch.sum(torch.stack([losses[k] * wd[k] for k in losses]), dim=0)     # :292-293
+        return losses
+
+    def trainable_parameters(self):
+        """The parameters above the backbone -- feat_proj, the cross-encoder, the correspondence head and the two InfoNCE W -- as a
+        list.  Turns requires_grad on for the two W (they are created frozen, which inference keeps)."""
+        mods = [self.feat_proj, self.transformer_encoder, self.correspondence_decoder, self.feature_criterion, self.feature_criterion_un]
+        for crit in mods[3:]:
+            crit.W.requires_grad_(True)
+        return [p for m in mods for p in m.parameters()]
+
+    def training_step(self, batch, batch_idx=None):
+        """generic_reg_model.py:64-66 of the reference: pred = forward_grad(batch), losses = compute_loss_grad(pred, batch) ->
+        (pred, losses); the caller runs losses['total'].backward() and steps its optimiser over trainable_parameters().  The backbone
+        is frozen: kpf_encoder's parameters end with grad None."""
+        pred = self.forward_grad(batch)
+        return pred, self.compute_loss_grad(pred, batch)
 
     # ------------------------------------------------------------------------------------------ losses (validation / test, no gradients)
     def _w_sym(self, crit):

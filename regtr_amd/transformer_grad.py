@@ -58,6 +58,24 @@ class _LayerNorm(torch.autograd.Function):
         return (dx if need[0] else None, dgamma if need[1] else None, dbeta if need[2] else None, dy if need[3] else None, None)
 
 
+def linear_bwd(a, weight, cache, key, dy, h=None, need=(True, True, True), residual=None):
+    """Backward of one Linear y = act(a W^T + b) of this module's kind, on float32 rows: dy (M, N) the gradient of its output, h the
+    activation it stored after its ReLU (None: no ReLU, or dy already carries the mask) -> (da, dw, db) for need = (a, weight, bias).
+    residual (M, K): added to da inside the dX GEMM's epilogue (a gradient that reached `a` by another branch).  The caller holds the
+    launch context."""
+    da = dw = db = None
+    g = dy
+    if h is not None:
+        g, db = ops.bias_relu_bwd(dy, h)
+    elif need[2]:
+        db = ops.bias_relu_bwd(dy)
+    if need[0]:
+        da = ops.gemm(g, _prepared(cache, key, weight, lambda w: ops.SplitWeight(w, 'kn')), planes=3, residual=residual)
+    if need[1]:
+        dw = ops.gemm_tn(g, a)
+    return da, dw, db if need[2] else None
+
+
 class _Linear(torch.autograd.Function):
     """(a, weight (out, in), bias, residual | None) -> act(a W^T + bias) [+ residual] by ops.gemm on the prepared weight `sw`."""
 
@@ -75,18 +93,9 @@ class _Linear(torch.autograd.Function):
         cache, key = ctx.prep
         need = ctx.needs_input_grad
         dy = _rows(dy)
-        da = dw = db = None
         with context.ForwardContext(a.device):
-            g = dy
-            if h is not None:
-                g, db = ops.bias_relu_bwd(dy, h)
-            elif need[2]:
-                db = ops.bias_relu_bwd(dy)
-            if need[0]:
-                da = ops.gemm(g, _prepared(cache, key, weight, lambda w: ops.SplitWeight(w, 'kn')), planes=3)
-            if need[1]:
-                dw = ops.gemm_tn(g, a)
-        return da, dw, db if need[2] else None, dy if need[3] else None, None, None, None, None, None
+            da, dw, db = linear_bwd(a, weight, cache, key, dy, h, need[:3])
+        return da, dw, db, dy if need[3] else None, None, None, None, None, None
 
 
 class _SplitQKV(torch.autograd.Function):
