@@ -50,6 +50,7 @@
  *   regtr_gemm_tn_any         KPConv.forward backward, weights (WF^T g) at widths regtr_gemm_tn refuses   kpconv_blocks.py:401-406
  *   regtr_instnorm_bwd        BatchNormBlock (InstanceNorm1d) + LeakyReLU + shortcut, backward   kpconv_blocks.py:497-519,556-561,741
  *   regtr_maxpool_argmax      max_pool: the index torch.max(dim) keeps for autograd   kpconv_blocks.py:142
+ *   regtr_maxpool_fwd_argmax  max_pool and that index in one pass over the rows               kpconv_blocks.py:127-143
  *   regtr_maxpool_gather_bwd  max_pool backward                   kpconv_blocks.py:127-143
  *   regtr_head_tail_bwd       CorrespondenceRegressor backward, the 3-wide and 1-wide output Linears   models/regtr.py:432-441
  *   regtr_bce_logits_bwd      nn.BCEWithLogitsLoss backward (the overlap loss)   models/regtr.py:250-257
@@ -582,6 +583,12 @@ int regtr_instnorm_bwd(const float* x, const int* seg_off, int n_clouds, int max
  * is -1.  Refused (REGTR_ERR_ARG, nothing launched): a negative count, H < 1, H > 32767, ld_nbr < H, C < 4 or not a multiple of 4,
  * NULLs with work to do, x not 16-byte or arg not 8-byte aligned. */
 int regtr_maxpool_argmax(const float* x, int ns, int C, const int* nbr, int ld_nbr, int nq, int H, short* arg, void* stream);
+
+/* regtr_maxpool_gather and regtr_maxpool_argmax in ONE pass over the rows (regtr_maxpool_argmax's thread mapping and loads): out [nq, C]
+ * bit-equal to regtr_maxpool_gather's for tables whose shadow entries are >= ns (the preprocessor's), arg [nq, C] equal to
+ * regtr_maxpool_argmax's.  nq = 0: nothing to do, REGTR_OK; ns = 0: out is all +0 and every arg is -1.  Refused (REGTR_ERR_ARG, nothing
+ * launched): regtr_maxpool_argmax's list, and out NULL or not 16-byte aligned. */
+int regtr_maxpool_fwd_argmax(const float* x, int ns, int C, const int* nbr, int ld_nbr, int nq, int H, float* out, short* arg, void* stream);
 
 /* Backward of regtr_maxpool_gather: from dy [nq, C] and arg [nq, C] (regtr_maxpool_argmax),
  *   dx[s, c] = sum over the entries e = q H + h of support s (row_off / entries of regtr_nbr_transpose(nbr, nq, H, ns)), ascending,

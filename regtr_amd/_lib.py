@@ -128,6 +128,7 @@ SIGNATURES = {
     'regtr_instnorm_bwd_ws_bytes': (_Z, [_I, _I, _I]),
     'regtr_instnorm_bwd': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _F, _P, _P, _P, _P, _Z, _P]),
     'regtr_maxpool_argmax': (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _P]),
+    'regtr_maxpool_fwd_argmax': (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
     'regtr_maxpool_gather_bwd': (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P, _P]),
     'regtr_head_tail_bwd_ws_bytes': (_Z, [_I, _I]),
     'regtr_head_tail_bwd': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),

@@ -14,9 +14,10 @@ activation's argument with the forward's own arithmetic, so every element's Leak
 
 max_pool is kpconv_blocks.py:127-143: the maximum over the rows a neighbour table lists, a zero shadow row for indices outside the
 supports.  Like torch.max(dim), the whole gradient of an output element goes to ONE row -- on equal values the lowest column of the
-table -- and none to the shadow row.  The forward stores that column per (query, channel) as int16 (ops.maxpool_argmax, one more pass
-over the rows: 2 bytes per output element instead of recomputing the maximum once per table entry in backward); the backward walks
-the table by support (ops.nbr_transpose) and adds, in ascending entry order, the gradients of the entries that won.
+table -- and none to the shadow row.  The forward stores that column per (query, channel) as int16 in the pass that takes the maximum
+(ops.maxpool_fwd_argmax: ops.maxpool's and ops.maxpool_argmax's results from one gather of the rows; 2 bytes per output element
+instead of recomputing the maximum once per table entry in backward); the backward walks the table by support (ops.nbr_transpose) and
+adds, in ascending entry order, the gradients of the entries that won.
 
 Both backward passes have one owner per output element, no atomics, and are bit-reproducible.  Nothing here synchronises.
 Refused: CPU tensors, double backward."""
@@ -70,12 +71,11 @@ def instance_norm(x, seg_off, max_len, residual=None, residual_normed=False, lre
 
 
 class _MaxPool(torch.autograd.Function):
-    """x (Ns, C) -> (Nq, C) by the ops.maxpool call of the plain path, plus the argmax launch."""
+    """x (Ns, C) -> (Nq, C), the bits of the plain path's ops.maxpool, and the winning columns from the same pass over the rows."""
 
     @staticmethod
     def forward(ctx, x, nbr, width, transposed):
-        out = ops.maxpool(x, nbr, width)
-        arg = ops.maxpool_argmax(x, nbr, width)
+        out, arg = ops.maxpool_fwd_argmax(x, nbr, width)
         ctx.save_for_backward(nbr, arg)
         ctx.ns, ctx.width, ctx.transposed = x.shape[0], width, transposed
         return out

@@ -226,6 +226,46 @@ __global__ void __launch_bounds__(256) k_maxpool_argmax(const float* __restrict_
     }
 }
 
+// k_maxpool_argmax and the forward's maximum in ONE pass over the rows: out[q, c] by regtr_maxpool_gather's own fmaxf chain over the same
+// values in the same column order (a repeated last column changes no maximum; a shadow reads as the zero row), arg[q, c] as above.
+__global__ void __launch_bounds__(256) k_maxpool_fwd_argmax(const float* __restrict__ x, int ns, int C, const int* __restrict__ nbr,
+                                                            int ld_nbr, int nq, int H, int lq_log2, float* __restrict__ out,
+                                                            short* __restrict__ arg)
+{
+    const int lane = rg_lane(), LQ = 1 << lq_log2;
+    const int q = ((rg_xcd_block(blockIdx.x, gridDim.x) * (blockDim.x >> 6) + (threadIdx.x >> 6)) << (6 - lq_log2)) + (lane >> lq_log2);
+    const int qc = q < nq ? q : nq - 1;              // a dead lane repeats the last query (it never stores)
+    const int* row = nbr + (size_t)qc * ld_nbr;
+    for (int c = (lane & (LQ - 1)) * 4; c < C; c += LQ * 4) {
+        float m[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};      // the winner under `>` (first column on ties)
+        float o[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};      // the forward's fmaxf chain
+        int a[4] = {-1, -1, -1, -1};
+        for (int h0 = 0; h0 < H; h0 += 8) {
+            int idx[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++) idx[u] = row[min(h0 + u, H - 1)];
+            float4 v[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++) v[u] = *(const float4*)(x + (size_t)min(max(idx[u], 0), ns - 1) * C + c);
+#pragma unroll
+            for (int u = 0; u < 8; u++) {
+                const bool real = (unsigned)idx[u] < (unsigned)ns;
+                const float w[4] = {real ? v[u].x : 0.f, real ? v[u].y : 0.f, real ? v[u].z : 0.f, real ? v[u].w : 0.f};
+                const int col = real ? min(h0 + u, H - 1) : -1;
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    o[j] = fmaxf(o[j], w[j]);
+                    if (w[j] > m[j]) { m[j] = w[j]; a[j] = col; }
+                }
+            }
+        }
+        if (q < nq) {
+            *(float4*)(out + (size_t)q * C + c) = make_float4(o[0], o[1], o[2], o[3]);
+            *(short4*)(arg + (size_t)q * C + c) = make_short4((short)a[0], (short)a[1], (short)a[2], (short)a[3]);
+        }
+    }
+}
+
 __global__ void __launch_bounds__(256) k_fill_i16(short* __restrict__ p, size_t n, short v)
 {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -338,6 +378,24 @@ int regtr_maxpool_argmax(const float* x, int ns, int C, const int* nbr, int ld_n
     } else {
         const int l = lanes_log2(C);
         k_maxpool_argmax<<<rg_xcd_grid(rg_cdiv(nq, 4 << (6 - l))), 256, 0, st>>>(x, ns, C, nbr, ld_nbr, nq, H, l, arg);
+    }
+    RG_RETURN_IF_LAUNCH_FAILED();
+    return RG_OK;
+}
+
+int regtr_maxpool_fwd_argmax(const float* x, int ns, int C, const int* nbr, int ld_nbr, int nq, int H, float* out, short* arg, void* stream)
+{
+    if (ns < 0 || nq < 0 || H < 1 || H > 32767 || ld_nbr < H || C < 4 || C % 4) return RG_ERR_ARG;
+    if (nq == 0) return RG_OK;
+    if (!nbr || !out || !arg || (ns > 0 && !x) || misaligned(x) || misaligned(out) || ((uintptr_t)arg % 8)) return RG_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (ns == 0) {                                            // no supports: every row is the zero shadow row
+        const size_t n = (size_t)nq * C;
+        if (hipMemsetAsync(out, 0, n * sizeof(float), st) != hipSuccess) return RG_ERR_LAUNCH;
+        k_fill_i16<<<rg_cdiv((long long)n, 256), 256, 0, st>>>(arg, n, (short)-1);
+    } else {
+        const int l = lanes_log2(C);
+        k_maxpool_fwd_argmax<<<rg_xcd_grid(rg_cdiv(nq, 4 << (6 - l))), 256, 0, st>>>(x, ns, C, nbr, ld_nbr, nq, H, l, out, arg);
     }
     RG_RETURN_IF_LAUNCH_FAILED();
     return RG_OK;

@@ -306,6 +306,12 @@ class UnaryBlock(nn.Module):
         y, st = self.linear(x, seg_off, max_len)
         return ops.instnorm_apply(y, seg_off, max_len, st, lrelu=not self.no_relu, out=y)
 
+    def forward_grad(self, x, seg_off, max_len):
+        """Linear -> InstanceNorm -> LeakyReLU as a differentiable call (regtr_amd/encoder_grad.py): .backward() fills mlp.weight.grad and
+        x.grad through HIP kernels.  The plain operators, not forward's GEMM-epilogue statistics: equal to forward within rounding."""
+        from .encoder_grad import unary_forward_grad
+        return unary_forward_grad(self, x, seg_off, max_len)
+
 
 class _LevelView:
     """What a block needs from kpconv_meta for its (possibly strided) convolution."""
@@ -349,6 +355,12 @@ class SimpleBlock(nn.Module):
                                          v.seg_post, v.max_post, xyzf=xyzf)
         y, st = self.KPConv(v.q_pts, v.s_pts, v.inds, x, want_stats=(v.seg_post, v.max_post), xyzf=xyzf)
         return ops.instnorm_apply(y, v.seg_post, v.max_post, st, lrelu=True, out=y)
+
+    def forward_grad(self, x, meta, tables=None, taps=None):
+        """forward(x, meta) as a differentiable call on the plain operators (regtr_amd/encoder_grad.py).  tables: the encoder_grad.Tables
+        of this step (None: this call's own); taps: a list that receives {'norms': [the InstanceNorm output], 'pools': []}."""
+        from .encoder_grad import simple_forward_grad
+        return simple_forward_grad(self, x, meta, tables, taps)
 
 
 class ResnetBottleneckBlock(nn.Module):
@@ -408,6 +420,13 @@ class ResnetBottleneckBlock(nn.Module):
         # LeakyReLU( IN(unary2) + [IN](shortcut) ) in one pass                                                :741
         return ops.instnorm_apply(y, v.seg_post, v.max_post, y_st, residual=shortcut, res_stats=sc_st, lrelu=True, out=y)
 
+    def forward_grad(self, features, meta, tables=None, taps=None):
+        """forward(features, meta) as a differentiable call on the plain operators (regtr_amd/encoder_grad.py).  tables: the
+        encoder_grad.Tables of this step (None: this call's own); taps: a list that receives {'norms': [the output of every InstanceNorm
+        call, in order: unary1's if there is one, the convolution's, the tail's], 'pools': [the max-pool's input if strided]}."""
+        from .encoder_grad import bottleneck_forward_grad
+        return bottleneck_forward_grad(self, features, meta, tables, taps)
+
 
 def block_decider(block_name, radius, in_dim, out_dim, layer_ind, config):
     """kpconv_blocks.py:429-471, restricted to the block types of the RegTR encoders."""
@@ -461,6 +480,15 @@ class KPFEncoder(nn.Module):
                 skip_x.append(x)
             x = block_op(x, batch)
         return x, skip_x
+
+    def forward_grad(self, x, meta, taps=None):
+        """The encoder as a differentiable call (regtr_amd/encoder_grad.py): every block through its forward_grad, the transposed
+        neighbour tables built once and shared -> the encoder output (N_coarse, C); .backward() fills every block weight's .grad
+        (kernel_points have requires_grad=False and get none).  The skip list feeds a decoder RegTR does not have and is not built.
+        The plain operators, not forward's fused routes: equal to forward within rounding, not bit for bit.  taps: a list that
+        receives one dict per block (the blocks' forward_grad); None keeps nothing extra alive."""
+        from .encoder_grad import encoder_forward_grad
+        return encoder_forward_grad(self, x, meta, taps)
 
     # ---- blocks [start, stop) through ONE C call (regtr_encoder_fwd, csrc/encoder.hip): the same launches in the same order, sequenced in C.
     # Small batches only (a pair or two per forward: the reference's own mode), where the host is the bound of an op-by-op forward.

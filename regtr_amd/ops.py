@@ -877,6 +877,21 @@ def maxpool_argmax(x, nbr, width=None, out=None):
     return arg
 
 
+def maxpool_fwd_argmax(x, nbr, width=None, out=None, out_arg=None):
+    """maxpool(x, nbr, width) and maxpool_argmax(x, nbr, width) from ONE pass over the rows (regtr_maxpool_fwd_argmax) -> (out (Nq, C)
+    float32, arg (Nq, C) int16), each bit-equal to the separate launch's.  out / out_arg: the buffers to write, or None for new ones."""
+    ns, C = x.shape
+    nq, ld = nbr.shape
+    res = torch.empty((nq, C), dtype=torch.float32, device=x.device) if out is None else out
+    arg = torch.empty((nq, C), dtype=torch.int16, device=x.device) if out_arg is None else out_arg
+    if tuple(res.shape) != (nq, C) or tuple(arg.shape) != (nq, C):
+        raise RuntimeError(f'maxpool_fwd_argmax: out and out_arg must be ({nq}, {C}), got {tuple(res.shape)}, {tuple(arg.shape)}')
+    check(_lib.lib().regtr_maxpool_fwd_argmax(ptr(x) if ns else None, ns, C, iptr(nbr) if nq else None, ld, nq, ld if width is None else int(width),
+                                              ptr(res) if nq else None, ptr(arg, torch.int16) if nq else None, stream()),
+          'regtr_maxpool_fwd_argmax')
+    return res, arg
+
+
 def maxpool_bwd(dy, arg, H, transposed, out=None):
     """Backward of maxpool (regtr_maxpool_gather_bwd): dy (Nq, C) the gradient of the pooled rows, arg = maxpool_argmax(...) of the same
     call, transposed = nbr_transpose(the (Nq, H) table the forward pooled through, Ns) -> dx (Ns, C).  out: the dx buffer, or None for a

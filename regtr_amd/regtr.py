@@ -6,8 +6,9 @@ batch['kpconv_meta'], output keys of regtr.py:218-235), same `state_dict` names 
 loads with `load_state_dict(state['state_dict'])` (demo.py:165).  `compute_loss(pred, batch)` gives the reference's validation /
 test losses (regtr.py:237-294) without gradients: the InfoNCE feature terms on regtr_infonce, the overlap and correspondence terms on
 regtr_loss_terms.  `training_step(batch)` trains everything above a frozen KPConv backbone (feat_proj, the cross-encoder, the
-correspondence head, the InfoNCE W) with HIP backward kernels: forward_grad / compute_loss_grad / trainable_parameters; the backbone's
-backward and an optimiser loop are not implemented.
+correspondence head, the InfoNCE W) with HIP backward kernels: forward_grad / compute_loss_grad / trainable_parameters;
+`training_step(batch, train_backbone=True)` also trains the 11 KPConv blocks (KPFEncoder.forward_grad, regtr_amd/encoder_grad.py) --
+every parameter the reference trains.  An optimiser loop is not implemented.
 
 The forward enqueues every stage on the current HIP stream with ONE host synchronisation (the data-dependent level
 sizes after preprocessing): preprocess -> KPConv encoder -> feat_proj -> 6 cross-encoder layers on packed tokens ->
@@ -326,13 +327,14 @@ class RegTR(nn.Module):
                              lambda _: torch.cat([torch.arange(B, 2 * B), torch.arange(0, B)]).to(torch.int32).to(dev))
         return kv_self, kv_cross
 
-    def _backbone(self, batch, dev, ev=None):
-        """preprocess (regtr.py:117-122) + KPConv encoder (regtr.py:136) -> (feats_un, kpconv_meta); sets batch['kpconv_meta']."""
+    def _backbone(self, batch, dev, ev=None, train=False):
+        """preprocess (regtr.py:117-122) + KPConv encoder (regtr.py:136) -> (feats_un, kpconv_meta); sets batch['kpconv_meta'].
+        train: the pyramid without gradient on ONE stream, the encoder through KPFEncoder.forward_grad inside autograd."""
         clouds = batch['src_xyz'] + batch['tgt_xyz']
         n0 = sum(int(p.shape[0]) for p in clouds)
         n_l0 = self.kpf_encoder.level0_blocks()
         two_streams = (overlap_preprocessing and n_l0 > 0 and not ev and not self.cfg.get('kpconv_ref_row_order', False))
-        if two_streams and n0 >= OVERLAP_MIN_POINTS:
+        if two_streams and n0 >= OVERLAP_MIN_POINTS and not train:
             # Large batches: the pyramid is built on a second HIP stream, and the level-0 blocks -- which need only level 0's conv
             # table and sizes the host already knows -- start on the main stream as soon as that table exists: the other 2.4 ms of
             # pyramid building (latency-bound small kernels) run under 6 ms of bandwidth-bound level-0 convolution.
@@ -356,13 +358,20 @@ class RegTR(nn.Module):
             batch['kpconv_meta'] = kpconv_meta
             feats_un, _ = self.kpf_encoder(x, kpconv_meta, n_l0, None, skips)
         else:
-            kpconv_meta = self.preprocessor(clouds)
+            if train:
+                with torch.no_grad():
+                    kpconv_meta = self.preprocessor(clouds)
+            else:
+                kpconv_meta = self.preprocessor(clouds)
             batch['kpconv_meta'] = kpconv_meta
             # (small batches -- a pair or two per forward -- run ONE stream: the level-0 blocks overlapped with pyramid levels 1-3 on a second
             #  stream, with the pyramid sequenced from C in two phases, measured 2.46 vs 2.38 ms per pair: docs/NEGATIVES.md, round 5)
             feats0 = self._ones(kpconv_meta['points'][0].shape[0], dev)
             if ev: ev[1].record()
-            feats_un, _ = self.kpf_encoder(feats0, kpconv_meta)
+            if train:
+                feats_un = self.kpf_encoder.forward_grad(feats0, kpconv_meta)
+            else:
+                feats_un, _ = self.kpf_encoder(feats0, kpconv_meta)
         return feats_un, kpconv_meta
 
     def _forward(self, batch, dev):
@@ -435,8 +444,8 @@ class RegTR(nn.Module):
         """The decoder layers a loss reads the head's outputs of: cfg.overlap_loss_on | cfg.corr_loss_on, ascending."""
         return sorted(set(self.cfg.overlap_loss_on) | set(self.cfg.corr_loss_on))
 
-    def forward_grad(self, batch, backbone_grad=False):
-        """forward(batch) as a differentiable call above a FROZEN backbone: the preprocessor and kpf_encoder run under torch.no_grad()
+    def forward_grad(self, batch, backbone_grad=False, train_backbone=False):
+        """forward(batch) as a differentiable call, by default above a FROZEN backbone: the preprocessor and kpf_encoder run under torch.no_grad()
         as in forward; feat_proj, the cross-encoder and the correspondence head run through head_grad.stack_forward_grad with a HIP
         backward, the head on the decoder layers of head_layers() only.  The arithmetic is that of forward's range fallback
         (compute_dtype 'fp32x3': six-term bf16 splits, float32's operand range), so there is no status word, no end-of-forward wait
@@ -447,7 +456,13 @@ class RegTR(nn.Module):
           * 'pose': (1, B, 3, 4), the LAST decoder layer's, computed without gradient (the reference's loss never reads it); absent
             when the last layer is not in head_layers().
         backbone_grad=True: feats_un, the backbone's output, becomes a leaf that requires grad and is returned as pred['_feats_un'];
-        its .grad after backward() is what a backbone backward starts from."""
+        its .grad after backward() is what a backbone backward starts from.
+        train_backbone=True: the preprocessor runs without gradient on one stream and the encoder through KPFEncoder.forward_grad
+        inside autograd, so backward() also fills the .grad of every kpf_encoder weight; pred['_feats_un'] is then the (non-leaf)
+        encoder output.  This pred is NOT bit-identical to the inference forward: KPFEncoder.forward_grad composes the plain operators,
+        whose InstanceNorm statistics come from a pass over the stored rows, where the fused inference routes take them from GEMM
+        epilogues and input moments -- the two agree within float32 rounding (docs/PARITY.md holds both to the same float64
+        restatement; tests/test_gpu_backbone_grads.py holds this pred to the bars forward is held to on the golden)."""
         from . import head_grad
         self._check_trainable('forward_grad')
         dev = batch['src_xyz'][0].device
@@ -459,10 +474,13 @@ class RegTR(nn.Module):
         B = len(batch['src_xyz'])
         layers = self.head_layers()
         with context.forward(dev, f16_pair=False, force_x3=True, status=None):
-            with torch.no_grad():
-                feats_un, meta = self._backbone(batch, dev)
-            if backbone_grad:
-                feats_un = feats_un.detach().requires_grad_()
+            if train_backbone:
+                feats_un, meta = self._backbone(batch, dev, train=True)
+            else:
+                with torch.no_grad():
+                    feats_un, meta = self._backbone(batch, dev)
+                if backbone_grad:
+                    feats_un = feats_un.detach().requires_grad_()
             slens_c = meta['_lens_host'][-1]
             xyz_c, seg_c = meta['points'][-1], meta['_seg_off'][-1]
             kv_self, kv_cross = self._kv_tables(B, dev)
@@ -493,7 +511,7 @@ class RegTR(nn.Module):
         }
         if pose is not None:
             pred['pose'] = pose
-        if backbone_grad:
+        if backbone_grad or train_backbone:
             pred['_feats_un'] = feats_un
         return pred
 
@@ -552,19 +570,25 @@ class RegTR(nn.Module):
         losses['total'] = torch.sum(torch.stack([losses[k] * wd[k] for k in losses]), dim=0)     # :292-293
         return losses
 
-    def trainable_parameters(self):
+    def trainable_parameters(self, backbone=False):
         """The parameters above the backbone -- feat_proj, the cross-encoder, the correspondence head and the two InfoNCE W -- as a
-        list.  Turns requires_grad on for the two W (they are created frozen, which inference keeps)."""
+        list.  Turns requires_grad on for the two W (they are created frozen, which inference keeps).  backbone=True: kpf_encoder's
+        weights as well (what training_step(train_backbone=True) fills); the kernel_points stay requires_grad=False and are not
+        listed."""
         mods = [self.feat_proj, self.transformer_encoder, self.correspondence_decoder, self.feature_criterion, self.feature_criterion_un]
         for crit in mods[3:]:
             crit.W.requires_grad_(True)
-        return [p for m in mods for p in m.parameters()]
+        params = [p for m in mods for p in m.parameters()]
+        if backbone:
+            params += [p for p in self.kpf_encoder.parameters() if p.requires_grad]
+        return params
 
-    def training_step(self, batch, batch_idx=None):
+    def training_step(self, batch, batch_idx=None, train_backbone=False):
         """generic_reg_model.py:64-66 of the reference: pred = forward_grad(batch), losses = compute_loss_grad(pred, batch) ->
-        (pred, losses); the caller runs losses['total'].backward() and steps its optimiser over trainable_parameters().  The backbone
-        is frozen: kpf_encoder's parameters end with grad None."""
-        pred = self.forward_grad(batch)
+        (pred, losses); the caller runs losses['total'].backward() and steps its optimiser over trainable_parameters().  By default
+        the backbone is frozen: kpf_encoder's parameters end with grad None.  train_backbone=True trains it too (forward_grad's
+        train_backbone; step over trainable_parameters(backbone=True))."""
+        pred = self.forward_grad(batch, train_backbone=train_backbone)
         return pred, self.compute_loss_grad(pred, batch)
 
     # ------------------------------------------------------------------------------------------ losses (validation / test, no gradients)

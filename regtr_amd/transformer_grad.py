@@ -61,8 +61,9 @@ class _LayerNorm(torch.autograd.Function):
 def linear_bwd(a, weight, cache, key, dy, h=None, need=(True, True, True), residual=None):
     """Backward of one Linear y = act(a W^T + b) of this module's kind, on float32 rows: dy (M, N) the gradient of its output, h the
     activation it stored after its ReLU (None: no ReLU, or dy already carries the mask) -> (da, dw, db) for need = (a, weight, bias).
-    residual (M, K): added to da inside the dX GEMM's epilogue (a gradient that reached `a` by another branch).  The caller holds the
-    launch context."""
+    residual (M, K): added to da inside the dX GEMM's epilogue (a gradient that reached `a` by another branch).  dW takes ops.gemm_tn
+    where both widths are multiples of 64 (every Linear of the cross-encoder and the head), ops.gemm_tn_any otherwise (the backbone's
+    32-wide unaries).  The caller holds the launch context."""
     da = dw = db = None
     g = dy
     if h is not None:
@@ -72,7 +73,8 @@ def linear_bwd(a, weight, cache, key, dy, h=None, need=(True, True, True), resid
     if need[0]:
         da = ops.gemm(g, _prepared(cache, key, weight, lambda w: ops.SplitWeight(w, 'kn')), planes=3, residual=residual)
     if need[1]:
-        dw = ops.gemm_tn(g, a)
+        tn = ops.gemm_tn if g.shape[1] % 64 == 0 and a.shape[1] % 64 == 0 else ops.gemm_tn_any
+        dw = tn(g, a)
     return da, dw, db if need[2] else None
 
 

@@ -7,7 +7,9 @@ Per level l of the 3DMatch encoder: InstanceNorm + LeakyReLU over the level's ro
 without a shortcut and with a normalised one; max-pool of those rows through the level's pooling table (levels 0-2).  Per line, medians
 of CUDA-event times after warm-up, one process: forward + backward (`hip_fwd_bwd_ms`; the pool's with the transposed table built once
 outside, `table_ms` beside it), the plain forward alone, the backward launches alone, and the torch formulation's forward + backward --
-or why it did not run (the gather materialises Nq x H x C floats).  No ratio here is a pass criterion."""
+or why it did not run (the gather materialises Nq x H x C floats).  The pool lines also time the differentiable forward's two launches
+(ops.maxpool + ops.maxpool_argmax) against the fused ops.maxpool_fwd_argmax, alternating, three rounds each.  No ratio here is a pass
+criterion."""
 import argparse
 import json
 import os
@@ -100,6 +102,14 @@ def main():
                        'hip_fwd_ms': timed(lambda: ops.maxpool(x, nbr, width)), 'argmax_ms': timed(lambda: ops.maxpool_argmax(x, nbr, width)),
                        'hip_bwd_ms': timed(lambda: ops.maxpool_bwd(gq, arg, H, table)),
                        'table_ms': timed(lambda: ops.nbr_transpose(nbr if width == nbr.shape[1] else nbr[:, :width].contiguous(), n))}
+                # the forward's two launches (ops.maxpool, ops.maxpool_argmax) against the one fused launch, alternating, three rounds: the
+                # spread between rounds is beside the difference
+                out_b, arg_b = torch.empty((nq, C), device=dev), torch.empty((nq, C), dtype=torch.int16, device=dev)
+                two, fused = [], []
+                for _ in range(3):
+                    two.append(timed(lambda: (ops.maxpool(x, nbr, width), ops.maxpool_argmax(x, nbr, width, out=arg_b))))
+                    fused.append(timed(lambda: ops.maxpool_fwd_argmax(x, nbr, width, out=out_b, out_arg=arg_b)))
+                rec['fwd_two_launches_ms'], rec['fwd_fused_ms'] = two, fused
             rec['hip_fwd_bwd_ms'] = timed(hip_pool)
             need_gb = nq * H * C * 4 / 1e9
             if need_gb > args.torch_max_gb:
