@@ -19,6 +19,7 @@
 //   num[q] = max(1, #{h : sum_c x[n_qh, c] > 0})            kpconv_blocks.py:409-411
 // which the GEMM epilogue divides by.
 #include "common.h"
+#include <type_traits>
 
 namespace {
 
@@ -253,6 +254,33 @@ typedef float rg_f32x2 __attribute__((ext_vector_type(2)));
 #ifndef RG_MG_WAVES_PER_EU
 #define RG_MG_WAVES_PER_EU 3
 #endif
+// Per-query neighbour-group count.  A table row is padded with shadows up to H: on the shipped workloads 31 of 40 slots are real (mean;
+// DESIGN.md par. 6) and the highest real slot ends 8.1 of the 10 groups.  A group behind it adds (+0) * (finite) to accumulators that
+// start at +0 and can therefore never be -0: leaving it out is the identity, bit for bit.  Each query runs through a body compiled for a
+// FIXED group count JJ -- the smallest offered value >= jn = ceil((highest real slot + 1) / 4) -- so every body stays branch free inside
+// (a guarded load becomes branch / load / vmcnt(0)).  Offered: J, J - STEP, ... (BODIES of them); a body is shadow-safe, so the smallest
+// one takes every lower count, jn = 0 (no real neighbour: WF rows of zeros, num 1) included.  The count comes from the HIGHEST real slot,
+// not the number of real slots: nothing assumes that shadows are a suffix of the row.
+// Measured on MI355X (64-pair tables, same process, alternating, bit-equal outputs; profiles/r07_gather_groups.md): level-0 convolution
+// 2050 us with the one fixed-J body, 1940 with bodies {J - 4, J - 2, J}, 1920 with every count 1 ... J, 1898 with the six J - 5 ... J kept
+// here (3 % of the rows need fewer: 0.818 of the groups run against 0.814); the gathers of a forward 6.56 -> 6.33 / 6.16 / 6.10 ms.
+#ifndef RG_MG_GROUP_STEP
+#define RG_MG_GROUP_STEP 1
+#endif
+#ifndef RG_MG_GROUP_BODIES
+#define RG_MG_GROUP_BODIES 6
+#endif
+// An instantiation that would lose a wave per SIMD to the extra bodies keeps the one fixed-J body.
+template <int J, int V, bool PRE> constexpr int rg_mg_bodies() { return RG_MG_GROUP_BODIES; }
+template <> constexpr int rg_mg_bodies<10, 2, false>() { return 1; }      // 94 -> 108 VGPRs: 5 -> 4 waves per SIMD
+template <int JJ, int JMIN, typename F>
+__device__ __forceinline__ void rg_for_group_count(int jn, F&& body)      // jn wave-uniform: scalar branches
+{
+    if constexpr (JJ - RG_MG_GROUP_STEP >= JMIN) {
+        if (jn <= JJ - RG_MG_GROUP_STEP) { rg_for_group_count<JJ - RG_MG_GROUP_STEP, JMIN>(jn, body); return; }
+    }
+    body(std::integral_constant<int, JJ>{});
+}
 // PRE: g.s_xyzf holds (x, y, z, positivity flag) records and the features are final (no InstanceNorm fold) -- the launcher's choice
 // when the caller passes `s_xyzf` and no x_stats.  Per neighbour ONE 16-byte load replaces three coordinate dwords (plus the flag):
 // PMC on the level-0 launch showed the texture-address path 76 % busy, 148 of ~260 lines per query being those scattered dwords,
@@ -332,25 +360,6 @@ __global__ void __launch_bounds__(GATHER_WAVES * RG_WAVE, RG_MG_WAVES_PER_EU) k_
             nb_s[lane] = make_float4(nb_cur.rx, nb_cur.ry, nb_cur.rz, __uint_as_float(ro));
         }
         __builtin_amdgcn_wave_barrier();
-        // ---- influences of kernel point k for neighbours h = 4 j + hh   (the A operands)
-        // (Measured, round 4: the same arithmetic on the packed-float32 instructions -- neighbour pairs interleaved in LDS, v_pk_add / v_pk_mul /
-        //  v_pk_fma, 75 instead of 120 vector instructions per query -- is bit-identical and NOT faster here: level 0 2118 vs 2114 us, level-0
-        //  pool 545 vs 520, level 1 594 vs 584; six more registers cost the Cin = 32 form a wave per SIMD.  This kernel is not bound by the
-        //  influence arithmetic; the Cin = 1 kernel below, which is nothing else, keeps the packed form.)
-        float w[J];
-        unsigned row[J];       // byte offset of the neighbour's feature row; RG_OOB for a shadow neighbour (reads as zeros)
-#pragma unroll
-        for (int j = 0; j < J; j++) {
-            const float4 nb = nb_s[4 * j + hh];
-            const float dx = nb.x - kx, dy = nb.y - ky, dz = nb.z - kz;
-            float d2;
-            {
-#pragma clang fp contract(off)
-                d2 = (dx * dx + dy * dy) + dz * dz;                                   // kpconv_blocks.py:326-329
-            }
-            w[j] = fmaxf(1.f - __builtin_amdgcn_sqrtf(d2) * inv_extent, 0.f);         // :368
-            row[j] = __float_as_uint(nb.w) + lane_off;
-        }
         const float2* st = nullptr;
         if (!PRE && g.x_stats) {
             // q is wave-uniform and the wave's queries are consecutive: the cloud changes at most rarely, and when it does
@@ -365,74 +374,101 @@ __global__ void __launch_bounds__(GATHER_WAVES * RG_WAVE, RG_MG_WAVES_PER_EU) k_
         Nb nb_nxt = nb_cur;
         int idx_nn = ns;
         const float f_cur = nb_cur.f;
-        float rsum[J];
+        // highest real slot of the row -> groups this query needs (lanes >= H hold ns)
+        const unsigned long long real = __ballot(idx_cur < ns);
+        const int jn = real ? (64 - __builtin_clzll(real) + 3) >> 2 : 0;
+        auto body = [&](auto jj) {
+            constexpr int JJ = decltype(jj)::value;
+            // ---- influences of kernel point k for neighbours h = 4 j + hh   (the A operands)
+            // (Measured, round 4: the same arithmetic on the packed-float32 instructions -- neighbour pairs interleaved in LDS, v_pk_add / v_pk_mul /
+            //  v_pk_fma, 75 instead of 120 vector instructions per query -- is bit-identical and NOT faster here: level 0 2118 vs 2114 us, level-0
+            //  pool 545 vs 520, level 1 594 vs 584; six more registers cost the Cin = 32 form a wave per SIMD.  This kernel is not bound by the
+            //  influence arithmetic; the Cin = 1 kernel below, which is nothing else, keeps the packed form.)
+            float w[JJ];
+            unsigned row[JJ];       // byte offset of the neighbour's feature row; RG_OOB for a shadow neighbour (reads as zeros)
 #pragma unroll
-        for (int j = 0; j < J; j++) rsum[j] = 0.f;
-        // ---- channel passes of 16 V channels
-#pragma unroll 1
-        for (int c0 = 0; c0 < Cin; c0 += 16 * V) {
-            const unsigned c0b = (unsigned)c0 * 4u;
-            vec xv[J];
-#pragma unroll
-            for (int j = 0; j < J; j++) xv[j] = rg_buf_load<V>(x_rs, row[j] + c0b);
-            if (c0 == 0) {   // prefetch for the next queries, queued behind this query's feature gathers
-                nb_nxt = load_nb(q + 1, idx_nxt);
-                idx_nn = load_idx(q + 2);
-            }
-            if (!PRE && st) {   // fused lrelu(InstanceNorm(x)) of the preceding UnaryBlock (wave-uniform branch)
-                float2 ms[V];
-#pragma unroll
-                for (int v = 0; v < V; v += 2) {
-                    const float4 t = *(const float4*)(st + c0 + V * k + v);
-                    ms[v] = make_float2(t.x, t.y); ms[v + 1] = make_float2(t.z, t.w);
+            for (int j = 0; j < JJ; j++) {
+                const float4 nb = nb_s[4 * j + hh];
+                const float dx = nb.x - kx, dy = nb.y - ky, dz = nb.z - kz;
+                float d2;
+                {
+#pragma clang fp contract(off)
+                    d2 = (dx * dx + dy * dy) + dz * dz;                                   // kpconv_blocks.py:326-329
                 }
+                w[j] = fmaxf(1.f - __builtin_amdgcn_sqrtf(d2) * inv_extent, 0.f);         // :368
+                row[j] = __float_as_uint(nb.w) + lane_off;
+            }
+            float rsum[JJ];
 #pragma unroll
-                for (int j = 0; j < J; j++)
+            for (int j = 0; j < JJ; j++) rsum[j] = 0.f;
+            // ---- channel passes of 16 V channels
+#pragma unroll 1
+            for (int c0 = 0; c0 < Cin; c0 += 16 * V) {
+                const unsigned c0b = (unsigned)c0 * 4u;
+                vec xv[JJ];
 #pragma unroll
-                    for (int v = 0; v < V; v++) {
-                        const float t = (rg_comp(xv[j], v) - ms[v].x) * ms[v].y;
-                        rg_set(xv[j], v, fmaxf(t, t * g.slope));          // LeakyReLU, 0 < slope < 1
+                for (int j = 0; j < JJ; j++) xv[j] = rg_buf_load<V>(x_rs, row[j] + c0b);
+                if (c0 == 0) {   // prefetch for the next queries, queued behind this query's feature gathers
+                    nb_nxt = load_nb(q + 1, idx_nxt);
+                    idx_nn = load_idx(q + 2);
+                }
+                if (!PRE && st) {   // fused lrelu(InstanceNorm(x)) of the preceding UnaryBlock (wave-uniform branch)
+                    float2 ms[V];
+#pragma unroll
+                    for (int v = 0; v < V; v += 2) {
+                        const float4 t = *(const float4*)(st + c0 + V * k + v);
+                        ms[v] = make_float2(t.x, t.y); ms[v + 1] = make_float2(t.z, t.w);
                     }
+#pragma unroll
+                    for (int j = 0; j < JJ; j++)
+#pragma unroll
+                        for (int v = 0; v < V; v++) {
+                            const float t = (rg_comp(xv[j], v) - ms[v].x) * ms[v].y;
+                            rg_set(xv[j], v, fmaxf(t, t * g.slope));          // LeakyReLU, 0 < slope < 1
+                        }
+                }
+                // A shadow neighbour's row needs no zeroing for WF: its influence w is exactly 0 (it sits 1e6 away).  Its row
+                // sum is discarded below.
+                if (!PRE)
+#pragma unroll
+                for (int j = 0; j < JJ; j++) {   // partial row sums for the normaliser (:409)
+                    float s = rg_comp(xv[j], 0);
+#pragma unroll
+                    for (int v = 1; v < V; v++) s += rg_comp(xv[j], v);
+                    rsum[j] += s;
+                }
+                floatx4 acc[V];
+#pragma unroll
+                for (int v = 0; v < V; v++) acc[v] = floatx4{0.f, 0.f, 0.f, 0.f};
+                // (the J dependent MFMAs of a channel slice as two independent accumulator chains, round 5: level-0 convolution 2170 us against
+                //  2136-2142 us, issue-stall share 67.0 % against 66.0 % -- the chain is not what the stalls wait for; profiles/r05_gather_chains.md)
+#pragma unroll
+                for (int j = 0; j < JJ; j++)
+#pragma unroll
+                    for (int v = 0; v < V; v++)
+                        acc[v] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[j], rg_comp(xv[j], v), acc[v], 0, 0, 0);
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    vec o;
+#pragma unroll
+                    for (int v = 0; v < V; v++) rg_set(o, v, acc[v][r]);
+                    rg_buf_store(wf_rs, st_off[r] + c0b, o);
+                }
             }
-            // A shadow neighbour's row needs no zeroing for WF: its influence w is exactly 0 (it sits 1e6 away).  Its row
-            // sum is discarded below.
-            if (!PRE)
+            // ---- normaliser: positive-row count over the query's real neighbours   (:409-411)
+            float cnt = 0.f;
+            if (PRE) {   // lanes = neighbours here (a lane beyond H or on a shadow neighbour loaded 0)
+                cnt = (float)__builtin_popcountll(__ballot(f_cur > 0.f));
+            } else {
 #pragma unroll
-            for (int j = 0; j < J; j++) {   // partial row sums for the normaliser (:409)
-                float s = rg_comp(xv[j], 0);
-#pragma unroll
-                for (int v = 1; v < V; v++) s += rg_comp(xv[j], v);
-                rsum[j] += s;
+                for (int j = 0; j < JJ; j++) cnt += (rg_row16_sum(rsum[j]) > 0.f && row[j] < RG_OOB) ? 1.f : 0.f;
+                cnt += __shfl_xor(cnt, 16, RG_WAVE);
+                cnt += __shfl_xor(cnt, 32, RG_WAVE);
             }
-            floatx4 acc[V];
-#pragma unroll
-            for (int v = 0; v < V; v++) acc[v] = floatx4{0.f, 0.f, 0.f, 0.f};
-            // (the J dependent MFMAs of a channel slice as two independent accumulator chains, round 5: level-0 convolution 2170 us against
-            //  2136-2142 us, issue-stall share 67.0 % against 66.0 % -- the chain is not what the stalls wait for; profiles/r05_gather_chains.md)
-#pragma unroll
-            for (int j = 0; j < J; j++)
-#pragma unroll
-                for (int v = 0; v < V; v++)
-                    acc[v] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[j], rg_comp(xv[j], v), acc[v], 0, 0, 0);
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                vec o;
-#pragma unroll
-                for (int v = 0; v < V; v++) rg_set(o, v, acc[v][r]);
-                rg_buf_store(wf_rs, st_off[r] + c0b, o);
-            }
-        }
-        // ---- normaliser: positive-row count over the query's real neighbours   (:409-411)
-        float cnt = 0.f;
-        if (PRE) {   // lanes = neighbours here (a lane beyond H or on a shadow neighbour loaded 0)
-            cnt = (float)__builtin_popcountll(__ballot(f_cur > 0.f));
-        } else {
-#pragma unroll
-            for (int j = 0; j < J; j++) cnt += (rg_row16_sum(rsum[j]) > 0.f && row[j] < RG_OOB) ? 1.f : 0.f;
-            cnt += __shfl_xor(cnt, 16, RG_WAVE);
-            cnt += __shfl_xor(cnt, 32, RG_WAVE);
-        }
-        if (lane == 0) g.num[q] = fmaxf(cnt, 1.f);
+            if (lane == 0) g.num[q] = fmaxf(cnt, 1.f);
+        };
+        constexpr int JMIN = J - (rg_mg_bodies<J, V, PRE>() - 1) * RG_MG_GROUP_STEP;
+        rg_for_group_count<J, (JMIN < 1 ? 1 : JMIN)>(jn, body);
         idx_cur = idx_nxt; nb_cur = nb_nxt; idx_nxt = idx_nn;
     }
 }
@@ -444,6 +480,17 @@ __global__ void __launch_bounds__(GATHER_WAVES * RG_WAVE, RG_MG_WAVES_PER_EU) k_
 //  gathered rows at ~15 B per clock and CU from L2 / Infinity Cache, and that is the limiter at Cin >= 64.  Removed after the
 //  measurement; numbers and phase clocks in profiles/r04_f16_gather_v2.md, docs/NEGATIVES.md.)
 
+
+// Wave-uniform maximum of a small non-negative int: four DPP rotate-max steps inside the 16-lane rows, then the four rows through SGPRs.
+__device__ __forceinline__ int rg_wave_max_uniform(int v)
+{
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x128, 0xf, 0xf, false));   // row_ror:8
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x124, 0xf, 0xf, false));   // row_ror:4
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x122, 0xf, 0xf, false));   // row_ror:2
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x121, 0xf, 0xf, false));   // row_ror:1
+    return max(max(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
+               max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
 
 // Cin == 1 (first encoder block, features = ones): no channel dimension to spread over lanes, so lanes are
 // (query, kernel point) pairs: 4 queries x 16 kernel points per wave, each lane walks its query's neighbours once and
@@ -461,6 +508,7 @@ __global__ void __launch_bounds__(GATHER_WAVES * RG_WAVE) k_kpconv_gather_c1(Gat
     float* pair_s = smem + (size_t)wave * QW * NPAIR * 10;
     const int q0 = (rg_xcd_block(blockIdx.x, gridDim.x) * GATHER_WAVES + wave) * QW;
     if (q0 >= g.nq) return;
+    int used = 0;      // slots up to the lane's highest real neighbour
     for (int e = lane; e < QW * HP; e += RG_WAVE) {
         const int qi = e / HP, h = e - qi * HP, q = q0 + qi;
         float rx = 1e6f, ry = 1e6f, rz = 1e6f, f = 0.f, x1 = 0.f;
@@ -468,6 +516,7 @@ __global__ void __launch_bounds__(GATHER_WAVES * RG_WAVE) k_kpconv_gather_c1(Gat
             const int idx = g.nbr[(size_t)q * H + h];
             float sx = 1e6f, sy = 1e6f, sz = 1e6f;
             if (idx < g.ns) {
+                used = max(used, h + 1);
                 if (g.s_xyzf) {   // (x, y, z, feature) in one 16-byte load
                     const float4 r = *(const float4*)(g.s_xyzf + 4 * (size_t)idx);
                     sx = r.x; sy = r.y; sz = r.z; x1 = r.w; f = x1 > 0.f ? 1.f : 0.f;
@@ -482,6 +531,9 @@ __global__ void __launch_bounds__(GATHER_WAVES * RG_WAVE) k_kpconv_gather_c1(Gat
         d[0] = rx; d[2] = ry; d[4] = rz; d[6] = x1; d[8] = f;
     }
     __builtin_amdgcn_wave_barrier();
+    // The walk below stops at the last pair that holds a real neighbour of ANY of the wave's four queries (the wave runs to its longest
+    // lane anyway): a shadow's influence and feature are +0, fmaf(+0, x, acc) and cnt += 0 are the identity.
+    const int npair = (rg_wave_max_uniform(used) + 1) >> 1;
     const int qi = lane >> 4, k = lane & 15, q = q0 + qi;
     if (q >= g.nq) return;
     const bool kvalid = k < g.KP;
@@ -490,7 +542,7 @@ __global__ void __launch_bounds__(GATHER_WAVES * RG_WAVE) k_kpconv_gather_c1(Gat
     const rg_f32x2 ninv{-inv_extent, -inv_extent}, one{1.f, 1.f};
     float acc = 0.f, cnt = 0.f;
     const float* pp = pair_s + qi * NPAIR * 10;
-    for (int p = 0; p < NPAIR; p++, pp += 10) {
+    for (int p = 0; p < npair; p++, pp += 10) {
         const rg_f32x2 dx = *(const rg_f32x2*)(pp) - kx, dy = *(const rg_f32x2*)(pp + 2) - ky, dz = *(const rg_f32x2*)(pp + 4) - kz;
         const rg_f32x2 xv = *(const rg_f32x2*)(pp + 6), fv = *(const rg_f32x2*)(pp + 8);
         rg_f32x2 d2;
@@ -553,11 +605,14 @@ __global__ void __launch_bounds__(GATHER_WAVES * RG_WAVE) k_kpconv_gather_c1p(Ga
             rec[s].qx = g.q_xyz[3 * qc]; rec[s].qy = g.q_xyz[3 * qc + 1]; rec[s].qz = g.q_xyz[3 * qc + 2];
         }
     };
-    auto stage = [&](float* buf, const int (&idx)[NS], const Rec (&rec)[NS]) {
+    // -> pairs of the group up to the last one that holds a real neighbour of any of its four queries (k_kpconv_gather_c1)
+    auto stage = [&](float* buf, const int (&idx)[NS], const Rec (&rec)[NS]) -> int {
+        int used = 0;
 #pragma unroll
         for (int s = 0; s < NS; s++) {
             if (e_q[s] < 0) continue;
             const bool elem = idx[s] >= 0, real = elem && idx[s] < ns;
+            used = real ? max(used, e_h[s] + 1) : used;
             // (as k_kpconv_gather_c1: a shadow neighbour sits at 1e6 - q, a pad slot at 1e6; both have influence 0 and feature 0)
             const float sx = real ? rec[s].r.x : 1e6f, sy = real ? rec[s].r.y : 1e6f, sz = real ? rec[s].r.z : 1e6f;
             const float x1 = real ? rec[s].r.w : 0.f;
@@ -565,6 +620,7 @@ __global__ void __launch_bounds__(GATHER_WAVES * RG_WAVE) k_kpconv_gather_c1p(Ga
             d[0] = elem ? sx - rec[s].qx : 1e6f; d[2] = elem ? sy - rec[s].qy : 1e6f; d[4] = elem ? sz - rec[s].qz : 1e6f;
             d[6] = x1; d[8] = x1 > 0.f ? 1.f : 0.f;
         }
+        return (rg_wave_max_uniform(used) + 1) >> 1;
     };
     const int qi = lane >> 4, k = lane & 15;
     const bool kvalid = k < g.KP;
@@ -577,7 +633,7 @@ __global__ void __launch_bounds__(GATHER_WAVES * RG_WAVE) k_kpconv_gather_c1p(Ga
     issue_idx(qbase, idx_a);
     issue_rec(qbase, idx_a, rec);
     issue_idx(qbase + QW, idx_b);
-    stage(buf_s, idx_a, rec);
+    int npair = stage(buf_s, idx_a, rec);
 #pragma unroll 1
     for (int gi = 0; gi < groups; gi++) {
         const int qg = qbase + gi * QW;
@@ -589,7 +645,7 @@ __global__ void __launch_bounds__(GATHER_WAVES * RG_WAVE) k_kpconv_gather_c1p(Ga
         const int q = qg + qi;
         const float* pp = buf_s + (gi & 1) * QW * NPAIR * 10 + qi * NPAIR * 10;
         float acc = 0.f, cnt = 0.f;
-        for (int p = 0; p < NPAIR; p++, pp += 10) {
+        for (int p = 0; p < npair; p++, pp += 10) {
             const rg_f32x2 dx = *(const rg_f32x2*)(pp) - kx, dy = *(const rg_f32x2*)(pp + 2) - ky, dz = *(const rg_f32x2*)(pp + 4) - kz;
             const rg_f32x2 xv = *(const rg_f32x2*)(pp + 6), fv = *(const rg_f32x2*)(pp + 8);
             rg_f32x2 d2;
@@ -608,7 +664,7 @@ __global__ void __launch_bounds__(GATHER_WAVES * RG_WAVE) k_kpconv_gather_c1p(Ga
             if (k == 0) g.num[q] = fmaxf(cnt, 1.f);
         }
         __builtin_amdgcn_wave_barrier();
-        stage(buf_s + ((gi + 1) & 1) * QW * NPAIR * 10, idx_b, rec);
+        npair = stage(buf_s + ((gi + 1) & 1) * QW * NPAIR * 10, idx_b, rec);
 #pragma unroll
         for (int s = 0; s < NS; s++) idx_b[s] = idx_c[s];
     }

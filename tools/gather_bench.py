@@ -23,6 +23,7 @@ def main():
     ap.add_argument('--debug', action='store_true')
     ap.add_argument('--xpat', default='', help='debug feature pattern: ones | chan | row')
     ap.add_argument('--levels', default='', help='comma list of level indices 0..6 to run')
+    ap.add_argument('--fill', action='store_true', help='print the table fill next to the times: mean real neighbours per row and mean neighbour groups (of ceil(H / 4)) up to the last real slot -- what the gathers skip')
     ap.add_argument('--against', default='', help='second build (libregtr_hip.<name>.so) to run on the same inputs: max relative WF difference')
     args = ap.parse_args()
     if args.pre:
@@ -80,6 +81,11 @@ def main():
         total += us
         print(f'layer {layer} {"pool" if strided else "conv"} Cin={Cin:3d} nq={nq:7d} ns={ns:7d}: {us:8.1f} us  {alg / us / 1e3:7.0f} GB/s alg '
               f'(+{nq * 15 * Cin * 4 / us / 1e3:5.0f} GB/s WF write)  chk={float(wf.sum()):.6e} {float(num.sum()):.1f}')
+        if args.fill:
+            real = nbr < ns
+            last = (real * torch.arange(1, H + 1, device=dev)).amax(1)      # highest real slot + 1
+            print(f'   fill: {float(real.sum(1).float().mean()):.1f} real of {H}, {float((real.sum(1) == H).float().mean()):.2f} of rows full, '
+                  f'{float(((last + 3) // 4).float().mean()):.2f} of {(H + 3) // 4} groups up to the last real slot')
         if L2 is not None:
             wf2 = torch.empty_like(wf); num2 = torch.empty_like(num)
             run(L2, wf2, num2)
