@@ -54,6 +54,10 @@
  *   regtr_maxpool_gather_bwd  max_pool backward                   kpconv_blocks.py:127-143
  *   regtr_head_tail_bwd       CorrespondenceRegressor backward, the 3-wide and 1-wide output Linears   models/regtr.py:432-441
  *   regtr_bce_logits_bwd      nn.BCEWithLogitsLoss backward (the overlap loss)   models/regtr.py:250-257
+ *   regtr_cloud_centroids +
+ *   regtr_augment_draws       RigidPerturb, RandomSwap (the decisions and the poses)   data_loaders/transforms.py:15-72,132-149
+ *   regtr_shuffle_keys +
+ *   regtr_augment_gather      RigidPerturb, Jitter, ShufflePoints, RandomSwap (the points and masks)   data_loaders/transforms.py:58-149
  */
 #ifndef REGTR_HIP_H
 #define REGTR_HIP_H
@@ -73,7 +77,7 @@ extern "C" {
  * regtr_kpconv_gather, regtr_instnorm_apply, regtr_mha_fwd, regtr_gemm_x3): a binding generated from another version of the header
  * would pass shifted arguments, so every binding must compare regtr_abi_version() with the REGTR_ABI_VERSION it was written against
  * before its first call (regtr_amd/_lib.py does).  Bumped on any signature change; a new entry point shifts nobody's
- * arguments and does not bump it. */
+ * arguments and does not bump it (the training-augmentation entry points were added at version 11). */
 #define REGTR_ABI_VERSION 11
 int regtr_abi_version(void);
 
@@ -626,6 +630,51 @@ int regtr_head_tail_bwd(const float* dcorr, const float* dlogit, const float* h2
  * float on the device.  The sigmoid is formed from exp(-|logit|) (no overflow, no cancellation for large |logit|).  n = 0: nothing to
  * do.  Refused: n < 0, NULLs with work to do. */
 int regtr_bce_logits_bwd(const float* logit, const float* target, const float* grad, int n, float* dlogit, void* stream);
+
+/* ---- training augmentation (regtr_amd/augment.py: RigidPerturb -> Jitter -> ShufflePoints -> RandomSwap on the device) --------------- */
+
+/* Random numbers of the four entries below: Philox4x32-10 with key = (seed & 0xffffffff, seed >> 32) and counter = (index, cloud_or_pair,
+ * purpose, step), purpose 0 pair draws / 1 shuffle keys / 2 jitter; a uniform is ((x >> 8) + 0.5) 2^-24 of one output word, a normal one
+ * half of a Box-Muller pair (words (x0, x1) and (x2, x3)).  csrc/augment.hip states which word feeds which decision.  Clouds are packed
+ * as 2 n_pairs slots: the src clouds of the pairs, then the tgt clouds. */
+
+/* out [n_clouds, 3] = the mean of every packed cloud's rows (xyz [n, 3], seg_off [n_clouds + 1]): float64 sums in a fixed order (one
+ * workgroup per cloud, a strided partial per lane, a fixed tree), rounded once to float32; bit-reproducible.  An empty cloud gives 0.
+ * Refused: a negative count, NULLs with work to do. */
+int regtr_cloud_centroids(const float* xyz, const int* seg_off, int n_clouds, int n, float* out, void* stream);
+
+/* One thread per pair b: the random decisions of RigidPerturb and RandomSwap and what follows from them.
+ *   perturb_mode 0 none: P = identity, perturb_source = 0.
+ *                1 small: axis uniform on the sphere, angle = N(0,1) perturb_std pi / sqrt(3), Rodrigues; translation N(0,1)^3 perturb_std /
+ *                  sqrt(3); then P <- C^-1 P C, C = translate(-centroid) of the perturbed INPUT cloud (centroids [2 n_pairs, 3]).
+ *                2 large: zyx Euler angles uniform in (0, 2 pi), zero translation.
+ *   perturb_source = u > 0.5 (the src cloud takes P, else the tgt cloud);  swap = (swap argument != 0) and u > 0.5.
+ *   pose_out [n_pairs, 3, 4] = pose o P^-1 (source perturbed) or P o pose (target perturbed), then inverted when swapped.
+ *   xform [2 n_pairs, 3, 4]: P for the perturbed input cloud slot, the identity for the other;  flags [n_pairs, 2] = perturb_source, swap.
+ * P is formed in float64 and rounded once to float32; every composition after that is float32 rounded per operation with sums taken
+ * left to right.  pose: pose_stride 12 (3x4) or 16 (4x4) floats per pair, rows 0-2 read.  Refused: a negative count, another
+ * pose_stride or perturb_mode, a negative or NaN perturb_std in mode 1, NULLs with work to do (centroids only in mode 1). */
+int regtr_augment_draws(const float* pose, int pose_stride, const float* centroids, int n_pairs, unsigned long long seed,
+                        unsigned int step, int perturb_mode, float perturb_std, int swap, float* xform, float* pose_out, int* flags,
+                        void* stream);
+
+/* keys [n] int64: (cloud_slot << 32) | word x0 of counter (row within the cloud, cloud_slot, 1, step), for every row of the packed
+ * clouds (seg_off [n_clouds + 1], seg_off[n_clouds] = n).  Their stable ascending sort is the shuffle: cloud c's segment of the sorted
+ * row indices is a permutation of its rows.  Refused: a negative count, NULLs with work to do. */
+int regtr_shuffle_keys(const int* seg_off, int n_clouds, int n, unsigned long long seed, unsigned int step, long long* keys,
+                       void* stream);
+
+/* The one pass over the points.  Output row j of output cloud slot c' (out_off [n_clouds + 1], out_off[n_clouds] = n_out) reads input
+ * row perm[in_off[c] + j] of the input cloud slot c = in_slot[c'] (perm [n_in] int64: global input rows, a permutation within every
+ * cloud; NULL: the identity, i.e. the cloud's leading rows), applies xform[c] (3x4, rounded per operation as regtr_se3_transform;
+ * xform NULL: no transform, the point is copied) and adds noise z with z three normals of counter (j, c', 2, step) (float32 Box-Muller
+ * with the accurate logf / log1pf / sincosf; noise == 0 adds nothing, so -0 stays -0).  out_xyz [n_out, 3]; out_mask [n_out] (optional)
+ * = mask[input row].  Rows and slots are clamped to their cloud, so no table can make a read leave the arrays; the caller keeps
+ * out_off[c' + 1] - out_off[c'] <= the length of input cloud in_slot[c'].  Refused: a negative count, n_out > n_in, a NaN noise, NULLs
+ * with work to do, out_mask without mask. */
+int regtr_augment_gather(const float* xyz, const unsigned char* mask, const int* in_off, int n_in, const long long* perm,
+                         const int* out_off, const int* in_slot, int n_clouds, int n_out, const float* xform, float noise,
+                         unsigned long long seed, unsigned int step, float* out_xyz, unsigned char* out_mask, void* stream);
 
 #ifdef __cplusplus
 }

@@ -21,6 +21,8 @@ _P = _c.c_void_p
 _I = _c.c_int
 _F = _c.c_float
 _Z = _c.c_size_t
+_U64 = _c.c_uint64
+_U32 = _c.c_uint32
 
 class Weight(_c.Structure):
     """regtr_weight_t (include/regtr_hip.h)."""
@@ -133,6 +135,10 @@ SIGNATURES = {
     'regtr_head_tail_bwd_ws_bytes': (_Z, [_I, _I]),
     'regtr_head_tail_bwd': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     'regtr_bce_logits_bwd': (_I, [_P, _P, _P, _I, _P, _P]),
+    'regtr_cloud_centroids': (_I, [_P, _P, _I, _I, _P, _P]),
+    'regtr_augment_draws': (_I, [_P, _I, _P, _I, _U64, _U32, _I, _F, _I, _P, _P, _P, _P]),
+    'regtr_shuffle_keys': (_I, [_P, _I, _I, _U64, _U32, _P, _P]),
+    'regtr_augment_gather': (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _F, _U64, _U32, _P, _P, _P]),
 }
 
 COMPOSITE = ('regtr_encoder_fwd', 'regtr_cross_encoder_fwd')      # bound through a GIL-releasing handle (see _load)

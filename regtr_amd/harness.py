@@ -580,6 +580,39 @@ def pose_errors(pred, gt):
     return np.degrees(np.arccos(tr)), np.linalg.norm(pred[:, :, 3] - gt[:, :, 3], axis=1)
 
 
+# ------------------------------------------------------------------------------------------------------ training input
+def train_batches(source, cfg, batch_size, seed, epochs=1, device=None, num_workers=4, loader_pool=None):
+    """Generator of augmented training batches over a 3DMatch-style pair source (`source[i]` -> {'src_xyz', 'tgt_xyz', 'pose', 'idx'}:
+    ThreeDMatchPairs, SyntheticPairs): the loader pool, pinned staging and side-stream H2D copy run_test reads its pairs through, then
+    augment.train_batch on the resident raw clouds -- overlap masks of the clean pair, the reference's augmentation chain -- with
+    `step` counting up from 0 across epochs, so batch k of a run is a function of (source, seed, k) alone.  Every epoch visits every pair
+    once in an order drawn from (seed, epoch); a last short batch is yielded as it is.  loader_pool: a LoaderPool over `source` made by the
+    caller (e.g. before the GPU was initialised); else one of num_workers processes is made here and closed at the end (0: one loader
+    thread).  Each batch goes straight into RegTR.training_step; 'ids' names its pairs."""
+    from .augment import train_batch
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    pool = loader_pool
+    if pool is None and num_workers > 0:
+        pool = LoaderPool(source, device, workers=num_workers, max_batch=batch_size)
+    step = 0
+    try:
+        for epoch in range(int(epochs)):
+            order = np.random.default_rng([int(seed) & ((1 << 64) - 1), epoch]).permutation(len(source)).tolist()
+            loader = pool.iterate(order, batch_size) if pool is not None else Prefetcher(source, order, batch_size, device)
+            for b in loader:
+                gp = b['gt_pose'] if 'gt_pose' in b else [i_['pose'] for i_ in b['items']]
+                if any(g_ is None for g_ in gp):
+                    raise RuntimeError('train_batches: the pair source gives no ground-truth pose')
+                pose = torch.from_numpy(np.stack([np.asarray(g_, dtype=np.float32)[:3] for g_ in gp])).to(device, non_blocking=True)
+                out = train_batch(b['src_xyz'], b['tgt_xyz'], pose, cfg, seed, step)
+                out['ids'] = b['ids'] if 'ids' in b else [i_['idx'] for i_ in b['items']]
+                step += 1
+                yield out
+    finally:
+        if pool is not None and loader_pool is None:
+            pool.close()
+
+
 # ------------------------------------------------------------------------------------------------------ the test loop
 def run_test(model, pairs, batch, device, logger=None, max_pairs=None, num_workers=0, loader_pool=None, losses=False):
     """Runs every pair of `pairs` (this rank's shard) through the model, B at a time.  loader_pool: a LoaderPool over `pairs` (loader

@@ -971,3 +971,54 @@ def bce_logits_bwd(logit, gt, grad):
     check(_lib.lib().regtr_bce_logits_bwd(ptr(logit) if n else None, ptr(gt) if n else None, ptr(grad.reshape(1)), n,
                                           ptr(out) if n else None, stream()), 'regtr_bce_logits_bwd')
     return out
+
+
+# ------------------------------------------------------------------------------------------------ training augmentation (csrc/augment.hip)
+PERTURB_MODES = {'none': 0, 'small': 1, 'large': 2}
+_U64 = (1 << 64) - 1
+
+
+def cloud_centroids(xyz, seg_off):
+    """xyz (N, 3) packed clouds (seg_off (C+1,) int32) -> (C, 3): per-cloud means, float64 sums in a fixed order (regtr_cloud_centroids)."""
+    n, C = xyz.shape[0], seg_off.numel() - 1
+    out = torch.empty((C, 3), dtype=torch.float32, device=xyz.device)
+    check(_lib.lib().regtr_cloud_centroids(ptr(xyz) if n else None, iptr(seg_off), C, n, ptr(out), stream()), 'regtr_cloud_centroids')
+    return out
+
+
+def augment_draws(pose, centroids, seed, step, perturb_mode='small', perturb_std=0.1, swap=True):
+    """The per-pair decisions of RigidPerturb / RandomSwap (regtr_augment_draws): pose (B, 3, 4) or (B, 4, 4), centroids (2B, 3) of the
+    input clouds (src slots, then tgt slots; read in mode 'small' only) -> (xform (2B, 3, 4), pose_out (B, 3, 4), flags (B, 2) int32:
+    perturb_source, swap)."""
+    B = pose.shape[0]
+    pose = pose.contiguous()
+    dev = pose.device
+    xform = torch.empty((2 * B, 3, 4), dtype=torch.float32, device=dev)
+    pose_out = torch.empty((B, 3, 4), dtype=torch.float32, device=dev)
+    flags = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    check(_lib.lib().regtr_augment_draws(ptr(pose), pose.shape[-2] * pose.shape[-1], ptr(centroids), B, int(seed) & _U64,
+                                         int(step) & 0xffffffff, PERTURB_MODES[perturb_mode], float(perturb_std), int(bool(swap)),
+                                         ptr(xform), ptr(pose_out), iptr(flags), stream()), 'regtr_augment_draws')
+    return xform, pose_out, flags
+
+
+def shuffle_keys(seg_off, n, seed, step):
+    """One int64 sort key per row of packed clouds, (cloud_slot << 32) | philox word (regtr_shuffle_keys); torch.sort(stable=True) of it
+    is the shuffle."""
+    keys = torch.empty(n, dtype=torch.int64, device=seg_off.device)
+    check(_lib.lib().regtr_shuffle_keys(iptr(seg_off), seg_off.numel() - 1, n, int(seed) & _U64, int(step) & 0xffffffff,
+                                        ptr(keys, torch.int64) if n else None, stream()), 'regtr_shuffle_keys')
+    return keys
+
+
+def augment_gather(xyz, mask, in_off, perm, out_off, in_slot, n_out, xform, noise, seed, step):
+    """The one pass over the points (regtr_augment_gather): xyz (N, 3), mask (N,) uint8 or None, in_off / out_off (C+1,) int32, perm (N,)
+    int64 or None, in_slot (C,) int32, xform (C, 3, 4) or None -> (out_xyz (n_out, 3), out_mask (n_out,) uint8 or None)."""
+    n_in, C = xyz.shape[0], in_off.numel() - 1
+    out = torch.empty((n_out, 3), dtype=torch.float32, device=xyz.device)
+    out_mask = None if mask is None else torch.empty(n_out, dtype=torch.uint8, device=xyz.device)
+    check(_lib.lib().regtr_augment_gather(ptr(xyz) if n_in else None, bptr(mask), iptr(in_off), n_in, ptr(perm, torch.int64),
+                                          iptr(out_off), iptr(in_slot), C, int(n_out), ptr(xform), float(noise), int(seed) & _U64,
+                                          int(step) & 0xffffffff, ptr(out) if n_out else None, bptr(out_mask) if n_out else None,
+                                          stream()), 'regtr_augment_gather')
+    return out, out_mask
