@@ -58,6 +58,10 @@
  *   regtr_augment_draws       RigidPerturb, RandomSwap (the decisions and the poses)   data_loaders/transforms.py:15-72,132-149
  *   regtr_shuffle_keys +
  *   regtr_augment_gather      RigidPerturb, Jitter, ShufflePoints, RandomSwap (the points and masks)   data_loaders/transforms.py:58-149
+ *   regtr_modelnet_draws      uniform_2_sphere, RandomTransformSE3_euler (the decisions and the pose)   data_loaders/modelnet_transforms.py:18-43,316-355
+ *   regtr_crop_select         RandomCrop.crop (a per-cloud percentile by radix select)   data_loaders/modelnet_transforms.py:188-200
+ *   regtr_modelnet_keys +
+ *   regtr_modelnet_gather     Resampler, RandomJitter, ShufflePoints, the crop's overlap masks   data_loaders/modelnet_transforms.py:63-173,219-228,374-397
  */
 #ifndef REGTR_HIP_H
 #define REGTR_HIP_H
@@ -77,7 +81,7 @@ extern "C" {
  * regtr_kpconv_gather, regtr_instnorm_apply, regtr_mha_fwd, regtr_gemm_x3): a binding generated from another version of the header
  * would pass shifted arguments, so every binding must compare regtr_abi_version() with the REGTR_ABI_VERSION it was written against
  * before its first call (regtr_amd/_lib.py does).  Bumped on any signature change; a new entry point shifts nobody's
- * arguments and does not bump it (the training-augmentation entry points were added at version 11). */
+ * arguments and does not bump it (the training-augmentation entry points, 3DMatch's and ModelNet's, were added at version 11). */
 #define REGTR_ABI_VERSION 11
 int regtr_abi_version(void);
 
@@ -675,6 +679,59 @@ int regtr_shuffle_keys(const int* seg_off, int n_clouds, int n, unsigned long lo
 int regtr_augment_gather(const float* xyz, const unsigned char* mask, const int* in_off, int n_in, const long long* perm,
                          const int* out_off, const int* in_slot, int n_clouds, int n_out, const float* xform, float noise,
                          unsigned long long seed, unsigned int step, float* out_xyz, unsigned char* out_mask, void* stream);
+
+/* ---- ModelNet training augmentation (regtr_amd/augment.py: modelnet_train_batch; csrc/augment_modelnet.hip) ------------------------- */
+
+/* The chain SplitSourceRef -> RandomCrop -> RandomTransformSE3_euler -> Resampler -> RandomJitter -> ShufflePoints of
+ * data_loaders/modelnet.py:102-109 on n_clouds packed raw clouds (xyz [n_raw, 3], raw_off [n_clouds + 1]).  2 n_clouds SLOTS: slot b is
+ * the source copy of raw cloud b, slot n_clouds + b its reference copy; slot_off [2 n_clouds + 1] are the exclusive offsets of the slots'
+ * raw rows (slot s has the rows of cloud s mod n_clouds; slot_off[2 n_clouds] = n_slot_rows = 2 n_raw).  Random numbers: the Philox
+ * convention above with purposes 3-7; csrc/augment_modelnet.hip states which word feeds which decision. */
+
+/* One thread per raw cloud b.  dirs [2 n_clouds, 3]: the crop direction of every slot, uniform on the sphere (float64 trigonometry, rounded
+ * to float32).  xform [n_clouds, 3, 4]: R = Rx Ry Rz of three angles u pi rot_mag / 180, t uniform in +-trans_mag, formed in float64 and
+ * rounded once to float32; pose [n_clouds, 3, 4] = its inverse [R^T | -R^T t] in float32 rounded per operation.  Refused: a negative
+ * count, a NaN magnitude, NULLs with work to do. */
+int regtr_modelnet_draws(int n_clouds, unsigned long long seed, unsigned int step, double rot_mag, double trans_mag, float* dirs,
+                         float* xform, float* pose, void* stream);
+
+/* The largest cloud whose distance keys regtr_crop_select keeps resident in LDS (host only). */
+int regtr_crop_select_lds_points(void);
+
+/* RandomCrop.crop of every slot, one workgroup per slot: centroid [2 n_clouds, 3] (float64 sums in a fixed order, rounded once to
+ * float32), distance of a row = float64 dot product of its float32 centred point with the float32 direction dirs[slot] (sums left to
+ * right, no contraction; -0 counts as +0), thr [2 n_clouds] (float64) = numpy's linear-interpolation percentile of the distances:
+ * with a <= b the order statistics of 0-based ranks sel_lo[slot] and sel_lo[slot] + 1 and t = sel_t[slot], a + (b - a) t for t < 0.5
+ * and b - (b - a)(1 - t) otherwise (sel_lo, sel_t: functions of n and p_keep alone, from the host).  keep [n_slot_rows] = distance > thr,
+ * strictly; count [2 n_clouds] the rows kept.  A slot that would keep nothing keeps every row instead and gets flag [2 n_clouds] = 1.
+ * The order statistics come from an 8-bit radix select on the order-preserving 64-bit keys of the distances, resident in LDS for a cloud
+ * of at most min(max_len, regtr_crop_select_lds_points()) rows and recomputed from xyz in every digit pass for a larger one (max_len: the
+ * caller's bound on the clouds' lengths; it sizes the LDS and may be wrong without harm).  Bit-reproducible.  A slot whose offsets are
+ * not this layout gets count 0 and no other write.  Refused: a negative count, NULLs with work to do. */
+int regtr_crop_select(const float* xyz, const int* raw_off, int n_raw, int n_clouds, int max_len, const float* dirs, const int* sel_lo,
+                      const double* sel_t, const int* slot_off, int n_slot_rows, float* centroid, double* thr, int* count, int* flag,
+                      unsigned char* keep, void* stream);
+
+/* keys [n_slot_rows + n_slots k_out] int64, two families in one array for ONE stable ascending sort:
+ *   raw row r of slot s (index slot_off[s] + r):        (s << 32) | (!keep << 31) | (x0 of counter (r, s, 4, step) >> 1)
+ *   pre-shuffle output row i of slot s (index n_slot_rows + s k_out + i):   ((n_slots + s) << 32) | x0 of counter (i, s, 6, step)
+ * Sorted, slot s's first segment lists its kept rows first, in uniform random order (Resampler); its second segment is ShufflePoints'
+ * permutation of its k_out output rows.  Refused: a negative count, 2^31 keys or more, NULLs with work to do. */
+int regtr_modelnet_keys(const int* slot_off, int n_slots, int n_slot_rows, int k_out, const unsigned char* keep, unsigned long long seed,
+                        unsigned int step, long long* keys, void* stream);
+
+/* The one pass over the 2 n_clouds k_out output rows.  Final row j of slot s reads pre-shuffle row i = perm[n_slot_rows + s k_out + j]
+ * (perm: the sorted keys' indices, int64); pre-shuffle row i reads sorted kept row q = i for i < m = count[s], else x0 of counter
+ * (i, s, 5, step) mod m (a pick with replacement); that is raw row r = perm[slot_off[s] + q] - slot_off[s] of the slot's cloud.  Source
+ * slots go through xform[s] (3x4, rounded per operation as regtr_se3_transform), then every row gains
+ * clip(scale z, -clip, clip) with z three normals of counter (j, s, 7, step) (scale == 0 adds nothing).  out_xyz [2 n_clouds k_out, 3];
+ * out_mask = keep[raw row r of the OTHER slot of the same cloud] (the ground-truth overlap); out_row = r.  Rows and slots are clamped to
+ * their cloud, so no table can make a read leave the arrays.  A slot whose offsets are not this layout (the condition under which
+ * regtr_crop_select writes count 0) gets zero points, a zero mask and out_row = -1 in all its rows.  Refused: a negative count, a NaN
+ * scale, a negative or NaN clip, 2^31 rows or more, NULLs with work to do. */
+int regtr_modelnet_gather(const float* xyz, const int* raw_off, int n_raw, int n_clouds, const int* slot_off, int n_slot_rows, int k_out,
+                          const long long* perm, const int* count, const unsigned char* keep, const float* xform, float scale, float clip,
+                          unsigned long long seed, unsigned int step, float* out_xyz, unsigned char* out_mask, int* out_row, void* stream);
 
 #ifdef __cplusplus
 }

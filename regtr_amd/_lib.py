@@ -139,6 +139,11 @@ SIGNATURES = {
     'regtr_augment_draws': (_I, [_P, _I, _P, _I, _U64, _U32, _I, _F, _I, _P, _P, _P, _P]),
     'regtr_shuffle_keys': (_I, [_P, _I, _I, _U64, _U32, _P, _P]),
     'regtr_augment_gather': (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _F, _U64, _U32, _P, _P, _P]),
+    'regtr_modelnet_draws': (_I, [_I, _U64, _U32, _c.c_double, _c.c_double, _P, _P, _P, _P]),
+    'regtr_crop_select_lds_points': (_I, []),
+    'regtr_crop_select': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    'regtr_modelnet_keys': (_I, [_P, _I, _I, _I, _P, _U64, _U32, _P, _P]),
+    'regtr_modelnet_gather': (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _F, _F, _U64, _U32, _P, _P, _P, _P]),
 }
 
 COMPOSITE = ('regtr_encoder_fwd', 'regtr_cross_encoder_fwd')      # bound through a GIL-releasing handle (see _load)

@@ -19,7 +19,8 @@ Five launches and one radix sort per batch: centroids, pair draws, shuffle keys,
 Nothing synchronises: the output lengths min(n, max_pts) depend on the swap decision, which the host takes from the same Philox words
 (`swap_flags`) instead of reading the device's flags back.
 
-Not built here: the ModelNet chain (RandomCrop needs a per-cloud quantile), the `correspondences` key (no loss reads it), an optimiser.
+The ModelNet chain (data_loaders/modelnet.py:102-109) is `modelnet_train_batch` below (csrc/augment_modelnet.hip, purposes 3-7 of the same
+Philox convention).  Not built here: the `correspondences` key (no loss reads it), an optimiser.
 Refused: CPU tensors, empty clouds, clouds that are not (n, 3), masks that do not match their cloud.
 """
 import numpy as np
@@ -139,3 +140,108 @@ def train_batch(src_list, tgt_list, poses, cfg, seed, step):
     batch['pose'] = poses
     batch['src_overlap'], batch['tgt_overlap'] = compute_overlap_masks(batch['src_xyz'], batch['tgt_xyz'], poses, cfg.overlap_radius)
     return augment_batch(batch, seed, step, augment_noise=cfg.get('augment_noise', 0.005), perturb_pose=cfg.get('perturb_pose', 'small'))
+
+
+# ---------------------------------------------------------------------------------------------------------------- the ModelNet chain
+MODELNET_RESAMPLE = 717      # modelnet_transforms.py:92-93: both sizes, whatever num_points says, with a two-element `partial`
+_quantile_cache = {}
+
+
+def crop_quantile(n, p_keep):
+    """np.percentile's position for RandomCrop.crop (modelnet_transforms.py:198) in a cloud of n points: (lo, t) with the threshold
+    lerp(sorted[lo], sorted[lo + 1], t).  The reference's p_keep is a float32 (:186), so q = (1 - float32(p)) 100 is a float32 (30.000002
+    for 0.7), and where numpy rounds on the way to the virtual index (n - 1) q / 100 is numpy's business: the position is read off
+    np.percentile itself: lo from the ramp 0..n-1 (the answer there is lo + t), t from the step that is 0 up to rank lo and 1 above it (the
+    answer there is lerp(0, 1, t) = t, exactly, in both branches of numpy's lerp)."""
+    key = (int(n), float(np.float32(p_keep)))
+    if key not in _quantile_cache:
+        q = (np.float32(1.0) - np.float32(p_keep)) * np.float32(100)
+        ramp = np.arange(int(n), dtype=np.float64)
+        lo = min(int(np.floor(np.percentile(ramp, q))), int(n) - 2)
+        _quantile_cache[key] = (lo, float(np.percentile((ramp > lo).astype(np.float64), q)))
+    return _quantile_cache[key]
+
+
+def _check_modelnet_cfg(cfg):
+    noise_type = cfg.get('noise_type', 'crop')
+    if noise_type != 'crop':
+        raise NotImplementedError(f"modelnet_train_batch: noise_type {noise_type!r} is not built (only 'crop', the value modelnet.yaml uses)")
+    partial = cfg.get('partial', [0.7, 0.7])
+    if not isinstance(partial, (list, tuple)) or len(partial) != 2:
+        raise NotImplementedError(f'modelnet_train_batch: partial {partial!r} is not built (only a two-element list, as in modelnet.yaml)')
+    p = float(partial[0])                                   # :216-217: both clouds use p_keep[0]
+    if not 0.0 < p < 1.0 or np.float32(p) == np.float32(0.5):
+        raise NotImplementedError(f'modelnet_train_batch: partial[0] = {partial[0]!r} is not built (a proportion in (0, 1) other than 0.5, '
+                                  'which the reference crops at the plane through the centroid instead of at a percentile)')
+    if int(cfg.get('num_points', 1024)) < 1:
+        raise RuntimeError(f"modelnet_train_batch: num_points must be positive, got {cfg.get('num_points')}")
+    return p, float(cfg.get('rot_mag', 45.0)), float(cfg.get('trans_mag', 0.5))
+
+
+def modelnet_train_batch(points, cfg, seed, step, *, jitter_scale=0.01, jitter_clip=0.05):
+    """One ModelNet training batch from B resident raw clouds (csrc/augment_modelnet.hip): the chain data_loaders/modelnet.py:102-109
+    composes for noise_type `crop` (data_loaders/modelnet_transforms.py),
+        SplitSourceRef -> RandomCrop(partial) -> RandomTransformSE3_euler(rot_mag, trans_mag) -> Resampler(num_points) -> RandomJitter
+        -> ShufflePoints
+    with the ground-truth overlap masks the crop itself defines (:219-228: a source point overlaps iff the reference's crop kept the same
+    raw point, and the other way round; no radius search).  The result goes straight into RegTR.training_step.
+
+    points: list (B) of device float32 (n_b, 3) clouds, n_b >= 2, of any lengths.  cfg keys read: partial, num_points, rot_mag, trans_mag,
+    noise_type (the reference's defaults when absent).  -> 'src_xyz', 'tgt_xyz', 'src_overlap', 'tgt_overlap' (lists (B) of views into
+    packed outputs, every cloud MODELNET_RESAMPLE = 717 rows: the reference's Resampler sets both sizes to 717 with a two-element
+    `partial`, :92-93, whatever num_points says, so no length has to be read back), 'pose' (B, 3, 4), and '_augment' = {'dirs' (2B, 3)
+    float32 crop directions and 'centroid' (2B, 3) per slot (source slots, then reference slots), 'thr' (2B,) float64, 'count' (2B,)
+    int32 kept rows, 'flag' (2B,) int32, 'keep' (list (2B) of bool masks over the raw rows), 'rows' (2B, 717) int32: the raw row of
+    every output row, 'perm' the stable sort's indices (resample order of every slot's raw rows, then the shuffle of every slot's output
+    rows), 'xform' (B, 3, 4) the source's transform, 'slot_off' (host)}.
+
+    Random numbers: the Philox convention above with purposes 3-7 (csrc/augment_modelnet.hip states which word feeds which decision;
+    tests/modelnet_augment_ref.py restates it).  Five launches and one radix sort: draws, crop select, keys, torch.sort(stable=True),
+    gather.  Bit-reproducible, no floating-point atomics, no host wait.
+
+    A crop that keeps nothing (possible only when every distance from the percentile's rank up ties at the maximum, e.g. coincident
+    points) makes the reference raise inside np.random.choice (:127); the device cannot raise without a read-back, so it keeps the whole
+    cloud and sets the slot's 'flag'.
+
+    Not built: `correspondences`, `corr_xyz`, `tgt_raw` (no loss reads them); the test-time transforms (they re-seed numpy's generator per
+    item); a one-element `partial`, partial[0] = 0.5 and noise_type other than `crop` (NotImplementedError naming the value).  The
+    reference's own `clean` and `jitter` training chains cannot run under its dataset class: ModelNetHdf.__getitem__
+    (data_loaders/modelnet.py:179-180) and Resampler (:111-112) read `src_overlap` / `ref_overlap`, which only RandomCrop writes.
+    Refused: CPU tensors, empty clouds, clouds that are not (n, 3) float32, n < 2."""
+    p_keep, rot_mag, trans_mag = _check_modelnet_cfg(cfg)
+    points = list(points)
+    if not points:
+        raise RuntimeError('modelnet_train_batch: points must be a non-empty list of clouds')
+    for b, c in enumerate(points):
+        if not isinstance(c, torch.Tensor) or c.device.type != 'cuda':
+            raise RuntimeError(f'modelnet_train_batch: points[{b}] must be a GPU tensor (got {getattr(c, "device", type(c))}); there is no CPU fallback')
+        if c.dim() != 2 or c.shape[1] != 3 or c.dtype is not torch.float32:
+            raise RuntimeError(f'modelnet_train_batch: points[{b}] must be a float32 (n, 3) cloud, got {c.dtype} {tuple(c.shape)}')
+        if c.shape[0] == 0:
+            raise RuntimeError(f'modelnet_train_batch: points[{b}] is empty; an empty cloud has no centroid and no crop')
+        if c.shape[0] < 2:
+            raise RuntimeError(f'modelnet_train_batch: points[{b}] has {c.shape[0]} point; the percentile of the crop needs n >= 2')
+    B, k = len(points), MODELNET_RESAMPLE
+    dev = points[0].device
+    lens = [int(c.shape[0]) for c in points]
+    raw_off = np.concatenate([[0], np.cumsum(lens)])
+    slot_off = np.concatenate([[0], np.cumsum(lens + lens)])
+    n_raw, n_slot_rows = int(raw_off[-1]), int(slot_off[-1])
+    if n_slot_rows + 2 * B * k >= 2 ** 31:
+        raise RuntimeError(f'modelnet_train_batch: {n_slot_rows + 2 * B * k} sort keys exceed the int32 row index')
+    sel = [crop_quantile(n, p_keep) for n in lens]
+    with _lib.on_device(dev):
+        meta = torch.from_numpy(np.concatenate([raw_off, slot_off, [s[0] for s in sel] * 2]).astype(np.int32)).to(dev, non_blocking=True)
+        d_raw_off, d_slot_off, d_lo = meta[:B + 1], meta[B + 1:3 * B + 2], meta[3 * B + 2:]
+        d_t = torch.from_numpy(np.array([s[1] for s in sel] * 2, dtype=np.float64)).to(dev, non_blocking=True)
+        xyz = torch.cat(points, dim=0)
+        dirs, xform, pose = ops.modelnet_draws(B, seed, step, rot_mag, trans_mag, dev)
+        centroid, thr, count, flag, keep = ops.crop_select(xyz, d_raw_off, max(lens), dirs, d_lo, d_t, d_slot_off, n_slot_rows)
+        perm = torch.sort(ops.modelnet_keys(d_slot_off, n_slot_rows, k, keep, seed, step), stable=True)[1]
+        out, out_mask, rows = ops.modelnet_gather(xyz, d_raw_off, d_slot_off, n_slot_rows, k, perm, count, keep, xform, jitter_scale,
+                                                  jitter_clip, seed, step)
+    xs, ms = list(out.view(2 * B, k, 3).unbind(0)), list(out_mask.view(torch.bool).view(2 * B, k).unbind(0))
+    return {'src_xyz': xs[:B], 'tgt_xyz': xs[B:], 'pose': pose, 'src_overlap': ms[:B], 'tgt_overlap': ms[B:],
+            '_augment': {'dirs': dirs, 'centroid': centroid, 'thr': thr, 'count': count, 'flag': flag,
+                         'keep': list(torch.split(keep.view(torch.bool), lens + lens)), 'rows': rows.view(2 * B, k), 'perm': perm,
+                         'xform': xform, 'slot_off': [int(v) for v in slot_off]}}

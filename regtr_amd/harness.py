@@ -613,6 +613,32 @@ def train_batches(source, cfg, batch_size, seed, epochs=1, device=None, num_work
             pool.close()
 
 
+def modelnet_train_batches(source, cfg, batch_size, seed, epochs=1, device=None):
+    """Generator of ModelNet training batches over any indexable source of (n, 3) arrays (`source[i]`; further columns such as ModelNet40's
+    normals are dropped, data_loaders/modelnet.py:176-177): the clouds of a batch go to the device in one pinned copy, then
+    augment.modelnet_train_batch builds the cropped, moved, resampled, jittered and shuffled pairs with their masks and pose there.
+    `step` counts up from 0 across epochs, so batch k of a run is a function of (source, seed, k) alone.  Every epoch visits every cloud
+    once in an order drawn from (seed, epoch); a last short batch is yielded as it is.  Each batch goes straight into
+    RegTR.training_step; 'ids' names its clouds.  (A 2048-point cloud is 24 KB: there is nothing for a loader pool to hide.  No HDF5
+    reader here: hand in the arrays.)"""
+    from .augment import modelnet_train_batch
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    step = 0
+    for epoch in range(int(epochs)):
+        order = np.random.default_rng([int(seed) & ((1 << 64) - 1), epoch]).permutation(len(source)).tolist()
+        for lo in range(0, len(order), int(batch_size)):
+            ids = order[lo:lo + int(batch_size)]
+            clouds = [np.ascontiguousarray(np.asarray(source[i], dtype=np.float32)[:, :3]) for i in ids]
+            lens = [len(c) for c in clouds]
+            flat = torch.from_numpy(np.concatenate(clouds, axis=0))
+            if device.type == 'cuda':
+                flat = flat.pin_memory()
+            out = modelnet_train_batch(list(torch.split(flat.to(device, non_blocking=True), lens)), cfg, seed, step)
+            out['ids'] = ids
+            step += 1
+            yield out
+
+
 # ------------------------------------------------------------------------------------------------------ the test loop
 def run_test(model, pairs, batch, device, logger=None, max_pairs=None, num_workers=0, loader_pool=None, losses=False):
     """Runs every pair of `pairs` (this rank's shard) through the model, B at a time.  loader_pool: a LoaderPool over `pairs` (loader

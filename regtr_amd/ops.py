@@ -1022,3 +1022,62 @@ def augment_gather(xyz, mask, in_off, perm, out_off, in_slot, n_out, xform, nois
                                           int(step) & 0xffffffff, ptr(out) if n_out else None, bptr(out_mask) if n_out else None,
                                           stream()), 'regtr_augment_gather')
     return out, out_mask
+
+
+# ------------------------------------------------------------------------------------------------ ModelNet training augmentation (csrc/augment_modelnet.hip)
+def modelnet_draws(n_clouds, seed, step, rot_mag, trans_mag, device):
+    """The per-cloud decisions of RandomCrop's directions and RandomTransformSE3_euler (regtr_modelnet_draws) -> (dirs (2B, 3): the crop
+    direction of every slot (source slots, then reference slots), xform (B, 3, 4), pose (B, 3, 4) = xform^-1)."""
+    dirs = torch.empty((2 * n_clouds, 3), dtype=torch.float32, device=device)
+    xform = torch.empty((n_clouds, 3, 4), dtype=torch.float32, device=device)
+    pose = torch.empty((n_clouds, 3, 4), dtype=torch.float32, device=device)
+    check(_lib.lib().regtr_modelnet_draws(n_clouds, int(seed) & _U64, int(step) & 0xffffffff, float(rot_mag), float(trans_mag), ptr(dirs),
+                                          ptr(xform), ptr(pose), stream()), 'regtr_modelnet_draws')
+    return dirs, xform, pose
+
+
+def crop_select_lds_points():
+    """The largest cloud whose distance keys regtr_crop_select keeps in LDS; a larger one re-reads global memory per digit pass."""
+    return int(_lib.lib().regtr_crop_select_lds_points())
+
+
+def crop_select(xyz, raw_off, max_len, dirs, sel_lo, sel_t, slot_off, n_slot_rows):
+    """RandomCrop.crop of every slot (regtr_crop_select): xyz (N, 3) packed raw clouds (raw_off (B+1,) int32), dirs (2B, 3), sel_lo (2B,)
+    int32 / sel_t (2B,) float64 the percentile's lower rank and interpolation weight, slot_off (2B+1,) int32 -> (centroid (2B, 3),
+    thr (2B,) float64, count (2B,) int32, flag (2B,) int32, keep (n_slot_rows,) uint8)."""
+    B = raw_off.numel() - 1
+    dev = xyz.device
+    centroid = torch.empty((2 * B, 3), dtype=torch.float32, device=dev)
+    thr = torch.empty(2 * B, dtype=torch.float64, device=dev)
+    count = torch.empty(2 * B, dtype=torch.int32, device=dev)
+    flag = torch.empty(2 * B, dtype=torch.int32, device=dev)
+    keep = torch.empty(n_slot_rows, dtype=torch.uint8, device=dev)
+    check(_lib.lib().regtr_crop_select(ptr(xyz), iptr(raw_off), xyz.shape[0], B, int(max_len), ptr(dirs), iptr(sel_lo), _lib.dptr(sel_t),
+                                       iptr(slot_off), int(n_slot_rows), ptr(centroid), _lib.dptr(thr), iptr(count), iptr(flag),
+                                       bptr(keep), stream()), 'regtr_crop_select')
+    return centroid, thr, count, flag, keep
+
+
+def modelnet_keys(slot_off, n_slot_rows, k_out, keep, seed, step):
+    """The resample keys of every slot's raw rows and the shuffle keys of its k_out output rows in one int64 array
+    (regtr_modelnet_keys); torch.sort(stable=True) of it is both orders."""
+    n_slots = slot_off.numel() - 1
+    keys = torch.empty(n_slot_rows + n_slots * k_out, dtype=torch.int64, device=slot_off.device)
+    check(_lib.lib().regtr_modelnet_keys(iptr(slot_off), n_slots, int(n_slot_rows), int(k_out), bptr(keep), int(seed) & _U64,
+                                         int(step) & 0xffffffff, ptr(keys, torch.int64), stream()), 'regtr_modelnet_keys')
+    return keys
+
+
+def modelnet_gather(xyz, raw_off, slot_off, n_slot_rows, k_out, perm, count, keep, xform, scale, clip, seed, step):
+    """The one pass over the output rows (regtr_modelnet_gather) -> (out_xyz (2B k_out, 3), out_mask (2B k_out,) uint8, out_row
+    (2B k_out,) int32: the raw row every output row came from)."""
+    B = raw_off.numel() - 1
+    n_out = 2 * B * k_out
+    out = torch.empty((n_out, 3), dtype=torch.float32, device=xyz.device)
+    out_mask = torch.empty(n_out, dtype=torch.uint8, device=xyz.device)
+    out_row = torch.empty(n_out, dtype=torch.int32, device=xyz.device)
+    check(_lib.lib().regtr_modelnet_gather(ptr(xyz), iptr(raw_off), xyz.shape[0], B, iptr(slot_off), int(n_slot_rows), int(k_out),
+                                           ptr(perm, torch.int64), iptr(count), bptr(keep), ptr(xform), float(scale), float(clip),
+                                           int(seed) & _U64, int(step) & 0xffffffff, ptr(out), bptr(out_mask), iptr(out_row), stream()),
+          'regtr_modelnet_gather')
+    return out, out_mask, out_row
