@@ -62,6 +62,9 @@
  *   regtr_crop_select         RandomCrop.crop (a per-cloud percentile by radix select)   data_loaders/modelnet_transforms.py:188-200
  *   regtr_modelnet_keys +
  *   regtr_modelnet_gather     Resampler, RandomJitter, ShufflePoints, the crop's overlap masks   data_loaders/modelnet_transforms.py:63-173,219-228,374-397
+ *   regtr_nearest +
+ *   regtr_segment_mean        the modified Chamfer distance (nearest neighbours, per-cloud means)   benchmark/benchmark_modelnet.py:69-76
+ *   regtr_pose_metrics        se3_compare; the RPMNet / DCP pose metrics   utils/se3_torch.py:93-105, benchmark/benchmark_modelnet.py:51-67
  */
 #ifndef REGTR_HIP_H
 #define REGTR_HIP_H
@@ -732,6 +735,39 @@ int regtr_modelnet_keys(const int* slot_off, int n_slots, int n_slot_rows, int k
 int regtr_modelnet_gather(const float* xyz, const int* raw_off, int n_raw, int n_clouds, const int* slot_off, int n_slot_rows, int k_out,
                           const long long* perm, const int* count, const unsigned char* keep, const float* xform, float scale, float clip,
                           unsigned long long seed, unsigned int step, float* out_xyz, unsigned char* out_mask, int* out_row, void* stream);
+
+/* ---- validation / test metrics (regtr_amd/metrics.py; csrc/metrics.hip) --------------------------------------------------------------
+ * New entry points only: no existing signature changes, REGTR_ABI_VERSION stays as it is. */
+
+/* Supports per LDS tile of regtr_nearest (host only): a longer support cloud is scanned in several tiles. */
+int regtr_nearest_lds_points(void);
+
+/* For every query point the nearest point of the support cloud of the same index, over n_clouds packed ragged clouds: q_xyz [n_q, 3]
+ * with q_off [n_clouds + 1], s_xyz [n_s, 3] with s_off [n_clouds + 1]; q_pose / s_pose [n_clouds, 12] (row-major 3x4, optional): the
+ * transform applied to cloud c's queries / supports first, ((r0 x + r1 y) + r2 z) + t per row.  d2 [n_q] = (dx dx + dy dy) + dz dz with
+ * d = q - s, float32 rounded per operation, no contraction; idx [n_q] (optional) the support's index within its cloud.  The minimum is
+ * taken by a strict < over the supports in ascending index: the lowest index wins a tie and a NaN distance never wins; a query with no
+ * candidate below +inf (an empty support cloud, every distance NaN or +inf) gets d2 = +inf and idx = -1.  max_q_len: the longest query
+ * cloud (it sizes the grid; queries beyond it are not written).  Bit-reproducible.  Offsets are clamped to the arrays.  Refused: a
+ * negative count, more than 65535 clouds, NULLs with work to do. */
+int regtr_nearest(const float* q_xyz, const int* q_off, int n_q, const float* s_xyz, const int* s_off, int n_s, int n_clouds,
+                  int max_q_len, const float* q_pose, const float* s_pose, float* d2, int* idx, void* stream);
+
+/* out [n_clouds] (float64) = the mean of every packed segment of v [n] (off [n_clouds + 1]): float64 sums in a fixed order (one
+ * workgroup per cloud, a strided partial per lane, a fixed tree), as regtr_cloud_centroids; bit-reproducible.  An empty segment gives
+ * 0.  Refused: a negative count, NULLs with work to do. */
+int regtr_segment_mean(const float* v, const int* off, int n_clouds, int n, double* out, void* stream);
+
+/* Registration errors of n_layers x n_pairs predicted poses pred [n_layers n_pairs, 12] against gt [n_pairs, gt_stride] (gt_stride 12
+ * or 16 floats per pair, rows 0-2 read), one thread per (layer, pair), in float64 with sums left to right.  out [n_layers n_pairs, 8]:
+ *   0 rot_err_deg, 1 trans_err of pred o gt^-1 (the reference's se3_compare: || t_p - R_p R_g^T t_g ||)
+ *   2 err_r_deg,   3 err_t     of gt^-1 o pred (ModelNet: || R_g^T (t_p - t_g) ||)
+ *   4 t_mse, 5 t_mae over the translation's components;  6 r_mse, 7 r_mae over the extrinsic-xyz Euler angles in degrees,
+ *     a = atan2(R21, R22), b = -asin(clamp(R20)), c = atan2(R10, R00) (at gimbal lock finite, but not scipy's convention).
+ * composed [n_layers n_pairs, 12] = pred o gt^-1 rounded to float32.  Refused: a negative count, another gt_stride, NULLs with work to
+ * do. */
+int regtr_pose_metrics(const float* pred, const float* gt, int gt_stride, int n_layers, int n_pairs, double* out, float* composed,
+                       void* stream);
 
 #ifdef __cplusplus
 }

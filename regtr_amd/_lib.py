@@ -144,6 +144,10 @@ SIGNATURES = {
     'regtr_crop_select': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     'regtr_modelnet_keys': (_I, [_P, _I, _I, _I, _P, _U64, _U32, _P, _P]),
     'regtr_modelnet_gather': (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _F, _F, _U64, _U32, _P, _P, _P, _P]),
+    'regtr_nearest_lds_points': (_I, []),
+    'regtr_nearest': (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    'regtr_segment_mean': (_I, [_P, _P, _I, _I, _P, _P]),
+    'regtr_pose_metrics': (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
 }
 
 COMPOSITE = ('regtr_encoder_fwd', 'regtr_cross_encoder_fwd')      # bound through a GIL-releasing handle (see _load)

@@ -1081,3 +1081,100 @@ def modelnet_gather(xyz, raw_off, slot_off, n_slot_rows, k_out, perm, count, kee
                                            int(seed) & _U64, int(step) & 0xffffffff, ptr(out), bptr(out_mask), iptr(out_row), stream()),
           'regtr_modelnet_gather')
     return out, out_mask, out_row
+
+
+# ------------------------------------------------------------------------------------------------ validation / test metrics (csrc/metrics.hip)
+NEAREST_QUERY_TILE = 768      # queries per workgroup of regtr_nearest (NR_QTILE in csrc/metrics.hip; tests straddle it)
+
+
+def nearest_lds_points():
+    """Supports per LDS tile of regtr_nearest; a longer support cloud is scanned in several tiles."""
+    return int(_lib.lib().regtr_nearest_lds_points())
+
+
+def _host_offsets(off, n, what):
+    """Exclusive offsets given on the HOST (a sequence, numpy array or CPU tensor: the lengths of packed clouds are known there) as a list
+    of ints, checked: they start at 0, never decrease and end at n."""
+    if isinstance(off, torch.Tensor):
+        if off.device.type != 'cpu':
+            raise RuntimeError(f'{what}: offsets are host data (a sequence or a CPU tensor), got a tensor on {off.device}')
+        off = off.tolist()
+    off = [int(o) for o in off]
+    if len(off) < 1 or off[0] != 0 or off[-1] != n or any(b < a for a, b in zip(off, off[1:])):
+        raise RuntimeError(f'{what}: offsets must run from 0 to {n} without decreasing, got {off[:4]} ... {off[-1:]} ({len(off)} entries)')
+    return off
+
+
+def _check_cloud(t, what):
+    if not isinstance(t, torch.Tensor) or t.device.type != 'cuda':
+        raise RuntimeError(f'{what} must be a GPU tensor (got {getattr(t, "device", type(t))}); there is no CPU fallback')
+    if t.dtype is not torch.float32 or t.dim() != 2 or t.shape[1] != 3:
+        raise RuntimeError(f'{what} must be a float32 (n, 3) cloud, got {t.dtype} {tuple(t.shape)}')
+    return t.contiguous()
+
+
+def _pose12(pose, C, what):
+    """(C, 3, 4) / (C, 4, 4) / (C, 12) float32 device poses -> contiguous (C, 12), or None."""
+    if pose is None:
+        return None
+    if pose.device.type != 'cuda' or pose.dtype is not torch.float32:
+        raise RuntimeError(f'{what} must be a float32 GPU tensor, got {pose.dtype} on {pose.device}')
+    if pose.dim() == 3 and pose.shape[1:] in ((3, 4), (4, 4)):
+        pose = pose[:, :3, :].reshape(pose.shape[0], 12)
+    if pose.dim() != 2 or tuple(pose.shape) != (C, 12):
+        raise RuntimeError(f'{what} must hold one 3x4 transform per cloud ({C}), got {tuple(pose.shape)}')
+    return pose.contiguous()
+
+
+def nearest(q_xyz, q_off, s_xyz, s_off, q_pose=None, s_pose=None, return_idx=True, return_offsets=False):
+    """For every query point the nearest point of the support cloud of the same index (regtr_nearest): q_xyz (Nq, 3), s_xyz (Ns, 3) packed
+    ragged clouds, q_off / s_off their (C+1) exclusive offsets on the HOST, q_pose / s_pose optional (C, 3, 4) transforms applied first
+    -> (d2 (Nq,) float32, idx (Nq,) int32 within the support cloud, or None).  Float32 rounded per operation, lowest index on ties, NaN
+    never chosen.  return_offsets: also the (2, C+1) int32 device tensor of q_off and s_off this call uploaded (one copy for both), for
+    the caller's next launch over the same clouds.  Refused: CPU tensors, clouds that are not float32 (n, 3), offset vectors of different lengths, an empty support cloud."""
+    q_xyz, s_xyz = _check_cloud(q_xyz, 'nearest: q_xyz'), _check_cloud(s_xyz, 'nearest: s_xyz')
+    nq, ns = q_xyz.shape[0], s_xyz.shape[0]
+    qo, so = _host_offsets(q_off, nq, 'nearest: q_off'), _host_offsets(s_off, ns, 'nearest: s_off')
+    if len(qo) != len(so):
+        raise RuntimeError(f'nearest: q_off and s_off must describe the same number of clouds, got {len(qo) - 1} and {len(so) - 1}')
+    C = len(qo) - 1
+    empty = [c for c in range(C) if so[c + 1] == so[c]]
+    if empty:
+        raise RuntimeError(f'nearest: support cloud(s) {empty[:4]} are empty; a query has no nearest point in an empty cloud')
+    dev = q_xyz.device
+    q_pose, s_pose = _pose12(q_pose, C, 'nearest: q_pose'), _pose12(s_pose, C, 'nearest: s_pose')
+    offs = torch.tensor([qo, so], dtype=torch.int32).to(dev, non_blocking=True)
+    d2 = torch.empty(nq, dtype=torch.float32, device=dev)
+    idx = torch.empty(nq, dtype=torch.int32, device=dev) if return_idx else None
+    max_q = max((b - a for a, b in zip(qo, qo[1:])), default=0)
+    check(_lib.lib().regtr_nearest(ptr(q_xyz) if nq else None, iptr(offs[0]), nq, ptr(s_xyz) if ns else None, iptr(offs[1]), ns, C, max_q,
+                                   ptr(q_pose), ptr(s_pose), ptr(d2) if nq else None, iptr(idx) if nq else None, stream()), 'regtr_nearest')
+    return (d2, idx, offs) if return_offsets else (d2, idx)
+
+
+def segment_mean(v, off):
+    """v (N,) float32, off (C+1,) int32 device offsets -> (C,) float64 per-segment means, float64 sums in a fixed order
+    (regtr_segment_mean); an empty segment gives 0."""
+    n, C = v.numel(), off.numel() - 1
+    out = torch.empty(max(C, 0), dtype=torch.float64, device=v.device)
+    check(_lib.lib().regtr_segment_mean(ptr(v) if n else None, iptr(off), C, n, _lib.dptr(out) if C > 0 else None, stream()),
+          'regtr_segment_mean')
+    return out
+
+
+def pose_metrics(pred, gt):
+    """pred (L, B, 3, 4) or (B, 3, 4) float32, gt (B, 3, 4) or (B, 4, 4) float32 -> (out (L, B, 8) float64: rot_err_deg, trans_err (of
+    pred o gt^-1, the reference's se3_compare), err_r_deg, err_t (of gt^-1 o pred), t_mse, t_mae, r_mse, r_mae; composed (L, B, 3, 4)
+    float32 = pred o gt^-1) (regtr_pose_metrics).  With a (B, 3, 4) pred the results lose the leading dimension."""
+    layered = pred.dim() == 4
+    p = pred if layered else pred[None]
+    if p.dim() != 4 or tuple(p.shape[2:]) != (3, 4) or gt.dim() != 3 or tuple(gt.shape[1:]) not in ((3, 4), (4, 4)) or gt.shape[0] != p.shape[1]:
+        raise RuntimeError(f'pose_metrics: pred must be ([L,] B, 3, 4) and gt (B, 3, 4) or (B, 4, 4), got {tuple(pred.shape)} and {tuple(gt.shape)}')
+    L, B = p.shape[0], p.shape[1]
+    p, gt = p.contiguous(), gt.contiguous()
+    out = torch.empty((L, B, 8), dtype=torch.float64, device=p.device)
+    comp = torch.empty((L, B, 3, 4), dtype=torch.float32, device=p.device)
+    n = L * B
+    check(_lib.lib().regtr_pose_metrics(ptr(p) if n else None, ptr(gt) if n else None, gt.shape[1] * gt.shape[2], L, B,
+                                        _lib.dptr(out) if n else None, ptr(comp) if n else None, stream()), 'regtr_pose_metrics')
+    return (out, comp) if layered else (out[0], comp[0])

@@ -8,7 +8,8 @@ test losses (regtr.py:237-294) without gradients: the InfoNCE feature terms on r
 regtr_loss_terms.  `training_step(batch)` trains everything above a frozen KPConv backbone (feat_proj, the cross-encoder, the
 correspondence head, the InfoNCE W) with HIP backward kernels: forward_grad / compute_loss_grad / trainable_parameters;
 `training_step(batch, train_backbone=True)` also trains the 11 KPConv blocks (KPFEncoder.forward_grad, regtr_amd/encoder_grad.py) --
-every parameter the reference trains.  An optimiser loop is not implemented.
+every parameter the reference trains.  An optimiser loop is not implemented.  `validation_step` / `validation_epoch_end` / `test_step`
+are the reference's (generic_reg_model.py:82-104, 130-158) with the registration metrics computed on the device (regtr_amd/metrics.py).
 
 The forward enqueues every stage on the current HIP stream with ONE host synchronisation (the data-dependent level
 sizes after preprocessing): preprocess -> KPConv encoder -> feat_proj -> 6 cross-encoder layers on packed tokens ->
@@ -666,3 +667,41 @@ class RegTR(nn.Module):
                     losses[f'corr_{i}'] = s[1] / s[2].clamp_min(1e-6) + s[3] / s[4].clamp_min(1e-6)
             losses['total'] = torch.sum(torch.stack([losses[k] * wd[k] for k in losses]), dim=0)   # :292-293
         return losses
+
+    # ------------------------------------------------------------------------------------------ validation / test (no gradients)
+    @torch.no_grad()
+    def compute_metrics(self, pred, batch):
+        """generic_reg_model.py:197-209 (_compute_metrics for the `pose` key): se3_compare of every decoder layer's pose with the
+        ground truth -> {'rot_err_deg', 'trans_err'}, (L, B) float32 device tensors (regtr_pose_metrics, computed in float64).
+        `trans_err` is || t_p - R_p R_g^T t_g ||, the reference's (docs/PARITY.md).  No host wait."""
+        from . import metrics
+        err, _ = metrics.pose_errors(pred['pose'], batch['pose'])
+        return {'rot_err_deg': err['rot_err_deg'].to(torch.float32), 'trans_err': err['trans_err'].to(torch.float32)}
+
+    def validation_step(self, batch, batch_idx=None):
+        """generic_reg_model.py:82-91: forward (no gradients), compute_loss, compute_metrics -> (losses, metrics).  Reads no parameter's
+        .grad and writes none; the only host wait is the forward's status read."""
+        pred = self.forward(batch)
+        return self.compute_loss(pred, batch), self.compute_metrics(pred, batch)
+
+    @torch.no_grad()
+    def validation_epoch_end(self, outputs):
+        """generic_reg_model.py:93-104: outputs a list of validation_step results -> (score, {'losses': the mean of every loss key over
+        the steps, 'metrics': metrics.aggregate(...)}) with score = reg_success_final as a Python float -- the one host read."""
+        from . import metrics
+        losses = [o[0] for o in outputs]
+        avg_losses = {k: torch.mean(torch.stack([l[k] for l in losses])) for k in losses[0]}
+        # (the shipped regtr_amd/conf/*.yaml carry no validation section: the reference configs' 10 degrees / 0.1, as test.py assumes)
+        avg_metrics = metrics.aggregate([o[1] for o in outputs], self.cfg.get('reg_success_thresh_rot', 10),
+                                        self.cfg.get('reg_success_thresh_trans', 0.1))
+        return avg_metrics['reg_success_final'].item(), {'losses': avg_losses, 'metrics': avg_metrics}
+
+    def test_step(self, batch, batch_idx=None):
+        """generic_reg_model.py:130-158 without the file output: validation_step's (losses, metrics); under cfg.dataset 'modelnet' with
+        batch['tgt_raw'] present, metrics['modelnet'] = metrics.modelnet_metrics(pred['pose'][-1], batch) (the RPMNet / DCP metrics)."""
+        from . import metrics
+        pred = self.forward(batch)
+        out = self.compute_metrics(pred, batch)
+        if self.cfg.get('dataset', None) == 'modelnet' and 'tgt_raw' in batch:
+            out['modelnet'] = metrics.modelnet_metrics(pred['pose'][-1], batch)
+        return self.compute_loss(pred, batch), out

@@ -73,6 +73,9 @@ parser.add_argument('--voxel_key', choices=('origin', 'floor', 'floor_rcp'), def
 parser.add_argument('--preprocessor', choices=('cpu', 'gpu'), default=None,
                     help="which reference preprocessor's semantics: cpu = Preprocessor (nearest + origin; default, pinned), "
                          'gpu = PreprocessorGPU, the class the reference model instantiates (index + floor)')
+parser.add_argument('--metrics', choices=('host', 'device'), default='host',
+                    help='ModelNet / ModelLoNet: where the RPMNet / DCP metrics are computed: host = regtr_amd.evaluation (scipy KD-trees, one pair at a '
+                         'time; default), device = regtr_amd.metrics (HIP kernels, --batch pairs per launch)')
 parser.add_argument('--benchmark_dir', type=str, default=os.path.join('datasets', '3dmatch', 'benchmarks'),
                     help='folder with <benchmark>/<scene>/gt.log, gt.info for the registration-recall table')
 
@@ -259,9 +262,22 @@ def main():
             # RPMNet / DCP metrics (benchmark_modelnet.py:33-105); the clean cloud of a synthetic pair is its own target
             from regtr_amd.evaluation import modelnet_metrics, summarize_metrics
             items = [pairs[int(i)] for i in ids]
-            per = [modelnet_metrics(poses[k:k + 1], np.stack(gts)[k:k + 1], it['src_xyz'][None], it['tgt_xyz'][None], it['tgt_xyz'][None])
-                   for k, it in enumerate(items)]
-            sm = summarize_metrics({key: np.concatenate([p[key] for p in per]) for key in per[0]})
+            if opt.metrics == 'device':
+                # the same metrics on the GPU (regtr_amd/metrics.py), --batch pairs per launch; one read-back: the stacked summary
+                from regtr_amd import metrics as dev_metrics
+                up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)
+                per = []
+                for k in range(0, len(items), opt.batch):
+                    chunk = items[k:k + opt.batch]
+                    tgt = [up(it['tgt_xyz']) for it in chunk]
+                    per.append(dev_metrics.modelnet_metrics(up(poses[k:k + opt.batch]), {
+                        'src_xyz': [up(it['src_xyz']) for it in chunk], 'tgt_xyz': tgt, 'tgt_raw': tgt, 'pose': up(np.stack(gts[k:k + opt.batch]))}))
+                sm = dev_metrics.summarize({key: torch.cat([p[key] for p in per]) for key in per[0]})
+                sm = dict(zip(sm, torch.stack(list(sm.values())).tolist()))
+            else:
+                per = [modelnet_metrics(poses[k:k + 1], np.stack(gts)[k:k + 1], it['src_xyz'][None], it['tgt_xyz'][None], it['tgt_xyz'][None])
+                       for k, it in enumerate(items)]
+                sm = summarize_metrics({key: np.concatenate([p[key] for p in per]) for key in per[0]})
             logger.info('DeepCP metrics:{:.4f}(rot-rmse) | {:.4f}(rot-mae) | {:.4g}(trans-rmse) | {:.4g}(trans-mae)'.format(
                 sm['r_rmse'], sm['r_mae'], sm['t_rmse'], sm['t_mae']))
             logger.info('Rotation error {:.4f}(deg, mean) | {:.4f}(deg, rmse)'.format(sm['err_r_deg_mean'], sm['err_r_deg_rmse']))
