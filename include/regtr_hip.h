@@ -41,6 +41,7 @@
  *   regtr_infonce_rows / _bwd InfoNCELossFull forward + backward  models/losses/feature_loss.py:246-314
  *   regtr_gemm_tn             dW of InfoNCELossFull (G^T dP')     models/losses/feature_loss.py:295-297
  *   regtr_corr_l1_bwd         CorrCriterion('mae') backward       models/losses/corr_loss.py:24-37
+ *   regtr_circle_rows / _bwd  CircleLossFull ('euclidean') forward + backward   models/losses/feature_loss.py:160-243
  *   regtr_mha_bwd             nn.MultiheadAttention core, backward   transformers.py:197-226
  *   regtr_layernorm_bwd       nn.LayerNorm backward (+ the residual branch's gradient)   transformers.py:194-238
  *   regtr_bias_relu_bwd       nn.Linear bias gradient, F.relu backward   transformers.py:194-238
@@ -467,6 +468,42 @@ int regtr_gemm_tn(const float* a, int lda, const float* b, int ldb, int M, int N
  * (pose_stride 12 or 16); grad and den (the clamped weight sum) are ONE float each on the device.  Refused like regtr_se3_transform. */
 int regtr_corr_l1_bwd(const float* kp, const float* warped, const float* w, const int* seg_off, int n_clouds, int n, const float* pose,
                       int pose_stride, const float* grad, const float* den, float* d_warped, void* stream);
+
+/* CircleLossFull with dist_type 'euclidean' (models/losses/feature_loss.py:160-243) over packed, ragged pairs: regtr_infonce_rows'
+ * argument conventions (anc / pos with row strides, the two segment-offset tables, anc_pose applied to the anchor coordinates on load;
+ * pos holds the positives' features themselves), plus max_pos.  Per pair, over anchors i and positives j:
+ *   d_ij = sqrt(sum_c (a_ic - b_jc)^2 + 1e-12), the explicit differences accumulated in float32 (c ascending, fused multiply-add);
+ *   pos_ij = cd_ij < r_p, neg_ij = cd_ij > r_n with cd_ij regtr_infonce's coordinate distance (the same arithmetic, both strict);
+ *   tp_ij = s (d - pos_margin) max(d - pos_optimal, 0) where pos_ij, else 0;  tn_ij = s (neg_margin - d) max(neg_optimal - d, 0) where
+ *   neg_ij, else 0 -- a masked entry enters its log-sum-exp as exp(0), as in the reference;
+ *   row_i = softplus(LSE_j tp_ij + LSE_j tn_ij) / s, selected when row i has a pos and a neg; col_j the same over i.
+ * anc_lse [n_anc, 2] / pos_lse [n_pos, 2]: the two log-sum-exps of every row / column (max-subtracted, online); anc_sel [n_anc] /
+ * pos_sel [n_pos]: the selection flags (1 / 0).  pair_out [n_pairs, 4]: (sum of the selected row_i, their number, sum of the selected
+ * col_j, their number), float64 sums in a fixed order: no atomics, bit-reproducible; the pair loss is (out0 / out1 + out2 / out3) / 2
+ * (NaN for an empty selection).  max_anc / max_pos >= every pair's counts (a pair with more, or with offsets outside the arrays,
+ * gives NaN sums).  No workspace.  Refused (REGTR_ERR_ARG, nothing launched): D not a multiple of 64 or above 512, a negative count,
+ * a NULL pointer with a non-zero count, ld < D or not a multiple of 4, anc / pos not 16-byte aligned, log_scale <= 0. */
+int regtr_circle_rows(const float* anc, int ld_anc, const float* pos, int ld_pos, const float* anc_xyz, const float* pos_xyz,
+                      const int* anc_seg_off, const int* pos_seg_off, int n_pairs, int n_anc, int n_pos, int max_anc, int max_pos, int D,
+                      float r_p, float r_n, float log_scale, float pos_margin, float pos_optimal, float neg_margin, float neg_optimal,
+                      const float* anc_pose, float* pair_out, float* anc_lse, float* anc_sel, float* pos_lse, float* pos_sel,
+                      void* stream);
+
+/* Backward of loss = (1 / mean_div) sum_b (out0 / out1 + out2 / out3)_b / 2 from regtr_circle_rows' statistics and the same distance
+ * arithmetic.  grad: ONE float on the device.  The weights max(.) are constants of the differentiation, so with
+ *   k_i = (grad / mean_div / 2 / out1) sigmoid(LSEp_i + LSEn_i) on selected rows (0 elsewhere), k_j likewise with out3 on columns,
+ *   g_ij = (k_i e^(tp - LSEp_i) + k_j e^(tp - LSEp_j)) max(d - pos_optimal, 0) [pos_ij]
+ *        - (k_i e^(tn - LSEn_i) + k_j e^(tn - LSEn_j)) max(neg_optimal - d, 0) [neg_ij],      c_ij = g_ij / d_ij,
+ *   d_anc_i = (sum_j c_ij) a_i - sum_j c_ij b_j,      d_pos_j = (sum_i c_ij) b_j - sum_i c_ij a_i.
+ * Every row of every pair is written; a pair whose loss is NaN (out1 = 0 or out3 = 0) gets zero rows.  One owner per output row, no
+ * atomics, no host wait, bit-reproducible.  Refused like regtr_circle_rows, and: mean_div <= 0, ld_danc / ld_dpos < D or not a
+ * multiple of 4, d_anc / d_pos not 16-byte aligned. */
+int regtr_circle_bwd(const float* anc, int ld_anc, const float* pos, int ld_pos, const float* anc_xyz, const float* pos_xyz,
+                     const int* anc_seg_off, const int* pos_seg_off, int n_pairs, int n_anc, int n_pos, int max_anc, int max_pos, int D,
+                     float r_p, float r_n, float log_scale, float pos_margin, float pos_optimal, float neg_margin, float neg_optimal,
+                     const float* anc_pose, const float* anc_lse, const float* anc_sel, const float* pos_lse, const float* pos_sel,
+                     const float* pair_out, const float* grad, float mean_div, float* d_anc, int ld_danc, float* d_pos, int ld_dpos,
+                     void* stream);
 
 /* Backward of regtr_mha_fwd's arithmetic on the same packed layout (head_dim = 32; cloud c's rows attend the rows of cloud kv_of[c]; any
  * kv_of with entries in [0, n_clouds) is legal, several query clouds may share a key cloud).  With s_ij = scale q_i . k_j, P = softmax_j(s),

@@ -112,6 +112,10 @@ SIGNATURES = {
     'regtr_infonce_rows': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     'regtr_infonce_bwd': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _F, _P, _I, _P, _I,
                                _P]),
+    'regtr_circle_rows': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P,
+                               _P]),
+    'regtr_circle_bwd': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P,
+                              _P, _F, _P, _I, _P, _I, _P]),
     'regtr_gemm_tn_ws_bytes': (_Z, [_I, _I, _I]),
     'regtr_gemm_tn': (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _Z, _P]),
     'regtr_corr_l1_bwd': (_I, [_P, _P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _P]),

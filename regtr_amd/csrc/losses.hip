@@ -28,6 +28,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "loss_common.h"      // lse_merge, transform_rn, coord_dist_rn, pair_ok: shared with circle_loss.hip
 
 namespace {
 
@@ -56,14 +57,6 @@ struct RowState {
     int jmin;                      // its target index (-1: none seen)
 };
 
-__device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2)
-{
-    const float M = fmaxf(m, m2);
-    if (M == -INFINITY) { s = s + s2; m = M; return; }          // both empty (s = s2 = 0)
-    s = s * expf(m - M) + s2 * expf(m2 - M);
-    m = M;
-}
-
 __device__ __forceinline__ void row_merge(RowState& a, const RowState& b)
 {
     lse_merge(a.m, a.s, b.m, b.s);
@@ -81,20 +74,6 @@ __device__ __forceinline__ RowState row_shfl_xor(const RowState& a, int o)
     b.lstar = __shfl_xor(a.lstar, o, RG_WAVE);
     b.jmin = __shfl_xor(a.jmin, o, RG_WAVE);
     return b;
-}
-
-__device__ __forceinline__ void transform_rn(const float* T, float x, float y, float z, float out[3])
-{
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-        out[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[4 * r], x), __fmul_rn(T[4 * r + 1], y)), __fmul_rn(T[4 * r + 2], z)), T[4 * r + 3]);
-}
-
-__device__ __forceinline__ bool pair_ok(const int* off, int b, int n, int& lo, int& hi)
-{
-    lo = off[b];
-    hi = off[b + 1];
-    return 0 <= lo && lo <= hi && hi <= n;
 }
 
 template <int D>
@@ -204,8 +183,7 @@ __global__ __launch_bounds__(IN_THREADS) void k_infonce(InfArgs g)
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 const float l = acc[c][r];
-                const float dx = __fsub_rn(ax[r][0], px), dy = __fsub_rn(ax[r][1], py), dz = __fsub_rn(ax[r][2], pz);
-                const float d = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+                const float d = coord_dist_rn(ax[r][0], ax[r][1], ax[r][2], px, py, pz);
                 if (d < st[r].dmin) { st[r].dmin = d; st[r].lstar = l; st[r].jmin = j; }   // strict: the lowest j keeps a tie
                 if (!(d < r_n)) {
                     if (l > st[r].m) { st[r].s = st[r].s * expf(st[r].m - l) + 1.f; st[r].m = l; }
@@ -522,8 +500,7 @@ __global__ __launch_bounds__(IN_THREADS) void k_infonce_bwd(InfBwdArgs g)
                     // d_ij with the anchor first, as the forward computes it
                     const float* ap = ANC_ROWS ? rx[r] : &cxyz_s[3 * col];
                     const float px = ANC_ROWS ? cx : rx[r][0], py = ANC_ROWS ? cy : rx[r][1], pz = ANC_ROWS ? cz : rx[r][2];
-                    const float dx = __fsub_rn(ap[0], px), dy = __fsub_rn(ap[1], py), dz = __fsub_rn(ap[2], pz);
-                    const float d = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+                    const float d = coord_dist_rn(ap[0], ap[1], ap[2], px, py, pz);
                     const int j = ANC_ROWS ? c : row;
                     const int jstar = ANC_ROWS ? ridx[r] : cidx_s[col];
                     const float lse = ANC_ROWS ? rlse[r] : clse_s[col];

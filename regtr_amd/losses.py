@@ -1,4 +1,5 @@
 """Differentiable drop-ins for the reference's training losses: InfoNCELossFull (models/losses/feature_loss.py:246-314),
+CircleLossFull (feature_loss.py:160-243, dist_type 'euclidean'; csrc/circle_loss.hip: regtr_circle_rows / regtr_circle_bwd),
 CorrCriterion (models/losses/corr_loss.py:9-40) and OverlapCriterion (nn.BCEWithLogitsLoss, models/regtr.py:84,250-252), with the same
 constructors, parameter names and forward signatures, so that
 
@@ -12,7 +13,7 @@ of csrc/losses.hip (regtr_infonce_rows / regtr_infonce_bwd / regtr_gemm_tn, regt
 (regtr_bce_logits_bwd) and the exact-f32 GEMM; torch only packs the per-pair lists and forms the scalar means.  Nothing here synchronises with the host.
 
 Reference semantics are kept: a pair without an anchor inside r_p gives NaN (0 / 0), and its gradient contributions are exactly 0.
-Refused: metric='mse', overlap_weights=None, coordinates / poses / weights that require grad, double backward, tensors off the GPU.
+Refused: metric='mse', overlap_weights=None, CircleLossFull's dist_type other than 'euclidean', coordinates / poses / weights that require grad, double backward, tensors off the GPU.
 """
 import torch
 import torch.nn as nn
@@ -104,6 +105,78 @@ class InfoNCELossFull(nn.Module):
         px = torch.cat(list(tgt_xyz)).contiguous()
         return _InfoNCE.apply(A, G, self.W, ax, px, _offsets(n_src, dev), _offsets(n_tgt, dev), max(n_src), max(n_tgt),
                               float(self.r_p), float(self.r_n))
+
+
+class _Circle(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, A, G, ax, px, a_off, p_off, max_anc, max_pos, r_p, r_n, params):
+        with context.forward(A.device, f16_pair=False, status=None):
+            saved = ops.circle_rows(A, G, ax, px, a_off, p_off, max_anc, max_pos, r_p, r_n, params)
+        out = saved[0]
+        ctx.save_for_backward(A, G, ax, px, a_off, p_off, *saved)
+        ctx.meta = (max_anc, max_pos, r_p, r_n, params, out.shape[0])
+        return ((out[:, 0] / out[:, 1] + out[:, 2] / out[:, 3]) / 2).mean()           # feature_loss.py:229, 243
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        A, G, ax, px, a_off, p_off, *saved = ctx.saved_tensors
+        max_anc, max_pos, r_p, r_n, params, B = ctx.meta
+        g = g.detach().to(torch.float32).contiguous()
+        with context.forward(A.device, f16_pair=False, status=None):
+            dA, dG = ops.circle_bwd(A, G, ax, px, a_off, p_off, max_anc, max_pos, r_p, r_n, saved, g, float(B), params)
+        return dA, dG, None, None, None, None, None, None, None, None, None
+
+
+class CircleLossFull(nn.Module):
+    """feature_loss.py:160-243 on the HIP kernels of csrc/circle_loss.hip, with the reference's constructor and attributes and, like it,
+    no parameters (an empty state_dict).  forward(anchor_feat, positive_feat, anchor_xyz, positive_xyz): lists of per-pair (N, D) float32
+    features and (N, 3) coordinates on the GPU (anchor_xyz already in the positives' frame) -> the mean over pairs of
+    (mean of the selected row losses + mean of the selected column losses) / 2.  Gradients go to the features.  dist_type: only
+    'euclidean', what the reference model constructs; any other is refused when called.  A pair without a selected row or column gives NaN,
+    as the reference's mean of nothing, and contributes exactly zero gradient (the reference's autograd would still pass the gradient of
+    the half that is not empty).  log_scale, the margins and the radii are read at every call."""
+
+    def __init__(self, dist_type='cosine', log_scale=10, r_p=0.125, r_n=0.25, pos_margin=0.1, neg_margin=1.4):
+        super().__init__()
+        self.log_scale = log_scale
+        self.pos_margin = pos_margin
+        self.neg_margin = neg_margin
+        self.pos_optimal = pos_margin
+        self.neg_optimal = neg_margin
+        self.dist_type = dist_type
+        self.r_p = r_p
+        self.r_n = r_n
+
+    def params(self):
+        """The kernels' scalar arguments, from the attributes as they are now."""
+        return dict(log_scale=float(self.log_scale), pos_margin=float(self.pos_margin), pos_optimal=float(self.pos_optimal),
+                    neg_margin=float(self.neg_margin), neg_optimal=float(self.neg_optimal))
+
+    def forward(self, anchor_feat, positive_feat, anchor_xyz, positive_xyz):
+        if self.dist_type != 'euclidean':
+            raise NotImplementedError(f"CircleLossFull: dist_type {self.dist_type!r} is not implemented (only 'euclidean', what RegTR uses)")
+        B = len(anchor_feat)
+        if B == 0 or not (len(positive_feat) == len(anchor_xyz) == len(positive_xyz) == B):
+            raise RuntimeError(f'CircleLossFull: need the same number (>= 1) of anchor / positive features and coordinates, got '
+                               f'{len(anchor_feat)}, {len(positive_feat)}, {len(anchor_xyz)}, {len(positive_xyz)}')
+        _no_grad_inputs('CircleLossFull', [*anchor_xyz, *positive_xyz])
+        _on_gpu('CircleLossFull', [*anchor_feat, *positive_feat, *anchor_xyz, *positive_xyz])
+        if any(f.dtype != torch.float32 for f in [*anchor_feat, *positive_feat, *anchor_xyz, *positive_xyz]):
+            raise RuntimeError('CircleLossFull: float32 features and coordinates only')
+        n_anc = [int(f.shape[0]) for f in anchor_feat]
+        n_pos = [int(f.shape[0]) for f in positive_feat]
+        if min(n_anc) < 1 or min(n_pos) < 1:
+            raise RuntimeError('CircleLossFull: every cloud needs at least one point')
+        if [int(x.shape[0]) for x in anchor_xyz] != n_anc or [int(x.shape[0]) for x in positive_xyz] != n_pos:
+            raise RuntimeError('CircleLossFull: one coordinate per feature row (feature_loss.py:235-236)')
+        dev = anchor_feat[0].device
+        A = torch.cat(list(anchor_feat)).contiguous()
+        G = torch.cat(list(positive_feat)).contiguous()
+        ax = torch.cat(list(anchor_xyz)).contiguous()
+        px = torch.cat(list(positive_xyz)).contiguous()
+        return _Circle.apply(A, G, ax, px, _offsets(n_anc, dev), _offsets(n_pos, dev), max(n_anc), max(n_pos), float(self.r_p),
+                             float(self.r_n), self.params())
 
 
 class _CorrL1(torch.autograd.Function):

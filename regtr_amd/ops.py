@@ -755,6 +755,58 @@ def infonce_bwd(anc, pos_t, anc_xyz, pos_xyz, anc_seg_off, pos_seg_off, max_anc,
     return d_anc, d_pos
 
 
+CIRCLE_DEFAULTS = dict(log_scale=10.0, pos_margin=0.1, pos_optimal=0.1, neg_margin=1.4, neg_optimal=1.4)     # feature_loss.py:168
+
+
+def _circle_args(anc, pos, anc_xyz, pos_xyz, anc_seg_off, pos_seg_off, max_anc, max_pos, r_p, r_n, params, anc_pose):
+    """The leading arguments regtr_circle_rows and regtr_circle_bwd share."""
+    n_anc, D = anc.shape
+    n_pos = pos.shape[0]
+    p = dict(CIRCLE_DEFAULTS, **(params or {}))
+    lda = anc.stride(0) if n_anc > 1 else D
+    ldp = pos.stride(0) if n_pos > 1 else D
+    assert anc.stride(1) == 1 and pos.stride(1) == 1
+    return (raw(anc) if n_anc else None, lda, raw(pos) if n_pos else None, ldp, ptr(anc_xyz) if n_anc else None,
+            ptr(pos_xyz) if n_pos else None, iptr(anc_seg_off), iptr(pos_seg_off), anc_seg_off.numel() - 1, n_anc, n_pos, int(max_anc),
+            int(max_pos), D, float(r_p), float(r_n), float(p['log_scale']), float(p['pos_margin']), float(p['pos_optimal']),
+            float(p['neg_margin']), float(p['neg_optimal']), ptr(anc_pose))
+
+
+def circle_rows(anc, pos, anc_xyz, pos_xyz, anc_seg_off, pos_seg_off, max_anc, max_pos, r_p, r_n, params=None, anc_pose=None):
+    """CircleLossFull ('euclidean') of packed, ragged pairs (regtr_circle_rows).  anc (N_anc, D) / pos (N_pos, D) row-strided views, xyz
+    (N, 3), seg_off (B+1,) int32 on the device, max_anc / max_pos >= every pair's counts, params: overrides of CIRCLE_DEFAULTS, anc_pose
+    (B, 12) float32 or None: applied to anc_xyz first.  -> (pair_out (B, 4) = (sum of selected row losses, their number, sum of selected
+    column losses, their number), anc_lse (N_anc, 2), anc_sel (N_anc,), pos_lse (N_pos, 2), pos_sel (N_pos,)): what circle_bwd reuses.
+    The pair loss is (out0 / out1 + out2 / out3) / 2.  Nothing here synchronises."""
+    n_anc, n_pos, dev = anc.shape[0], pos.shape[0], anc.device
+    B = anc_seg_off.numel() - 1
+    out = torch.empty((B, 4), dtype=torch.float32, device=dev)
+    a_lse = torch.empty((n_anc, 2), dtype=torch.float32, device=dev)
+    a_sel = torch.empty(n_anc, dtype=torch.float32, device=dev)
+    p_lse = torch.empty((n_pos, 2), dtype=torch.float32, device=dev)
+    p_sel = torch.empty(n_pos, dtype=torch.float32, device=dev)
+    head = _circle_args(anc, pos, anc_xyz, pos_xyz, anc_seg_off, pos_seg_off, max_anc, max_pos, r_p, r_n, params, anc_pose)
+    check(_lib.lib().regtr_circle_rows(*head, ptr(out), ptr(a_lse) if n_anc else None, ptr(a_sel) if n_anc else None,
+                                       ptr(p_lse) if n_pos else None, ptr(p_sel) if n_pos else None, stream()), 'regtr_circle_rows')
+    return out, a_lse, a_sel, p_lse, p_sel
+
+
+def circle_bwd(anc, pos, anc_xyz, pos_xyz, anc_seg_off, pos_seg_off, max_anc, max_pos, r_p, r_n, saved, grad, mean_div, params=None,
+               anc_pose=None):
+    """Backward of (1 / mean_div) sum_b (out0 / out1 + out2 / out3)_b / 2 (regtr_circle_bwd): saved = circle_rows' result, grad a 0-dim
+    float32 device tensor -> (d_anc (N_anc, D), d_pos (N_pos, D)); a NaN pair's rows are zero.  Nothing here synchronises."""
+    out, a_lse, a_sel, p_lse, p_sel = saved
+    n_anc, D = anc.shape
+    n_pos = pos.shape[0]
+    d_anc = torch.empty((n_anc, D), dtype=torch.float32, device=anc.device)
+    d_pos = torch.empty((n_pos, D), dtype=torch.float32, device=anc.device)
+    head = _circle_args(anc, pos, anc_xyz, pos_xyz, anc_seg_off, pos_seg_off, max_anc, max_pos, r_p, r_n, params, anc_pose)
+    check(_lib.lib().regtr_circle_bwd(*head, ptr(a_lse) if n_anc else None, ptr(a_sel) if n_anc else None, ptr(p_lse) if n_pos else None,
+                                      ptr(p_sel) if n_pos else None, ptr(out), ptr(grad.reshape(1)), float(mean_div),
+                                      ptr(d_anc) if n_anc else None, D, ptr(d_pos) if n_pos else None, D, stream()), 'regtr_circle_bwd')
+    return d_anc, d_pos
+
+
 def gemm_tn(a, b, fold=False):
     """a (M, N1)^T @ b (M, N2) -> (N1, N2) over a tall M (regtr_gemm_tn: split-K, fixed-order second pass, bit-reproducible); N1, N2
     multiples of 64.  fold=True (N1 == N2): InfoNCELossFull's dW from dW_sym = a^T b (upper triangle dW_sym + dW_sym^T, diagonal

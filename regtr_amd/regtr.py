@@ -4,7 +4,8 @@ Drop-in for the reference's `RegTR` (/root/reference/src/models/regtr.py:22-235)
 same `forward(batch) -> dict` contract (input lists batch['src_xyz'] / batch['tgt_xyz'], side effect
 batch['kpconv_meta'], output keys of regtr.py:218-235), same `state_dict` names and shapes, so a reference checkpoint
 loads with `load_state_dict(state['state_dict'])` (demo.py:165).  `compute_loss(pred, batch)` gives the reference's validation /
-test losses (regtr.py:237-294) without gradients: the InfoNCE feature terms on regtr_infonce, the overlap and correspondence terms on
+test losses (regtr.py:237-294) without gradients: the feature terms on regtr_infonce (`feature_loss_type: infonce`) or
+regtr_circle_rows (`feature_loss_type: circle`, CircleLossFull with no parameters), the overlap and correspondence terms on
 regtr_loss_terms.  `training_step(batch)` trains everything above a frozen KPConv backbone (feat_proj, the cross-encoder, the
 correspondence head, the InfoNCE W) with HIP backward kernels: forward_grad / compute_loss_grad / trainable_parameters;
 `training_step(batch, train_backbone=True)` also trains the 11 KPConv blocks (KPFEncoder.forward_grad, regtr_amd/encoder_grad.py) --
@@ -202,9 +203,16 @@ class RegTR(nn.Module):
             self.correspondence_decoder = CorrespondenceRegressor(cfg.d_embed)
         else:
             self.correspondence_decoder = CorrespondenceDecoder(cfg.d_embed, cfg.corr_decoder_has_pos_emb)
-        if cfg.get('feature_loss_type', 'infonce') == 'infonce':                  # :79-81
+        loss_type = cfg.get('feature_loss_type', 'infonce')
+        if loss_type == 'infonce':                                                # :79-81
             self.feature_criterion = _LossParams(cfg.d_embed)
             self.feature_criterion_un = _LossParams(cfg.d_embed)
+        elif loss_type == 'circle':                                               # :82-84: ONE criterion, no parameters
+            from .losses import CircleLossFull
+            self.feature_criterion = self.feature_criterion_un = CircleLossFull('euclidean', r_p=cfg.get('r_p', 0.125),
+                                                                                r_n=cfg.get('r_n', 0.25))
+        else:
+            raise NotImplementedError(f"feature_loss_type {loss_type!r}: choose 'infonce' or 'circle'")        # :85-86
         self.weight_dict = loss_weight_dict(cfg) if 'wt_feature_un' in cfg else None        # :90-95 (configs with a losses section)
         self._cache = {}
         self.last_timings = None
@@ -435,8 +443,6 @@ class RegTR(nn.Module):
         if not isinstance(self.correspondence_decoder, CorrespondenceRegressor):
             raise NotImplementedError(f'{what}: the attention-valued head (direct_regress_coor: false) has no backward; only '
                                       'CorrespondenceRegressor configs can be trained')
-        if self.cfg.get('feature_loss_type', 'infonce') != 'infonce':
-            raise NotImplementedError(f"{what}: feature_loss_type {self.cfg.feature_loss_type!r} (CircleLossFull) is not implemented")
         missing = [k for k in ('r_p', 'r_n', 'wt_overlap', 'wt_feature', 'wt_feature_un', 'wt_corr') if k not in self.cfg]
         if missing:
             raise KeyError(f'{what} needs the losses section of the config (regtr_amd/conf/*.yaml); missing: {missing}')
@@ -519,7 +525,8 @@ class RegTR(nn.Module):
     def compute_loss_grad(self, pred, batch):
         """compute_loss(pred, batch) -- the same keys and reference semantics (regtr.py:237-294) -- as differentiable 0-dim tensors, built
         from the training criteria of regtr_amd/losses.py: the overlap terms on OverlapCriterion's Function (bit-equal to compute_loss's),
-        the feature terms on InfoNCELossFull's with this model's feature_criterion.W / feature_criterion_un.W, the correspondence terms
+        the feature terms on InfoNCELossFull's with this model's feature_criterion.W / feature_criterion_un.W (or on CircleLossFull's
+        under feature_loss_type 'circle', with the shared criterion's margins and radii), the correspondence terms
         on CorrCriterion's in both directions (the inverse GT pose for tgt), the total weighted by loss_weight_dict(cfg).  Gradients go
         to the features, the warped points, the overlap logits and the two W.  No host wait, forward or backward."""
         from . import losses as L
@@ -561,9 +568,14 @@ class RegTR(nn.Module):
             losses[f'overlap_{i}'] = L.overlap_bce(rows('overlap', i).reshape(N), gt_c, seg_c, xyz, warped.detach().contiguous(), pose)
         feat_sets = [(f'feature_{i}', self.feature_criterion, rows('feat', i)) for i in cfg.feature_loss_on]
         feat_sets.append(('feature_un', self.feature_criterion_un, rows('feat_un')))
+        circle = isinstance(self.feature_criterion, L.CircleLossFull)
         for key, crit, feats in feat_sets:                                                        # :255-265
-            losses[key] = L._InfoNCE.apply(feats[:n_src], feats[n_src:], crit.W, anc_xyz, xyz[n_src:], seg_s, seg_t, max(lens[:B]),
-                                           max(lens[B:]), float(cfg.r_p), float(cfg.r_n))
+            if circle:
+                losses[key] = L._Circle.apply(feats[:n_src].contiguous(), feats[n_src:].contiguous(), anc_xyz, xyz[n_src:], seg_s, seg_t,
+                                              max(lens[:B]), max(lens[B:]), float(crit.r_p), float(crit.r_n), crit.params())
+            else:
+                losses[key] = L._InfoNCE.apply(feats[:n_src], feats[n_src:], crit.W, anc_xyz, xyz[n_src:], seg_s, seg_t, max(lens[:B]),
+                                               max(lens[B:]), float(cfg.r_p), float(cfg.r_n))
         for i in cfg.corr_loss_on:                                                                # :268-281
             warped = rows('kp_warped', i)
             losses[f'corr_{i}'] = (L._CorrL1.apply(warped[:n_src], xyz[:n_src], gt_c[:n_src], seg_s, seg2_s, pose) +
@@ -573,12 +585,13 @@ class RegTR(nn.Module):
 
     def trainable_parameters(self, backbone=False):
         """The parameters above the backbone -- feat_proj, the cross-encoder, the correspondence head and the two InfoNCE W -- as a
-        list.  Turns requires_grad on for the two W (they are created frozen, which inference keeps).  backbone=True: kpf_encoder's
+        list.  Turns requires_grad on for the two W (they are created frozen, which inference keeps; a circle config has none).  backbone=True: kpf_encoder's
         weights as well (what training_step(train_backbone=True) fills); the kernel_points stay requires_grad=False and are not
         listed."""
         mods = [self.feat_proj, self.transformer_encoder, self.correspondence_decoder, self.feature_criterion, self.feature_criterion_un]
         for crit in mods[3:]:
-            crit.W.requires_grad_(True)
+            if hasattr(crit, 'W'):                    # (CircleLossFull has no parameters)
+                crit.W.requires_grad_(True)
         params = [p for m in mods for p in m.parameters()]
         if backbone:
             params += [p for p in self.kpf_encoder.parameters() if p.requires_grad]
@@ -605,6 +618,12 @@ class RegTR(nn.Module):
         ops.gemm(feats[n_src:], self._w_sym(crit), out=pos_t[n_src:])                         # exact-f32 MFMA GEMM
         return ops.infonce(feats, pos_t, xyz, xyz, seg_c[:B + 1], seg_c[B:], max(lens[:B], default=0), r_p, r_n, anc_pose=pose12)
 
+    def _circle(self, crit, feats, xyz, seg_c, lens, B, pose12):
+        """Per-pair (row-loss sum, selected rows, column-loss sum, selected columns) of CircleLossFull.forward on packed tokens (src
+        clouds, then tgt clouds), anchors and positives as in _infonce: regtr_circle_rows reads both sides in place."""
+        return ops.circle_rows(feats, feats, xyz, xyz, seg_c[:B + 1], seg_c[B:], max(lens[:B], default=0), max(lens[B:], default=0),
+                               float(crit.r_p), float(crit.r_n), crit.params(), anc_pose=pose12)[0]
+
     def loss_keys(self):
         """The keys of compute_loss's result, in its order."""
         cfg = self.cfg
@@ -617,13 +636,16 @@ class RegTR(nn.Module):
         or (B,) tensors of every term per pair with per_pair=True (what the reference computes with one pair per batch).
         batch: 'pose' (B, 3, 4) or (B, 4, 4), 'src_overlap' / 'tgt_overlap' level-0 masks, 'kpconv_meta' from the preceding forward
         (batch['overlap_pyr'] is set as the reference does).  Reference semantics kept, NaN included: a pair without an anchor inside
-        r_p gives 0 / 0 in its feature term, and the total is then NaN.  Float32-grade whatever cfg.compute_dtype; no host wait."""
+        r_p gives 0 / 0 in its feature term, and the total is then NaN.  Float32-grade whatever cfg.compute_dtype; no host wait.
+        Under feature_loss_type 'circle' a prediction with no pairs raises NotImplementedError (the loss divides by their number)."""
         cfg = self.cfg
-        if cfg.get('feature_loss_type', 'infonce') != 'infonce':
-            raise NotImplementedError(f"compute_loss: feature_loss_type {cfg.feature_loss_type!r} (CircleLossFull) is not implemented")
         missing = [k for k in ('r_p', 'r_n', 'wt_overlap', 'wt_feature', 'wt_feature_un', 'wt_corr') if k not in cfg]
         if missing:
             raise KeyError(f'compute_loss needs the losses section of the config (regtr_amd/conf/*.yaml); missing: {missing}')
+        if cfg.get('feature_loss_type', 'infonce') == 'circle' and len(pred['src_kp']) == 0:
+            # CircleLossFull divides by the number of pairs (feature_loss.py:243): there is no circle loss of no pairs, and
+            # regtr_circle_rows has no pair to reduce
+            raise NotImplementedError("compute_loss: feature_loss_type 'circle' over an empty batch (no pairs) is not implemented")
         meta = batch['kpconv_meta']
         B = len(pred['src_kp'])
         dev = pred['src_kp'][0].device
@@ -654,9 +676,14 @@ class RegTR(nn.Module):
             feat_sets = [(f'feature_{i}', self.feature_criterion,
                           _packed_rows([f[i] for f in pred['src_feat']] + [f[i] for f in pred['tgt_feat']])) for i in cfg.feature_loss_on]
             feat_sets.append(('feature_un', self.feature_criterion_un, _packed_rows(list(pred['src_feat_un']) + list(pred['tgt_feat_un']))))
+            circle = cfg.get('feature_loss_type', 'infonce') == 'circle'
             for key, crit, feats in feat_sets:                                                    # :258-269, feature_loss.py:303-314
-                out = self._infonce(crit, feats, xyz, seg_c, lens, B, pose12, cfg.r_p, cfg.r_n)
-                per = out[:, 0] / out[:, 1]
+                if circle:                                                                        # feature_loss.py:229-243
+                    out = self._circle(crit, feats, xyz, seg_c, lens, B, pose12)
+                    per = (out[:, 0] / out[:, 1] + out[:, 2] / out[:, 3]) / 2
+                else:
+                    out = self._infonce(crit, feats, xyz, seg_c, lens, B, pose12, cfg.r_p, cfg.r_n)
+                    per = out[:, 0] / out[:, 1]
                 losses[key] = per if per_pair else per.mean()
             for i in cfg.corr_loss_on:                                                            # :271-285, corr_loss.py:18-40
                 t = terms[i]
