@@ -806,6 +806,53 @@ int regtr_segment_mean(const float* v, const int* off, int n_clouds, int n, doub
 int regtr_pose_metrics(const float* pred, const float* gt, int gt_stride, int n_layers, int n_pairs, double* out, float* composed,
                        void* stream);
 
+/* ---- the optimiser step (regtr_amd/optim.py; csrc/optim.hip) --------------------------------------------------------------------------
+ * clip_grad_norm_ + torch.optim.AdamW / Adam (the reference's trainer.py:104-121) over many tensors per launch.  New entry points only:
+ * no existing signature changes, REGTR_ABI_VERSION stays as it is. */
+
+/* One tensor of a multi-tensor call, filled on the HOST and read there by the entry points (they pack chunks of
+ * regtr_optim_chunk_tensors() tensors into a by-value kernel argument: no device-side table, no copy, nothing kept between calls).
+ * p, g, m, v: device pointers to n float32 elements (parameter, gradient, exp_avg, exp_avg_sq), 4-byte aligned; 16-byte alignment of
+ * all of them selects the 16-byte loads and stores.  The scalars are the tensor's own (torch keeps a step count per parameter):
+ * bias_correction1 = 1 - beta1^t, sqrt_bias_correction2 = sqrt(1 - beta2^t), computed in float64; each is rounded to float32 once. */
+typedef struct {
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    long long n;
+    double lr, weight_decay, beta1, beta2, eps, bias_correction1, sqrt_bias_correction2;
+} regtr_optim_tensor_t;
+
+/* Host only: elements per workgroup (= per float64 partial) of regtr_grad_sumsq; elements per workgroup of regtr_adam_step; tensors
+ * per launch. */
+int regtr_optim_norm_slice(void);
+int regtr_optim_step_slice(void);
+int regtr_optim_chunk_tensors(void);
+
+/* First half of the global gradient norm.  Tensor t's gradient g (n elements; p, m, v and the scalars are not read) is cut into
+ * ceil(n / regtr_optim_norm_slice()) slices; partials [n_partials] (float64) receives the sum of squares of every slice, tensor after
+ * tensor, slice after slice, each summed in float64 in a fixed order that depends on neither the grid nor the pointer's alignment.
+ * n_partials must equal the number of slices.  Bit-reproducible.  Refused: negative counts, a wrong n_partials, NULLs with work to do,
+ * a pointer that is not 4-byte aligned. */
+int regtr_grad_sumsq(const regtr_optim_tensor_t* tensors, int n_tensors, double* partials, long long n_partials, void* stream);
+
+/* Second half: one workgroup adds the partials in float64 in a fixed order; norm_coef [2] (float32, device) = {total_norm =
+ * sqrt(sum), clip_coef = min(1, max_norm / (total_norm + 1e-6))} -- torch.nn.utils.clip_grad_norm_'s formula in float32.  max_norm
+ * <= 0: no clipping, clip_coef = 1 and the norm is still written.  A NaN norm gives a NaN coefficient (no skip logic).  n_partials
+ * == 0 gives a norm of 0.  Refused: a negative count, a NaN max_norm, NULLs. */
+int regtr_grad_norm_finish(const double* partials, long long n_partials, float max_norm, float* norm_coef, void* stream);
+
+/* torch's single-tensor AdamW (decoupled != 0) or Adam (decoupled == 0, weight decay added to the gradient) on every tensor, per
+ * element in float32 rounded per operation:
+ *   g' = g coef;  AdamW: p = p (1 - lr wd);  Adam: g' = g' + wd p
+ *   m = beta1 m + (1 - beta1) g';  v = beta2 v + ((1 - beta2) g') g';  p = p - (lr / bc1) (m / (sqrt(v) / sqrt(bc2) + eps))
+ * clip_coef: device float32 read by the kernel (regtr_grad_norm_finish's norm_coef + 1), NULL = 1.  g is NOT modified (unlike
+ * clip_grad_norm_, which scales .grad in place).  Elements outside [0, n) of every tensor are never touched.  Bit-reproducible.
+ * Refused: negative counts, NULLs with work to do, misaligned pointers, bias corrections that are not positive, a negative eps, NaN
+ * scalars. */
+int regtr_adam_step(const regtr_optim_tensor_t* tensors, int n_tensors, const float* clip_coef, int decoupled, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

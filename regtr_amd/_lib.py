@@ -152,6 +152,12 @@ SIGNATURES = {
     'regtr_nearest': (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     'regtr_segment_mean': (_I, [_P, _P, _I, _I, _P, _P]),
     'regtr_pose_metrics': (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    'regtr_optim_norm_slice': (_I, []),
+    'regtr_optim_step_slice': (_I, []),
+    'regtr_optim_chunk_tensors': (_I, []),
+    'regtr_grad_sumsq': (_I, [_P, _I, _P, _c.c_longlong, _P]),
+    'regtr_grad_norm_finish': (_I, [_P, _c.c_longlong, _F, _P, _P]),
+    'regtr_adam_step': (_I, [_P, _I, _P, _I, _P]),
 }
 
 COMPOSITE = ('regtr_encoder_fwd', 'regtr_cross_encoder_fwd')      # bound through a GIL-releasing handle (see _load)

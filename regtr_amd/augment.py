@@ -20,7 +20,8 @@ Nothing synchronises: the output lengths min(n, max_pts) depend on the swap deci
 (`swap_flags`) instead of reading the device's flags back.
 
 The ModelNet chain (data_loaders/modelnet.py:102-109) is `modelnet_train_batch` below (csrc/augment_modelnet.hip, purposes 3-7 of the same
-Philox convention).  Not built here: the `correspondences` key (no loss reads it), an optimiser.
+Philox convention).  Not built here: the `correspondences` key (no loss reads it).  (The optimiser: regtr_amd/optim.py;
+the loop: harness.train_loop, train.py.)
 Refused: CPU tensors, empty clouds, clouds that are not (n, 3), masks that do not match their cloud.
 """
 import numpy as np

@@ -581,14 +581,16 @@ def pose_errors(pred, gt):
 
 
 # ------------------------------------------------------------------------------------------------------ training input
-def train_batches(source, cfg, batch_size, seed, epochs=1, device=None, num_workers=4, loader_pool=None):
+def train_batches(source, cfg, batch_size, seed, epochs=1, device=None, num_workers=4, loader_pool=None, first_step=0):
     """Generator of augmented training batches over a 3DMatch-style pair source (`source[i]` -> {'src_xyz', 'tgt_xyz', 'pose', 'idx'}:
     ThreeDMatchPairs, SyntheticPairs): the loader pool, pinned staging and side-stream H2D copy run_test reads its pairs through, then
     augment.train_batch on the resident raw clouds -- overlap masks of the clean pair, the reference's augmentation chain -- with
     `step` counting up from 0 across epochs, so batch k of a run is a function of (source, seed, k) alone.  Every epoch visits every pair
     once in an order drawn from (seed, epoch); a last short batch is yielded as it is.  loader_pool: a LoaderPool over `source` made by the
     caller (e.g. before the GPU was initialised); else one of num_workers processes is made here and closed at the end (0: one loader
-    thread).  Each batch goes straight into RegTR.training_step; 'ids' names its pairs."""
+    thread).  Each batch goes straight into RegTR.training_step; 'ids' names its pairs.  first_step: start the (seed, step) sequence at
+    that batch (a resumed run): batches 0 .. first_step - 1 are neither loaded nor built, batch first_step is the one an unbroken run
+    yields there."""
     from .augment import train_batch
     device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
     pool = loader_pool
@@ -598,6 +600,9 @@ def train_batches(source, cfg, batch_size, seed, epochs=1, device=None, num_work
     try:
         for epoch in range(int(epochs)):
             order = np.random.default_rng([int(seed) & ((1 << 64) - 1), epoch]).permutation(len(source)).tolist()
+            order, step = _skip_batches(order, int(batch_size), step, int(first_step))
+            if not order:
+                continue
             loader = pool.iterate(order, batch_size) if pool is not None else Prefetcher(source, order, batch_size, device)
             for b in loader:
                 gp = b['gt_pose'] if 'gt_pose' in b else [i_['pose'] for i_ in b['items']]
@@ -613,19 +618,28 @@ def train_batches(source, cfg, batch_size, seed, epochs=1, device=None, num_work
             pool.close()
 
 
-def modelnet_train_batches(source, cfg, batch_size, seed, epochs=1, device=None):
+def _skip_batches(order, batch_size, step, first_step):
+    """An epoch's visiting order without the batches that lie before first_step, and the step its first remaining batch has."""
+    if step >= first_step:
+        return order, step
+    skip = min(first_step - step, -(-len(order) // batch_size))
+    return order[skip * batch_size:], step + skip
+
+
+def modelnet_train_batches(source, cfg, batch_size, seed, epochs=1, device=None, first_step=0):
     """Generator of ModelNet training batches over any indexable source of (n, 3) arrays (`source[i]`; further columns such as ModelNet40's
     normals are dropped, data_loaders/modelnet.py:176-177): the clouds of a batch go to the device in one pinned copy, then
     augment.modelnet_train_batch builds the cropped, moved, resampled, jittered and shuffled pairs with their masks and pose there.
     `step` counts up from 0 across epochs, so batch k of a run is a function of (source, seed, k) alone.  Every epoch visits every cloud
     once in an order drawn from (seed, epoch); a last short batch is yielded as it is.  Each batch goes straight into
     RegTR.training_step; 'ids' names its clouds.  (A 2048-point cloud is 24 KB: there is nothing for a loader pool to hide.  No HDF5
-    reader here: hand in the arrays.)"""
+    reader here: hand in the arrays.)  first_step: as train_batches'."""
     from .augment import modelnet_train_batch
     device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
     step = 0
     for epoch in range(int(epochs)):
         order = np.random.default_rng([int(seed) & ((1 << 64) - 1), epoch]).permutation(len(source)).tolist()
+        order, step = _skip_batches(order, int(batch_size), step, int(first_step))
         for lo in range(0, len(order), int(batch_size)):
             ids = order[lo:lo + int(batch_size)]
             clouds = [np.ascontiguousarray(np.asarray(source[i], dtype=np.float32)[:, :3]) for i in ids]
@@ -637,6 +651,111 @@ def modelnet_train_batches(source, cfg, batch_size, seed, epochs=1, device=None)
             out['ids'] = ids
             step += 1
             yield out
+
+
+# ------------------------------------------------------------------------------------------------------ the training loop
+class CheckpointSaver:
+    """The reference's CheckPointManager layout (cvhelpers/torch_helpers.py:98-193): `<dir>/model-<step>.pth`, one torch.save of
+    {'state_dict', 'step', 'optimizer', 'scheduler'}, and `<dir>/checkpoints.txt` whose first line is `Best step: N` (the step of the
+    highest score so far, the later one on a tie) followed by the kept files' names; the last max_to_keep checkpoints and the best one
+    are kept.  load() takes a file or such a directory (the best step's file then), as the reference's --resume does."""
+
+    def __init__(self, ckpt_dir, max_to_keep=3):
+        self.dir, self.max_to_keep = ckpt_dir, int(max_to_keep)
+        self.kept, self.best_score, self.best_step = [], None, None
+        os.makedirs(ckpt_dir, exist_ok=True)
+
+    def _path(self, step):
+        return os.path.join(self.dir, f'model-{step}.pth')
+
+    def save(self, model, step, score=0.0, **kwargs):
+        state = {'state_dict': {k: v for k, v in model.state_dict().items() if not v.is_sparse}, 'step': step}
+        for k, v in kwargs.items():
+            state[k] = v.state_dict() if getattr(v, 'state_dict', None) is not None else v
+        torch.save(state, self._path(step))
+        self.kept.append(step)
+        if self.best_score is None or score >= self.best_score:
+            old = self.best_step
+            self.best_score, self.best_step = score, step
+            if old is not None and old not in self.kept and os.path.exists(self._path(old)):
+                os.remove(self._path(old))
+        while len(self.kept) > self.max_to_keep:
+            gone = self.kept.pop(0)
+            if gone != self.best_step:
+                os.remove(self._path(gone))
+        with open(os.path.join(self.dir, 'checkpoints.txt'), 'w') as f:
+            f.write(f'Best step: {self.best_step}\n')
+            f.write('\n'.join(os.path.basename(self._path(k)) for k in self.kept))
+        return self._path(step)
+
+    @staticmethod
+    def load(path, model=None, map_location=None, **kwargs):
+        """-> the checkpoint's step.  model: load_state_dict(strict=False), as the reference; kwargs (optimizer=, scheduler=): their
+        load_state_dict with the entry of the same name, where the checkpoint has one."""
+        if os.path.isdir(path):
+            with open(os.path.join(path, 'checkpoints.txt')) as f:
+                line = f.readline()
+            if not line.startswith('Best'):
+                raise RuntimeError(f'{path}/checkpoints.txt is not in the expected format (first line: Best step: N)')
+            path = os.path.join(path, f'model-{int(line.split(":")[1])}.pth')
+        state = torch.load(path, map_location=map_location, weights_only=False)
+        if model is not None and 'state_dict' in state:
+            model.load_state_dict(state['state_dict'], strict=False)
+        for k, obj in kwargs.items():
+            if k in state and getattr(obj, 'load_state_dict', None) is not None:
+                obj.load_state_dict(state[k])
+        return int(state.get('step', 0))
+
+
+def train_loop(model, batches, steps, first_step=0, train_backbone=True, validate_every=0, val_batches=None, saver=None, logger=None,
+               log_every=50):
+    """The reference's training loop (trainer.py:95-161) without tqdm and tensorboard: for each of `steps` batches of the iterable
+    `batches` -- optimizer.zero_grad(), RegTR.training_step, backward, optimizer.step() (the gradient clip is inside it),
+    scheduler.step() -- with model.optimizer / model.scheduler from RegTR.configure_optimizers (called here if the model has none yet).
+    The global step starts at first_step (a resumed run: hand in batches that start there too).  Every loss key's running sum stays on
+    the device, and so does the smoothed total (0.99 / 0.01, a non-finite total left out, as the reference); ONE host read per
+    log_every steps prints it.  validate_every > 0 with val_batches (a callable returning an iterable of batches): every
+    validate_every-th global step runs validation_step over them, validation_epoch_end, and saver.save(model, step, score,
+    optimizer=, scheduler=) (a CheckpointSaver).  -> {'step', 'loss_smooth' (device scalar), 'loss_avg' {key: device scalar},
+    'scores' [(step, score)], 'validation' the last validation_epoch_end outputs}."""
+    if getattr(model, 'optimizer', None) is None:
+        model.configure_optimizers(train_backbone=train_backbone)
+    opt, sched = model.optimizer, model.scheduler
+    step = int(first_step)
+    sums, smooth, n_done, scores, last_val = {}, None, 0, [], None
+    it = iter(batches)
+    while n_done < int(steps):
+        try:
+            batch = next(it)
+        except StopIteration:
+            break
+        step += 1
+        opt.zero_grad()
+        _, losses = model.training_step(batch, step, train_backbone=train_backbone)
+        losses['total'].backward()
+        opt.step()
+        sched.step()
+        n_done += 1
+        with torch.no_grad():
+            for k, v in losses.items():
+                v = v.detach()
+                sums[k] = v.clone() if k not in sums else sums[k] + v
+            total = losses['total'].detach()
+            smooth = total.clone() if smooth is None else torch.where(torch.isfinite(total), 0.99 * smooth + 0.01 * total, smooth)
+        if logger is not None and (n_done == 1 or step % int(log_every) == 0):
+            logger.info(f'step {step}: smoothed total loss {smooth.item():.4g}, lr {opt.param_groups[0]["lr"]:.3g}')      # the one host read
+        if validate_every > 0 and val_batches is not None and step % int(validate_every) == 0:
+            outputs = [model.validation_step(vb, i) for i, vb in enumerate(val_batches())]
+            score, last_val = model.validation_epoch_end(outputs)
+            scores.append((step, score))
+            if logger is not None:
+                logger.info(f'validation at step {step}: score {score:.4f}, total loss {float(last_val["losses"]["total"]):.4g}')
+            if saver is not None:
+                path = saver.save(model, step, score, optimizer=opt, scheduler=sched)
+                if logger is not None:
+                    logger.info(f'Saved checkpoint: {path} (best step {saver.best_step})')
+    return {'step': step, 'loss_smooth': smooth, 'loss_avg': {k: v / max(n_done, 1) for k, v in sums.items()}, 'scores': scores,
+            'validation': last_val}
 
 
 # ------------------------------------------------------------------------------------------------------ the test loop

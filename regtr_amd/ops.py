@@ -3,6 +3,7 @@ stream only; every arithmetic step runs in libregtr_hip.so.  Nothing here synchr
 exception: `KdTree` (the reference-order parity mode) reads its row width back.  Every pointer handed to the library is checked
 for device, dtype and contiguity (_lib.ptr / iptr / bptr / dptr)."""
 import math
+import operator
 
 import torch
 
@@ -1230,3 +1231,150 @@ def pose_metrics(pred, gt):
     check(_lib.lib().regtr_pose_metrics(ptr(p) if n else None, ptr(gt) if n else None, gt.shape[1] * gt.shape[2], L, B,
                                         _lib.dptr(out) if n else None, ptr(comp) if n else None, stream()), 'regtr_pose_metrics')
     return (out, comp) if layered else (out[0], comp[0])
+
+
+# ------------------------------------------------------------------------------------------------ optimiser step (csrc/optim.hip)
+_OPTIM_DTYPE = None
+_T = torch.Tensor
+_dtype_of = operator.attrgetter('dtype')
+
+
+def _optim_all_ok(lists):
+    """True when every tensor of every list is a float32 tensor on the launch device (C-level passes: this runs over ~600 tensors on
+    every optimiser step); False sends the caller to the per-tensor checks, which say what is wrong."""
+    try:
+        dev = context.current().device_index
+        dev = dev if dev is not None else torch.cuda.current_device()
+        for lst in lists:
+            if set(map(_T.get_device, lst)) != {dev} or set(map(_dtype_of, lst)) != {torch.float32}:
+                return False
+    except (RuntimeError, TypeError, AttributeError, AssertionError):
+        return False
+    return True
+
+
+def _optim_table(grads, params=None, exp_avgs=None, exp_avg_sqs=None, scalars=None, what='optim'):
+    """The host array of regtr_optim_tensor_t the multi-tensor entry points read (include/regtr_hip.h), built afresh on every call, and
+    the list of gradient tensors it points at (kept alive by the caller until the launches are enqueued).  Every tensor is checked HERE,
+    with a Python exception: a GPU tensor on the launch device, float32; p, m, v contiguous; g of p's shape, m and v of p's element count
+    (a non-contiguous g is made contiguous)."""
+    global _OPTIM_DTYPE
+    import numpy as np
+    if _OPTIM_DTYPE is None:
+        _OPTIM_DTYPE = np.dtype([('p', np.uint64), ('g', np.uint64), ('m', np.uint64), ('v', np.uint64), ('n', np.int64),
+                                 ('scalars', np.float64, (7,))], align=True)
+        assert _OPTIM_DTYPE.itemsize == 96
+    n = len(grads)
+    state = params is not None
+    if state and not (len(params) == len(exp_avgs) == len(exp_avg_sqs) == len(scalars) == n):
+        raise RuntimeError(f'{what}: params, grads, exp_avgs, exp_avg_sqs and scalars must have one entry per tensor')
+    ok = n > 0 and _optim_all_ok((grads, params, exp_avgs, exp_avg_sqs) if state else (grads,))
+    if ok and state:
+        ns = list(map(_T.numel, grads))
+        ok = (all(map(_T.is_contiguous, params)) and all(map(_T.is_contiguous, exp_avgs)) and all(map(_T.is_contiguous, exp_avg_sqs))
+              and list(map(_T.numel, exp_avgs)) == ns == list(map(_T.numel, exp_avg_sqs)) and list(map(_T.size, grads)) == list(map(_T.size, params)))
+    if not ok:
+        _optim_explain(grads, params, exp_avgs, exp_avg_sqs, what)
+    keep = grads if all(map(_T.is_contiguous, grads)) else [g if g.is_contiguous() else g.contiguous() for g in grads]
+    tab = np.zeros(n, dtype=_OPTIM_DTYPE)
+    tab['g'] = list(map(_T.data_ptr, keep))
+    tab['n'] = list(map(_T.numel, keep))
+    if state:
+        tab['p'] = list(map(_T.data_ptr, params))
+        tab['m'] = list(map(_T.data_ptr, exp_avgs))
+        tab['v'] = list(map(_T.data_ptr, exp_avg_sqs))
+        if n:
+            tab['scalars'] = np.asarray(scalars, dtype=np.float64).reshape(n, 7)
+    return tab, keep
+
+
+def _optim_explain(grads, params, exp_avgs, exp_avg_sqs, what):
+    """The per-tensor checks, with the reason: raises, or returns when every tensor is acceptable after all."""
+    dev = context.current().device_index
+
+    def checked(t, name, i, contiguous):
+        nonlocal dev
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f'{what}: {name}[{i}] must be a GPU tensor (got {getattr(t, "device", type(t))}); there is no CPU fallback')
+        if dev is None:
+            dev = torch.cuda.current_device()
+        if t.dtype is not torch.float32:
+            raise RuntimeError(f'{what}: {name}[{i}] must be float32, got {t.dtype} (the kernels reinterpret nothing)')
+        if t.get_device() != dev:
+            raise RuntimeError(f'{what}: {name}[{i}] is on {t.device} but the launch device is cuda:{dev}; wrap the call in '
+                               'regtr_amd._lib.on_device(tensor.device)')
+        if contiguous and not t.is_contiguous():
+            raise RuntimeError(f'{what}: {name}[{i}] must be contiguous (the kernel writes it in place)')
+        return t
+
+    for i in range(len(grads)):
+        g = checked(grads[i], 'grads', i, False)
+        if params is not None:
+            p = checked(params[i], 'params', i, True)
+            m, v = checked(exp_avgs[i], 'exp_avgs', i, True), checked(exp_avg_sqs[i], 'exp_avg_sqs', i, True)
+            if g.shape != p.shape or m.numel() != p.numel() or v.numel() != p.numel():
+                raise RuntimeError(f'{what}: tensor {i}: the gradient {tuple(g.shape)} must have the parameter\'s shape {tuple(p.shape)} and the '
+                                   f'moments {tuple(m.shape)}, {tuple(v.shape)} its element count')
+
+
+def optim_slices():
+    """(elements per float64 partial of grad_sumsq, elements per workgroup of adam_step, tensors per launch) -- tests straddle them."""
+    L = _lib.lib()
+    return int(L.regtr_optim_norm_slice()), int(L.regtr_optim_step_slice()), int(L.regtr_optim_chunk_tensors())
+
+
+_optim_norm_slice = None
+
+
+def _sumsq(tab, keep):
+    global _optim_norm_slice
+    if _optim_norm_slice is None:
+        _optim_norm_slice = int(_lib.lib().regtr_optim_norm_slice())
+    sl = _optim_norm_slice
+    n_part = int(((tab['n'] + (sl - 1)) // sl).sum())
+    dev = keep[0].device if keep else torch.device('cuda', torch.cuda.current_device())
+    partials = torch.empty(n_part, dtype=torch.float64, device=dev)
+    check(_lib.lib().regtr_grad_sumsq(tab.ctypes.data if len(keep) else None, len(keep), dptr(partials) if n_part else None, n_part, stream()),
+          'regtr_grad_sumsq')
+    return partials
+
+
+def grad_sumsq(grads):
+    """First half of the global gradient norm (regtr_grad_sumsq): grads, a list of float32 GPU tensors -> (P,) float64 partial sums of
+    squares, one per norm slice of every tensor in list order -- a function of the tensors' lengths alone.  Refused with a Python
+    exception: CPU tensors, tensors that are not float32.  A non-contiguous gradient is made contiguous."""
+    return _sumsq(*_optim_table(grads, what='grad_sumsq'))
+
+
+def grad_norm_finish(partials, max_norm):
+    """Second half (regtr_grad_norm_finish): (P,) float64 partials -> (2,) float32 device tensor [total_norm, clip_coef], clip_coef =
+    min(1, max_norm / (total_norm + 1e-6)) as torch.nn.utils.clip_grad_norm_; max_norm <= 0: no clipping (coef 1).  No host read."""
+    out = torch.empty(2, dtype=torch.float32, device=partials.device)
+    n = partials.numel()
+    check(_lib.lib().regtr_grad_norm_finish(dptr(partials) if n else None, n, float(max_norm), ptr(out), stream()), 'regtr_grad_norm_finish')
+    return out
+
+
+def adam_step(params, grads, exp_avgs, exp_avg_sqs, scalars, clip_coef=None, decoupled=True):
+    """torch's single-tensor AdamW (decoupled) / Adam step on every tensor in place (regtr_adam_step).  scalars: per tensor (lr,
+    weight_decay, beta1, beta2, eps, bias_correction1 = 1 - beta1^t, sqrt(bias_correction2) = sqrt(1 - beta2^t)), host float64.
+    clip_coef: a 1-element float32 device tensor the kernel multiplies every gradient by (grad_norm_finish(...)[1:]), None = 1; the
+    gradients themselves are not modified.  The kernel writes through raw pointers: the CALLER advances the tensors' version counters
+    (regtr_amd.optim.FusedAdamW does).  Refused with a Python exception: CPU tensors; tensors that are not float32; a non-contiguous
+    parameter or moment; a gradient whose shape, or a moment whose element count, differs from its parameter's.  A non-contiguous
+    gradient is made contiguous."""
+    tab, keep = _optim_table(grads, params, exp_avgs, exp_avg_sqs, scalars, what='adam_step')
+    if clip_coef is not None and clip_coef.numel() != 1:
+        raise RuntimeError(f'adam_step: clip_coef must hold one float32, got {tuple(clip_coef.shape)}')
+    check(_lib.lib().regtr_adam_step(tab.ctypes.data if len(keep) else None, len(keep), ptr(clip_coef), 1 if decoupled else 0, stream()),
+          'regtr_adam_step')
+
+
+def clip_adam_step(params, grads, exp_avgs, exp_avg_sqs, scalars, max_norm, decoupled=True):
+    """grad_sumsq, grad_norm_finish(max_norm) and adam_step with the coefficient it left on the device, over ONE table of the tensors
+    (checked once) -> the (2,) float32 device tensor [total_norm before clipping, clip_coef].  What FusedAdamW.step runs."""
+    tab, keep = _optim_table(grads, params, exp_avgs, exp_avg_sqs, scalars, what='clip_adam_step')
+    norm_coef = grad_norm_finish(_sumsq(tab, keep), max_norm)
+    check(_lib.lib().regtr_adam_step(tab.ctypes.data if len(keep) else None, len(keep), ptr(norm_coef[1:]), 1 if decoupled else 0, stream()),
+          'regtr_adam_step')
+    return norm_coef

@@ -9,7 +9,8 @@ regtr_circle_rows (`feature_loss_type: circle`, CircleLossFull with no parameter
 regtr_loss_terms.  `training_step(batch)` trains everything above a frozen KPConv backbone (feat_proj, the cross-encoder, the
 correspondence head, the InfoNCE W) with HIP backward kernels: forward_grad / compute_loss_grad / trainable_parameters;
 `training_step(batch, train_backbone=True)` also trains the 11 KPConv blocks (KPFEncoder.forward_grad, regtr_amd/encoder_grad.py) --
-every parameter the reference trains.  An optimiser loop is not implemented.  `validation_step` / `validation_epoch_end` / `test_step`
+every parameter the reference trains.  `configure_optimizers` sets the reference's optimiser and scheduler (regtr_amd/optim.py: the fused
+clip + AdamW step; harness.train_loop / train.py run the loop).  `validation_step` / `validation_epoch_end` / `test_step`
 are the reference's (generic_reg_model.py:82-104, 130-158) with the registration metrics computed on the device (regtr_amd/metrics.py).
 
 The forward enqueues every stage on the current HIP stream with ONE host synchronisation (the data-dependent level
@@ -597,11 +598,39 @@ class RegTR(nn.Module):
             params += [p for p in self.kpf_encoder.parameters() if p.requires_grad]
         return params
 
+    def configure_optimizers(self, train_backbone=True):
+        """generic_reg_model.py:28-62: sets self.optimizer and self.scheduler from cfg.optimizer ('AdamW' | 'Adam'), cfg.base_lr,
+        cfg.weight_decay, cfg.grad_clip and cfg.scheduler ('step': StepLR(*cfg.scheduler_param); 'none' / absent: StepLR(50, 1.0);
+        'warmup' is not implemented: no shipped config uses it).  The optimiser is regtr_amd.optim.FusedAdamW over
+        list(self.parameters()) in that order -- the reference builds its own over self.parameters() too, so the indices of the
+        optimiser's state_dict are the reference's; the frozen kernel_points (and, with train_backbone=False, the backbone's weights)
+        sit in the list and never get a gradient, hence no state.  The reference's clip_grad_norm_(model.parameters(), cfg.grad_clip)
+        lives in the optimiser (max_grad_norm), so a step is: optimizer.zero_grad(), training_step(batch,
+        train_backbone=train_backbone), losses['total'].backward(), optimizer.step(), scheduler.step()."""
+        from .optim import FusedAdamW
+        cfg = self.cfg
+        scheduler_type = cfg.get('scheduler', None)
+        if scheduler_type == 'warmup':
+            raise NotImplementedError("scheduler 'warmup' is not implemented (no shipped config uses it)")
+        if scheduler_type not in (None, 'none', 'step'):
+            raise NotImplementedError(f'scheduler {scheduler_type!r}')
+        if cfg.optimizer not in ('AdamW', 'Adam'):
+            raise NotImplementedError(f'optimizer {cfg.optimizer!r}: choose AdamW or Adam')
+        self.trainable_parameters(backbone=train_backbone)          # turns requires_grad on for the two InfoNCE W
+        self.optimizer = FusedAdamW(list(self.parameters()), lr=cfg.base_lr, weight_decay=cfg.weight_decay,
+                                    max_grad_norm=cfg.get('grad_clip', 0.0), decoupled=cfg.optimizer == 'AdamW')
+        if scheduler_type == 'step':
+            self.scheduler = torch.optim.lr_scheduler.StepLR(self.optimizer, cfg.scheduler_param[0], cfg.scheduler_param[1])
+        else:
+            self.scheduler = torch.optim.lr_scheduler.StepLR(self.optimizer, 50, 1.0)
+        self.logger.info(f'Using optimizer {self.optimizer} with scheduler {self.scheduler}')
+        return self.optimizer, self.scheduler
+
     def training_step(self, batch, batch_idx=None, train_backbone=False):
         """generic_reg_model.py:64-66 of the reference: pred = forward_grad(batch), losses = compute_loss_grad(pred, batch) ->
-        (pred, losses); the caller runs losses['total'].backward() and steps its optimiser over trainable_parameters().  By default
+        (pred, losses); the caller runs losses['total'].backward() and steps its optimiser (configure_optimizers).  By default
         the backbone is frozen: kpf_encoder's parameters end with grad None.  train_backbone=True trains it too (forward_grad's
-        train_backbone; step over trainable_parameters(backbone=True))."""
+        train_backbone)."""
         pred = self.forward_grad(batch, train_backbone=train_backbone)
         return pred, self.compute_loss_grad(pred, batch)
 

@@ -147,3 +147,19 @@ def synth_modelnet_pair(pair_id, num_points=1024, keep=0.7, return_pose=False):
     if return_pose:
         return src.astype(np.float32), tgt.astype(np.float32), np.concatenate([R, t[:, None]], 1).astype(np.float32)
     return src.astype(np.float32), tgt.astype(np.float32)
+
+
+def synth_modelnet_cloud(cloud_id, num_points=2048):
+    """A seeded raw ModelNet40-like cloud for training input (train.py --synthetic with a ModelNet config): num_points points on a box
+    and a sphere inside the unit ball (ModelNet40's normalisation), in random order; (num_points, 3) float32, a function of cloud_id."""
+    rng = np.random.default_rng([7919, int(cloud_id)])
+    a = num_points // 2
+    dims = rng.uniform(0.3, 1.0, 3)
+    box = rng.uniform(-0.5, 0.5, (a, 3)) * dims
+    face = rng.integers(0, 3, a)
+    box[np.arange(a), face] = np.sign(box[np.arange(a), face]) * 0.5 * dims[face]
+    v = rng.standard_normal((num_points - a, 3))
+    ball = rng.uniform(0.2, 0.4) * v / np.linalg.norm(v, axis=1, keepdims=True) + rng.uniform(-0.25, 0.25, 3)
+    pts = np.concatenate([box, ball])
+    pts /= max(1.0, float(np.linalg.norm(pts, axis=1).max()))
+    return pts.astype(np.float32)[rng.permutation(num_points)]

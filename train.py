@@ -1,0 +1,169 @@
+"""Training entry point: the reference's loop (src/train.py, src/trainer.py:95-161) on the MI355X-native model.
+
+    python train.py --config CFG [--logdir DIR] [--dev] [--name NAME] [--num_workers N] [--resume CKPT_OR_DIR]
+                    [--batch B] [--steps K] [--validate_every V] [--seed S] [--freeze_backbone]
+                    [--synthetic N | --data_root ROOT --info TRAIN_INFO.pkl]
+
+Every step: device-side training batch (regtr_amd.augment), RegTR.training_step, backward, the fused clip + AdamW step
+(regtr_amd.optim.FusedAdamW, from RegTR.configure_optimizers) and StepLR.  Every --validate_every steps: validation_step over the
+validation batches, validation_epoch_end, and a checkpoint `<log>/ckpt/model-<step>.pth` = {'state_dict', 'step', 'optimizer',
+'scheduler'} with `<log>/ckpt/checkpoints.txt` (first line `Best step: N`), the reference's CheckPointManager layout.  --resume takes such
+a file or folder and restores model, optimiser, scheduler and the global step; the batches continue at that step of the (seed, step)
+sequence, so a resumed run computes what the unbroken one does.
+
+--synthetic N: N seeded synthetic training items (3DMatch config: SyntheticPairs; ModelNet config: 2048-point clouds) and N // 4 (at
+least 1) more for validation.  Real data: 3DMatch through --data_root / --info (the reference's train_info.pkl layout; validation then
+needs --val_info); ModelNet HDF5 reading is not built (h5py is not a dependency): hand arrays to harness.modelnet_train_batches.
+No tensorboard summaries.  Validation batches go through the same augmentation chain as training ones, at a fixed seed."""
+import argparse
+import logging
+import os
+import sys
+import time
+
+os.environ.setdefault('OMP_WAIT_POLICY', 'PASSIVE')      # idle OpenMP workers must not spin against a cgroup CPU quota
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+parser = argparse.ArgumentParser()
+parser.add_argument('--config', type=str, help='Path to the config file.')
+parser.add_argument('--logdir', type=str, default='../logs', help='Directory to store logs, summaries, checkpoints.')
+parser.add_argument('--dev', action='store_true', help='If true, will ignore logdir and log to ../logdev instead')
+parser.add_argument('--name', type=str, help='Prefix to add to logging directory')
+parser.add_argument('--num_workers', type=int, default=-1, help='loader processes of the 3DMatch pair source (-1: 4; 0: one loader thread)')
+parser.add_argument('--resume', type=str, help='Checkpoint file, or a folder with checkpoints.txt (its best step), to resume from')
+parser.add_argument('--batch', type=int, default=0, help='items per training batch (default: cfg.train_batch_size, else 1)')
+parser.add_argument('--synthetic', type=int, default=0, help='train on N seeded synthetic items instead of dataset files')
+parser.add_argument('--data_root', type=str, default=None, help='overrides cfg.root (3DMatch)')
+parser.add_argument('--info', type=str, default=None, help='3DMatch training info pickle')
+parser.add_argument('--val_info', type=str, default=None, help='3DMatch validation info pickle')
+parser.add_argument('--steps', type=int, default=100, help='training steps of this run (after --resume: further steps)')
+parser.add_argument('--validate_every', type=int, default=0, help='validate and save a checkpoint every this many global steps (0: never)')
+parser.add_argument('--seed', type=int, default=0, help='seed of the batch order and the augmentation draws')
+parser.add_argument('--freeze_backbone', action='store_true', help='train only what sits above the KPConv backbone')
+parser.add_argument('--log_every', type=int, default=50)
+
+
+def prepare_logger(opt):
+    """cvhelpers.misc.prepare_logger: <logdir>/<yymmdd_HHMMSS>[_name] (or ../logdev with --dev), log.txt inside."""
+    if opt.dev:
+        log_path = '../logdev'
+    else:
+        stamp = time.strftime('%y%m%d_%H%M%S')
+        log_path = os.path.join(opt.logdir, stamp if not opt.name else f'{stamp}_{opt.name}')
+    os.makedirs(log_path, exist_ok=True)
+    logger = logging.getLogger('regtr_amd.train')
+    logger.setLevel(logging.INFO)
+    for h in (logging.StreamHandler(), logging.FileHandler(os.path.join(log_path, 'log.txt'))):
+        h.setFormatter(logging.Formatter('%(asctime)s [%(levelname)s] %(message)s'))
+        logger.addHandler(h)
+    return logger, log_path
+
+
+class _SyntheticClouds:
+    """Indexable source of seeded raw ModelNet-like clouds (regtr_amd.synthetic.synth_modelnet_cloud)."""
+
+    def __init__(self, n, first=0):
+        self.n, self.first = n, first
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        from regtr_amd.synthetic import synth_modelnet_cloud
+        return synth_modelnet_cloud(self.first + i)
+
+
+def main():
+    opt = parser.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit('regtr_amd runs on an MI355X (HIP) device only; there is no CPU path')
+    if opt.config is None:
+        if opt.resume is None or not os.path.exists(opt.resume):
+            sys.exit('--config needs to be supplied unless resuming from checkpoint')
+        folder = opt.resume if os.path.isdir(opt.resume) else os.path.dirname(opt.resume)
+        opt.config = os.path.normpath(os.path.join(folder, '../config.yaml'))
+        if not os.path.exists(opt.config):
+            sys.exit('Config not found in resume directory')
+    logger, log_path = prepare_logger(opt)
+    with open(opt.config, 'r') as fin:
+        text = fin.read()
+    if os.path.abspath(opt.config) != os.path.abspath(os.path.join(log_path, 'config.yaml')):
+        with open(os.path.join(log_path, 'config.yaml'), 'w') as fout:
+            fout.write(f'# Original file name: {opt.config}\n' + text)
+
+    from regtr_amd import RegTR, harness, load_config
+    torch.set_num_threads(max(1, min(torch.get_num_threads(), harness.usable_cores() // 2, 8)))
+    cfg = load_config(opt.config)
+    device = torch.device('cuda', 0)
+    batch = opt.batch if opt.batch > 0 else int(cfg.get('train_batch_size', 1))
+    modelnet = cfg.dataset == 'modelnet'
+    workers = opt.num_workers if opt.num_workers >= 0 else 4
+
+    # sources
+    if opt.synthetic > 0:
+        n_val = max(1, opt.synthetic // 4)
+        if modelnet:
+            source, val_source = _SyntheticClouds(opt.synthetic), _SyntheticClouds(n_val, first=1 << 20)
+        else:
+            source, val_source = harness.SyntheticPairs(opt.synthetic), harness.SyntheticPairs(n_val, pairs_per_scene=1)
+    elif modelnet:
+        logger.error('ModelNet HDF5 reading is not built (h5py is not a dependency); use --synthetic N or harness.modelnet_train_batches')
+        sys.exit(-4)
+    else:
+        cfg_root = cfg.get('root', None)
+        roots = [opt.data_root] if opt.data_root else ([cfg_root] if isinstance(cfg_root, str) else list(cfg_root or []))
+        root = next((r for r in roots if os.path.exists(r)), None)
+        if root is None or not opt.info or not os.path.exists(opt.info):
+            logger.error(f'Dataset not found (info {opt.info}, roots {roots}); pass --data_root and --info, or use --synthetic N')
+            sys.exit(-4)
+        source = harness.ThreeDMatchPairs(opt.info, root)
+        val_source = harness.ThreeDMatchPairs(opt.val_info, root) if opt.val_info else None
+
+    # loader processes of the pair source: forked before this process holds a HIP context (as test.py)
+    pool = None
+    if not modelnet and workers > 0:
+        import atexit
+        pool = harness.LoaderPool(None, device, workers=workers, max_batch=batch)
+        atexit.register(pool.close)
+    torch.cuda.set_device(device)
+    if pool is not None:
+        pool.set_source(source)
+        pool.prepare()
+
+    torch.manual_seed(opt.seed)          # the initial weights (and numpy: the kernel points' random rotation) follow --seed, as setup_seed
+    np.random.seed(opt.seed % (1 << 32))
+    model = RegTR(cfg).to(device)
+    model.configure_optimizers(train_backbone=not opt.freeze_backbone)
+    first_step = 0
+    if opt.resume:
+        first_step = harness.CheckpointSaver.load(opt.resume, model, map_location=device, optimizer=model.optimizer, scheduler=model.scheduler)
+        logger.info(f'Resumed from {opt.resume} at step {first_step}')
+
+    per_epoch = -(-len(source) // batch)
+    epochs = -(-(first_step + opt.steps) // per_epoch)
+    if modelnet:
+        batches = harness.modelnet_train_batches(source, cfg, batch, opt.seed, epochs=epochs, device=device, first_step=first_step)
+        val_batches = lambda: harness.modelnet_train_batches(val_source, cfg, batch, opt.seed + 1, epochs=1, device=device)
+    else:
+        batches = harness.train_batches(source, cfg, batch, opt.seed, epochs=epochs, device=device, num_workers=workers, loader_pool=pool,
+                                        first_step=first_step)
+        val_batches = (lambda: harness.train_batches(val_source, cfg, batch, opt.seed + 1, epochs=1, device=device, num_workers=0)) \
+            if val_source is not None else None
+    saver = harness.CheckpointSaver(os.path.join(log_path, 'ckpt')) if opt.validate_every > 0 else None
+    t0 = time.perf_counter()
+    out = harness.train_loop(model, batches, opt.steps, first_step=first_step, train_backbone=not opt.freeze_backbone,
+                             validate_every=opt.validate_every, val_batches=val_batches, saver=saver, logger=logger, log_every=opt.log_every)
+    torch.cuda.synchronize(device)
+    dt = time.perf_counter() - t0
+    avg = ', '.join(f'{k} {float(v):.4g}' for k, v in out['loss_avg'].items())
+    logger.info(f'Ending training. Number of training steps = {out["step"]} ({out["step"] - first_step} in {dt:.1f} s); average losses: {avg}')
+
+
+if __name__ == '__main__':
+    main()
