@@ -32,6 +32,7 @@
  *   regtr_encoder_fwd         KPFEncoder.forward (blocks sequenced) models/backbone_kpconv/kpconv.py:81-88, kpconv_blocks.py:632-646,706-741
  *   regtr_layernorm           nn.LayerNorm (+ with_pos_embed)     transformers.py:116-119,194-195,213-215,232
  *   regtr_posemb_sine         PositionEmbeddingCoordsSine.forward models/transformer/position_embedding.py:29-50
+ *   regtr_posemb_mlp          PositionEmbeddingLearned.forward    models/transformer/position_embedding.py:53-72
  *   regtr_mha_fwd             nn.MultiheadAttention core          transformers.py:197-226
  *   regtr_attn_xyz            CorrespondenceDecoder.simple_attention   models/regtr.py:316-351
  *   regtr_weighted_procrustes pose assembly + compute_rigid_transform   regtr.py:185-203, utils/se3_torch.py:108-154
@@ -303,6 +304,19 @@ int regtr_layernorm(const float* x, int n, int D, const float* gamma, const floa
 
 int regtr_posemb_sine(const float* xyz, int n, int npf, int d_model, float scale, const float* dim_t, float* pe,
                       void* stream);
+
+/* pe [n, d_model] = L5(relu(L4(relu(L3(relu(L2(relu(L1(xyz))))))))), the learned positional embedding's five-Linear ReLU MLP
+ * 3 -> 32 -> 64 -> 128 -> 256 -> d_model, in one launch: a workgroup owns 32 rows and keeps the hidden activations in LDS.  xyz [n, 3]
+ * (12-byte rows, 4-byte aligned).  w_kn / bias: HOST arrays of the five layers' DEVICE pointers, the weights transposed to (K, N) layout:
+ * (3, 32), (32, 64), (64, 128), (128, 256), (256, d_model).  acts (optional) [n, 480] = h1 | h2 | h3 | h4, the activations after their
+ * ReLUs (what the backward reads); pe does not depend on it being asked for.  Float32 throughout with float32's operand range: L1 on
+ * vector FMAs, the others on the exact-f32 MFMA, per element one fmaf chain in k order from zero, + bias, ReLU (v < 0 ? 0 : v: a NaN
+ * stays a NaN) -- a row's result is a function of that row and the weights only.  No atomics, no workspace, bit-reproducible.  Rows >= n
+ * of pe / acts are not written.  n = 0: REGTR_OK, nothing launched.  Refused (REGTR_ERR_ARG, nothing read or launched): n < 0, d_model
+ * not a multiple of 64 in [64, 512], w_kn / bias or one of their entries NULL, xyz or pe NULL with n > 0, a weight / bias / pe / acts
+ * pointer that is not 16-byte aligned, xyz not 4-byte aligned. */
+int regtr_posemb_mlp(const float* xyz, int n, const float* const* w_kn, const float* const* bias, int d_model, float* pe, float* acts,
+                     void* stream);
 
 /* ---- attention + pose -------------------------------------------------------------------------------------- */
 

@@ -23,6 +23,7 @@ _F = _c.c_float
 _Z = _c.c_size_t
 _U64 = _c.c_uint64
 _U32 = _c.c_uint32
+_P5 = _c.POINTER(_c.c_void_p * 5)       # a host array of five device pointers (regtr_posemb_mlp's layers)
 
 class Weight(_c.Structure):
     """regtr_weight_t (include/regtr_hip.h)."""
@@ -95,6 +96,7 @@ SIGNATURES = {
     'regtr_add_f32': (_I, [_P, _P, _Z, _P, _P]),
     'regtr_layernorm': (_I, [_P, _I, _I, _P, _P, _F, _P, _P, _P, _P]),
     'regtr_posemb_sine': (_I, [_P, _I, _I, _I, _F, _P, _P, _P]),
+    'regtr_posemb_mlp': (_I, [_P, _I, _P5, _P5, _I, _P, _P, _P]),
     'regtr_mha_fwd': (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _F, _I, _P, _P]),
     'regtr_cross_encoder_per_layer_params': (_I, []),
     'regtr_cross_encoder_supported': (_I, [_I, _I, _I, _I]),

@@ -95,11 +95,52 @@ def regressor_forward_grad(head, feats):
     return corr.view(Lyr, N, 3), logit.view(Lyr, N)
 
 
+class _PosembMLP(torch.autograd.Function):
+    """(xyz (n, 3), the five Linears' weight and bias) -> pe (n, d_model) by ops.posemb_mlp with save=True: one launch, the four
+    activations after their ReLUs kept as one (n, 480) buffer.  Backward: transformer_grad.linear_bwd per layer, last to first, on
+    column views of that buffer -- the ReLU mask and the bias sums by ops.bias_relu_bwd, dX by ops.gemm on a (K, N)-layout SplitWeight,
+    dW by ops.gemm_tn / ops.gemm_tn_any.  No dX for the first layer: xyz takes no gradient."""
+
+    @staticmethod
+    def forward(ctx, xyz, w0, b0, w1, b1, w2, b2, w3, b3, w4, b4, module):
+        pe, acts = ops.posemb_mlp(xyz, module._weights(), save=True)
+        ctx.save_for_backward(xyz, acts, w0, w1, w2, w3, w4)
+        ctx.cache = module._cache
+        return pe
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dpe):
+        xyz, acts, *w = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        g = _rows(dpe)
+        c = (0, 32, 96, 224, 480)
+        h = [acts[:, c[l]:c[l + 1]] for l in range(4)]
+        a = [xyz] + h
+        grads = [None] * 10
+        with context.ForwardContext(xyz.device):
+            for l in (4, 3, 2, 1, 0):
+                g, grads[2 * l], grads[2 * l + 1] = linear_bwd(a[l], w[l], ctx.cache, (('bwd', l), 'kn'), g, h[l] if l < 4 else None,
+                                                               (l > 0, need[1 + 2 * l], need[2 + 2 * l]))
+        return (None, *grads, None)
+
+
+def posemb_forward_grad(module, xyz):
+    """PositionEmbeddingLearned.forward_grad: xyz (n, 3) -> pe (n, d_model), the bits of module(xyz)."""
+    if not isinstance(xyz, torch.Tensor) or xyz.device.type != 'cuda':
+        raise RuntimeError(f'forward_grad: xyz must be a GPU tensor (got {getattr(xyz, "device", type(xyz))}); there is no CPU fallback')
+    if xyz.requires_grad:
+        raise NotImplementedError('forward_grad: xyz.requires_grad (a gradient with respect to the coordinates) is not implemented')
+    lin = module.linears()
+    return _PosembMLP.apply(xyz, *[t for m in lin for t in (m.weight, m.bias)], module)
+
+
 def stack_forward_grad(feat_proj, pos_embed, encoder, head, feats_un, xyz, seg_off, kv_self, kv_cross, max_len, head_layers, cache=None):
     """Everything above the backbone on packed tokens (regtr.py:145-168 of the reference), differentiable in feats_un and in every
     parameter of feat_proj, encoder and head:
         both_feats_un = feat_proj(feats_un)                                 (N, D)      a transformer_grad._Linear
-        pe            = pos_embed(xyz)                                      (N, D)      no gradient; pos_embed None: no embedding
+        pe            = pos_embed(xyz)                                      (N, D)      pos_embed None: no embedding; the sine table takes no
+                                                                                        gradient, the learned MLP runs pos_embed.forward_grad(xyz)
         feats_cond    = encoder.forward_grad(both_feats_un, pe, ...)        (L, N, D)
         corr, logit   = head.forward_grad(feats_cond[head_layers])          (L', N, 3), (L', N)
     head_layers: the decoder layers a loss reads, ascending; the head runs on those only, so a layer no loss reads costs no head
@@ -125,8 +166,12 @@ def stack_forward_grad(feat_proj, pos_embed, encoder, head, feats_un, xyz, seg_o
     both_feats_un = _Linear.apply(feats_un, feat_proj.weight, feat_proj.bias, None, sw, cache, ('feat_proj', 'kn'), 3, False)
     pe = None
     if pos_embed is not None:
-        with torch.no_grad():
-            pe = pos_embed(xyz)
+        if isinstance(pos_embed, torch.nn.Module) and next(pos_embed.parameters(), None) is not None:
+            # the learned embedding: dpe, summed over the LN(x) + pe sites of the layers, trains it
+            pe = pos_embed.forward_grad(xyz)
+        else:
+            with torch.no_grad():
+                pe = pos_embed(xyz)
     feats_cond = encoder.forward_grad(both_feats_un, pe, seg_off, kv_self, kv_cross, max_len)
     lo, hi = head_layers[0], head_layers[-1]
     sel = feats_cond[lo:hi + 1] if hi - lo + 1 == len(head_layers) else torch.stack([feats_cond[l] for l in head_layers])

@@ -467,6 +467,61 @@ def posemb_sine(xyz, d_model, scale=1.0, temperature=10000):
     return pe
 
 
+POSEMB_MLP_WIDTHS = (3, 32, 64, 128, 256)      # the input widths of PositionEmbeddingLearned's five Linears (the last one's output: d_model)
+POSEMB_MLP_ACTS = 480                          # 32 + 64 + 128 + 256: h1 | h2 | h3 | h4, the row of the saved-activations buffer
+# A-B switch of the learned positional embedding: regtr_posemb_mlp (one launch, the hidden activations stay in LDS), or the same MLP
+# composed from five ops.gemm calls on the exact-f32 kernel (tools/posemb_mlp_bench.py measures both; docs/KERNELS.md)
+use_fused_posemb_mlp = True
+
+
+def _posemb_mlp_check(xyz, weights):
+    if not isinstance(xyz, torch.Tensor) or xyz.device.type != 'cuda':
+        raise RuntimeError(f'posemb_mlp: xyz must be a GPU tensor (got {getattr(xyz, "device", type(xyz))}); there is no CPU fallback')
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise RuntimeError(f'posemb_mlp: xyz must be (n, 3), got {tuple(xyz.shape)}')
+    if len(weights) != 5:
+        raise RuntimeError(f'posemb_mlp: five (weight (K, N), bias (N,)) pairs are needed, got {len(weights)}')
+    d_model = int(weights[4][0].shape[1])
+    widths = POSEMB_MLP_WIDTHS + (d_model,)
+    for l, (w, b) in enumerate(weights):
+        if tuple(w.shape) != (widths[l], widths[l + 1]) or tuple(b.shape) != (widths[l + 1],):
+            raise RuntimeError(f'posemb_mlp: layer {l} must be a ({widths[l]}, {widths[l + 1]}) weight in (K, N) layout and a '
+                               f'({widths[l + 1]},) bias, got {tuple(w.shape)} and {tuple(b.shape)}')
+    return d_model
+
+
+def posemb_mlp(xyz, weights, save=False):
+    """PositionEmbeddingLearned.forward (position_embedding.py:53-72) in one launch (regtr_posemb_mlp): xyz (n, 3), weights five
+    (w (K, N) float32 -- the Linear's weight transposed --, bias (N,)) pairs of the MLP 3 -> 32 -> 64 -> 128 -> 256 -> d_model -> pe
+    (n, d_model).  save=True -> (pe, acts): acts (n, 480) = h1 | h2 | h3 | h4, the activations after their ReLUs; pe is the same bits
+    either way.  Exact float32 (vector FMAs / the f32 MFMA), float32's operand range.  Nothing here synchronises."""
+    if not use_fused_posemb_mlp:
+        return posemb_mlp_composed(xyz, weights, save)
+    d_model = _posemb_mlp_check(xyz, weights)
+    n = xyz.shape[0]
+    pe = torch.empty((n, d_model), dtype=torch.float32, device=xyz.device)
+    acts = torch.empty((n, POSEMB_MLP_ACTS), dtype=torch.float32, device=xyz.device) if save else None
+    w5 = (_lib._c.c_void_p * 5)(*[ptr(w) for w, _ in weights])
+    b5 = (_lib._c.c_void_p * 5)(*[ptr(b) for _, b in weights])
+    check(_lib.lib().regtr_posemb_mlp(ptr(xyz), n, w5, b5, d_model, ptr(pe), ptr(acts), stream()), 'regtr_posemb_mlp')
+    return (pe, acts) if save else pe
+
+
+def posemb_mlp_composed(xyz, weights, save=False):
+    """posemb_mlp from five ops.gemm calls on the exact-f32 kernel (regtr_gemm_f32 takes K = 3), the ReLUs in the epilogues; with save the
+    four activations are written as the column blocks of one (n, 480) buffer, as regtr_posemb_mlp lays them out."""
+    d_model = _posemb_mlp_check(xyz, weights)
+    n = xyz.shape[0]
+    acts = torch.empty((n, POSEMB_MLP_ACTS), dtype=torch.float32, device=xyz.device) if save else None
+    h, c0 = xyz, 0
+    for w, b in weights[:4]:
+        N = w.shape[1]
+        h = gemm(h, w, bias=b, relu=True, out=acts[:, c0:c0 + N] if save else None)
+        c0 += N
+    pe = gemm(h, weights[4][0], bias=weights[4][1])
+    return (pe, acts) if save else pe
+
+
 # ------------------------------------------------------------------------------------------------ KPConv encoder
 def kpconv(q_xyz, s_xyz, nbr, x, w_flat, kernel_points, extent, x_stats=None, s_seg_off=None, q_seg_off=None, slope=0.1,
            want_stats=None, xyzf=None):
@@ -811,16 +866,27 @@ def circle_bwd(anc, pos, anc_xyz, pos_xyz, anc_seg_off, pos_seg_off, max_anc, ma
 def gemm_tn(a, b, fold=False):
     """a (M, N1)^T @ b (M, N2) -> (N1, N2) over a tall M (regtr_gemm_tn: split-K, fixed-order second pass, bit-reproducible); N1, N2
     multiples of 64.  fold=True (N1 == N2): InfoNCELossFull's dW from dW_sym = a^T b (upper triangle dW_sym + dW_sym^T, diagonal
-    doubled, zero below)."""
+    doubled, zero below).  a / b may be row-strided views with unit column stride (a column block of a wider buffer)."""
     L = _lib.lib()
     M, N1 = a.shape
     N2 = b.shape[1]
     out = torch.empty((N1, N2), dtype=torch.float32, device=a.device)
     nb = L.regtr_gemm_tn_ws_bytes(M, N1, N2)
     ws = _ws(max(nb, 1), a.device)
-    check(L.regtr_gemm_tn(ptr(a) if M else None, N1, ptr(b) if M else None, N2, M, N1, N2, int(bool(fold)), ptr(out), N2, bptr(ws), nb,
+    (pa, lda), (pb, ldb) = _rows_ptr(a), _rows_ptr(b)
+    check(L.regtr_gemm_tn(pa if M else None, lda, pb if M else None, ldb, M, N1, N2, int(bool(fold)), ptr(out), N2, bptr(ws), nb,
                           stream()), 'regtr_gemm_tn')
     return out
+
+
+def _rows_ptr(t):
+    """(device pointer, row stride) of a float32 (M, N) operand of the transposed GEMMs: a contiguous tensor goes through ptr()'s checks
+    as before; a row-strided view with unit column stride (a column block of a wider buffer) through raw() with its own stride."""
+    if t.is_contiguous():
+        return ptr(t), t.shape[1]
+    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1) or t.stride(0) < t.shape[1]:
+        raise RuntimeError(f'regtr_amd transposed GEMM: an operand must have unit column stride, got strides {tuple(t.stride())}')
+    return raw(t), t.stride(0)
 
 
 def corr_l1_bwd(kp, warped, w, seg_off, pose, grad, den):
@@ -978,7 +1044,8 @@ def gemm_tn_any(a, b):
     out = torch.empty((N1, N2), dtype=torch.float32, device=a.device)
     nb = L.regtr_gemm_tn_any_ws_bytes(M, N1, N2)
     ws = _ws(max(nb, 1), a.device)
-    check(L.regtr_gemm_tn_any(ptr(a) if M else None, N1, ptr(b) if M else None, N2, M, N1, N2, ptr(out), N2, bptr(ws), nb, stream()),
+    (pa, lda), (pb, ldb) = _rows_ptr(a), _rows_ptr(b)
+    check(L.regtr_gemm_tn_any(pa if M else None, lda, pb if M else None, ldb, M, N1, N2, ptr(out), N2, bptr(ws), nb, stream()),
           'regtr_gemm_tn_any')
     return out
 

@@ -12,6 +12,8 @@ correspondence head, the InfoNCE W) with HIP backward kernels: forward_grad / co
 every parameter the reference trains.  `configure_optimizers` sets the reference's optimiser and scheduler (regtr_amd/optim.py: the fused
 clip + AdamW step; harness.train_loop / train.py run the loop).  `validation_step` / `validation_epoch_end` / `test_step`
 are the reference's (generic_reg_model.py:82-104, 130-158) with the registration metrics computed on the device (regtr_amd/metrics.py).
+`pos_emb_type: learned` puts the reference's PositionEmbeddingLearned in place of the sine table (one launch, regtr_posemb_mlp); its ten
+tensors are trained with everything else above the backbone.
 
 The forward enqueues every stage on the current HIP stream with ONE host synchronisation (the data-dependent level
 sizes after preprocessing): preprocess -> KPConv encoder -> feat_proj -> 6 cross-encoder layers on packed tokens ->
@@ -43,6 +45,40 @@ class PositionEmbeddingCoordsSine(nn.Module):
 
     def forward(self, xyz):
         return ops.posemb_sine(xyz, self.d_model, self.scale, self.temperature)
+
+
+class PositionEmbeddingLearned(nn.Module):
+    """position_embedding.py:53-72: a five-Linear ReLU MLP 3 -> 32 -> 64 -> 128 -> 256 -> d_model over the coordinates, `mlp` with the
+    reference's layer indices (state_dict: mlp.{0,2,4,6,8}.{weight,bias}) and nn.Linear's default initialisation.  forward runs it in
+    one launch (ops.posemb_mlp: regtr_posemb_mlp, exact float32); forward_grad is the same bits with a HIP backward."""
+
+    def __init__(self, n_dim=1, d_model=256):
+        super().__init__()
+        if n_dim != 3:
+            raise NotImplementedError(f'PositionEmbeddingLearned: n_dim {n_dim} (only the 3 coordinates of a point are implemented)')
+        if d_model % 64 or not 64 <= d_model <= 512:
+            raise NotImplementedError(f'PositionEmbeddingLearned: d_model must be a multiple of 64 in [64, 512] (regtr_posemb_mlp), got {d_model}')
+        self.n_dim, self.d_model = n_dim, d_model
+        self.mlp = nn.Sequential(nn.Linear(n_dim, 32), nn.ReLU(), nn.Linear(32, 64), nn.ReLU(), nn.Linear(64, 128), nn.ReLU(),
+                                 nn.Linear(128, 256), nn.ReLU(), nn.Linear(256, d_model))
+        self._cache = {}
+
+    def linears(self):
+        return [self.mlp[i] for i in (0, 2, 4, 6, 8)]
+
+    def _weights(self):
+        """The five (weight in (K, N) layout, bias) pairs ops.posemb_mlp reads: the transposes once per weight version."""
+        return [(_prepared(self._cache, ('kn', i), lin.weight, lambda w: w.t().contiguous()), lin.bias.detach())
+                for i, lin in enumerate(self.linears())]
+
+    def forward(self, xyz):
+        return ops.posemb_mlp(xyz, self._weights())
+
+    def forward_grad(self, xyz):
+        """forward(xyz), bit for bit, differentiable in the ten parameters with a HIP backward (head_grad.posemb_forward_grad).
+        Refused: CPU tensors, double backward, xyz.requires_grad (coordinates take no gradient)."""
+        from . import head_grad
+        return head_grad.posemb_forward_grad(self, xyz)
 
 
 # A-B switch and size gate of the two-stream forward (RegTR._forward)
@@ -166,10 +202,13 @@ class RegTR(nn.Module):
         self.preprocessor = PreprocessorGPU(cfg)                                  # regtr.py:29
         self.kpf_encoder = KPFEncoder(cfg, cfg.d_embed)                           # :34
         self.feat_proj = nn.Linear(self.kpf_encoder.encoder_skip_dims[-1], cfg.d_embed, bias=True)   # :36
-        if cfg.get('pos_emb_type', 'sine') == 'sine':                             # :41-47
+        pos_emb_type = cfg.get('pos_emb_type', 'sine')                            # :41-47
+        if pos_emb_type == 'sine':
             self.pos_embed = PositionEmbeddingCoordsSine(3, cfg.d_embed, scale=cfg.get('pos_emb_scaling', 1.0))
+        elif pos_emb_type == 'learned':
+            self.pos_embed = PositionEmbeddingLearned(3, cfg.d_embed)
         else:
-            raise NotImplementedError('only the sine positional embedding of the shipped configs is implemented')
+            raise NotImplementedError(f"pos_emb_type {pos_emb_type!r}: choose 'sine' or 'learned'")
         encoder_layer = TransformerCrossEncoderLayer(                             # :52-59
             cfg.d_embed, cfg.nhead, cfg.d_feedforward, cfg.dropout, activation=cfg.transformer_act,
             normalize_before=cfg.pre_norm, sa_val_has_pos_emb=cfg.sa_val_has_pos_emb,
@@ -585,12 +624,14 @@ class RegTR(nn.Module):
         return losses
 
     def trainable_parameters(self, backbone=False):
-        """The parameters above the backbone -- feat_proj, the cross-encoder, the correspondence head and the two InfoNCE W -- as a
+        """The parameters above the backbone -- feat_proj, the learned positional embedding's ten tensors (pos_emb_type 'learned'; the
+        sine embedding has none), the cross-encoder, the correspondence head and the two InfoNCE W -- as a
         list.  Turns requires_grad on for the two W (they are created frozen, which inference keeps; a circle config has none).  backbone=True: kpf_encoder's
         weights as well (what training_step(train_backbone=True) fills); the kernel_points stay requires_grad=False and are not
         listed."""
-        mods = [self.feat_proj, self.transformer_encoder, self.correspondence_decoder, self.feature_criterion, self.feature_criterion_un]
-        for crit in mods[3:]:
+        mods = [self.feat_proj, self.pos_embed, self.transformer_encoder, self.correspondence_decoder, self.feature_criterion,
+                self.feature_criterion_un]
+        for crit in mods[4:]:
             if hasattr(crit, 'W'):                    # (CircleLossFull has no parameters)
                 crit.W.requires_grad_(True)
         params = [p for m in mods for p in m.parameters()]
