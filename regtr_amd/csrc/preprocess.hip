@@ -227,6 +227,39 @@ __device__ __forceinline__ int hash_insert(int* __restrict__ rep, unsigned mask,
     }
 }
 
+// Lanes of a wave that hold the same (key, cloud) form a GROUP: a surface cloud in scan order puts ~25 distinct voxels / cells into 64
+// consecutive rows, scattered (A B A B), not in runs.  The table transactions of a group -- the probe, the first / cnt atomics, the fill
+// reservation -- are issued once, by its leader, for the whole group; every lane keeps only its own store.
+// One ballot per distinct key of the wave (wave-uniform loop); inactive lanes (rows behind the live count) take part in the ballots and
+// belong to no group.  leader: the group's lowest lane = its lowest input row; rank: the lane's position inside the group in lane order.
+struct WaveGroup {
+    int leader, size, rank;
+    bool is_leader;
+};
+
+__device__ __forceinline__ WaveGroup wave_group(bool active, uint64_t key, int cid)
+{
+    const int lane = rg_lane();
+    const unsigned klo = (unsigned)key, khi = (unsigned)(key >> 32);
+    unsigned long long mine = 0;          // the lanes of this lane's group
+    unsigned long long todo = __ballot(active);
+    while (todo) {          // wave-uniform
+        const int src = __ffsll((long long)todo) - 1;
+        const unsigned slo = __builtin_amdgcn_readlane(klo, src), shi = __builtin_amdgcn_readlane(khi, src);
+        const int scid = __builtin_amdgcn_readlane(cid, src);
+        const bool in = active && klo == slo && khi == shi && cid == scid;
+        const unsigned long long grp = __ballot(in);      // lane src at least
+        if (in) mine = grp;
+        todo &= ~grp;
+    }
+    WaveGroup g;
+    g.leader = mine ? __ffsll((long long)mine) - 1 : lane;
+    g.size = __popcll(mine);
+    g.rank = __popcll(mine & ((1ULL << lane) - 1ULL));
+    g.is_leader = mine && g.leader == lane;
+    return g;
+}
+
 // ------------------------------------------------------------------------------------------------
 // grid subsample
 // ------------------------------------------------------------------------------------------------
@@ -352,11 +385,20 @@ __global__ void __launch_bounds__(256) k_insert(const int* __restrict__ n_ptr, c
 {
     const int n = *n_ptr;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int s = hash_insert(rep, rg_live_table(n) - 1u, pkey, pcid, i, pkey[i], pcid[i]);
-    slot_of[i] = s;
-    if (first) atomicMin(&first[s], i);
-    atomicAdd(&cnt[s], 1);
+    const bool live = i < n;
+    const uint64_t key = live ? pkey[i] : 0;
+    const int cid = live ? pcid[i] : -1;
+    const WaveGroup g = wave_group(live, key, cid);
+    // leaders only: hash_insert waits for no other lane.  (Which of the rows of a key a slot names as its representative was a race
+    // before and still is; nothing reads more of it than that row's key and cloud.)
+    int s = -1;
+    if (g.is_leader) s = hash_insert(rep, rg_live_table(n) - 1u, pkey, pcid, i, key, cid);
+    s = __shfl(s, g.leader, RG_WAVE);
+    if (live) slot_of[i] = s;
+    if (g.is_leader) {      // the leader's row is the group's lowest
+        if (first) atomicMin(&first[s], i);
+        atomicAdd(&cnt[s], g.size);
+    }
 }
 
 // scan input: leaders (lowest input index of their voxel) carry (1 << 32 | member count)
@@ -377,11 +419,14 @@ __global__ void __launch_bounds__(256) k_scatter_members(const int* __restrict__
 {
     const int n = *n_ptr;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int s = slot_of[i];
-    const unsigned start = (unsigned)(scan_out[first[s]] & 0xFFFFFFFFu);
-    const int p = atomicAdd(&fill[s], 1);
-    members[start + p] = i;
+    const bool live = i < n;
+    const int s = live ? slot_of[i] : -1;
+    const WaveGroup g = wave_group(live, (uint64_t)(unsigned)s, 0);
+    // the leader looks the voxel's list up and reserves the group's places in it (the order inside a list is arbitrary: k_barycentres sorts it)
+    unsigned base = 0;
+    if (g.is_leader) base = (unsigned)(scan_out[first[s]] & 0xFFFFFFFFu) + (unsigned)atomicAdd(&fill[s], g.size);
+    base = (unsigned)__shfl((int)base, g.leader, RG_WAVE);
+    if (live) members[base + (unsigned)g.rank] = i;
 }
 
 // one thread per voxel leader: order the member list by input index, accumulate in float32 in that order,
@@ -509,10 +554,15 @@ __global__ void __launch_bounds__(256) k_scatter_cells(const float* __restrict__
 {
     const int n = *n_ptr;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int s = slot_of[i];
-    const unsigned pos = (unsigned)cell_start[s] + (unsigned)atomicAdd(&fill[s], 1);
-    sorted[pos] = make_float4(xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], __int_as_float(i));
+    const bool live = i < n;
+    const int s = live ? slot_of[i] : -1;
+    const WaveGroup g = wave_group(live, (uint64_t)(unsigned)s, 0);
+    // the leader reserves the group's places in the cell's run.  (The order inside a run is arbitrary: every reader ranks a run's supports by
+    // (d2, index) or by index, k_nearest_in_radius breaks its ties by index, and the rows of the self kernel go by the support's own index.)
+    unsigned base = 0;
+    if (g.is_leader) base = (unsigned)cell_start[s] + (unsigned)atomicAdd(&fill[s], g.size);
+    base = (unsigned)__shfl((int)base, g.leader, RG_WAVE);
+    if (live) sorted[base + (unsigned)g.rank] = make_float4(xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], __int_as_float(i));
 }
 
 // One probe = ONE memory round trip: everything a radius query needs from a hash slot, packed into 32 bytes by
