@@ -36,6 +36,7 @@
  *   regtr_mha_fwd             nn.MultiheadAttention core          transformers.py:197-226
  *   regtr_attn_xyz            CorrespondenceDecoder.simple_attention   models/regtr.py:316-351
  *   regtr_weighted_procrustes pose assembly + compute_rigid_transform   regtr.py:185-203, utils/se3_torch.py:108-154
+ *   regtr_weighted_procrustes_bwd  its backward (what autograd gives the reference through torch.svd)   the same lines
  *   regtr_infonce             InfoNCELossFull.compute_infonce     models/losses/feature_loss.py:281-314
  *   regtr_se3_transform       se3_transform (GT overlap masks)    data_loaders/threedmatch.py:78-84
  *   regtr_loss_terms          overlap BCE + CorrCriterion sums    models/regtr.py:250-285, models/losses/corr_loss.py:18-40
@@ -405,6 +406,18 @@ int regtr_attn_xyz(const float* q, const float* k, const float* xyz, float* out,
  * status word, REGTR_STATUS_NONFINITE_POSE when an R|t came out non-finite */
 int regtr_weighted_procrustes(const float* kp, const float* corr, const float* logit, const int* seg_off, int n_pairs,
                               int n_total, int n_layers, float* pose, int* status, void* stream);
+
+/* The backward of regtr_weighted_procrustes in closed form (no SVD derivative; csrc/procrustes.hip states it): the same inputs and
+ * d_pose [L,n_pairs,3,4], the gradient of every R|t -> d_corr [L,n_total,3]; optionally (NULL: not written) d_logit [L,n_total],
+ * d_kp [L,n_total,3] -- PER LAYER, kp's gradient is their sum over L -- and d_weight [L,n_total], the gradient with respect to
+ * w = sigmoid(logit) (d_logit without the factor w (1 - w), finite at w = 0 and 1).  One workgroup per (pair, layer) recomputes the
+ * forward with the forward's own code, nothing is saved by the forward; float64 fixed-tree sums, every row written once by one thread:
+ * no atomics, no workspace, bit-reproducible, no host wait.  A pair whose R is no differentiable function of its float32 inputs gets
+ * exactly zero rows: min_{i<j} (lam_i + lam_j) <= 2^-23 lam_0 with lam = (S0, S1, d S2) (the zero covariance, collinear points, a
+ * reflection with S1 = S2), a weight sum at the 1e-6 clamp, an empty pair.  The other pairs of the launch are unaffected. */
+int regtr_weighted_procrustes_bwd(const float* kp, const float* corr, const float* logit, const int* seg_off, int n_pairs, int n_total,
+                                  int n_layers, const float* d_pose, float* d_corr, float* d_logit, float* d_kp, float* d_weight,
+                                  void* stream);
 
 
 /* ---- validation / test losses (models/regtr.py:237-294 compute_loss; inference only, no gradients) ----------------------------- */

@@ -107,6 +107,7 @@ SIGNATURES = {
     'regtr_encoder_fwd': (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _I, _F, _F, _P, _Z, _P, _P]),
     'regtr_attn_xyz': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
     'regtr_weighted_procrustes': (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    'regtr_weighted_procrustes_bwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     'regtr_infonce_ws_bytes': (_Z, [_I, _I]),
     'regtr_infonce': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P, _Z, _P]),
     'regtr_loss_terms': (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _I, _P, _P]),

@@ -95,6 +95,52 @@ def regressor_forward_grad(head, feats):
     return corr.view(Lyr, N, 3), logit.view(Lyr, N)
 
 
+class _Procrustes(torch.autograd.Function):
+    """(kp (N, 3), corr (L, N, 3), logit (L, N), seg_off (2B + 1,)) -> pose (L, B, 3, 4) by ops.weighted_procrustes.  Backward:
+    ops.weighted_procrustes_bwd, the closed form of csrc/procrustes.hip, which recomputes the forward from the saved INPUTS (the
+    forward launch saves nothing).  Gradients go to corr and logit."""
+
+    @staticmethod
+    def forward(ctx, kp, corr, logit, seg_off, n_pairs):
+        pose = ops.weighted_procrustes(kp, corr, logit, seg_off, n_pairs)
+        ctx.save_for_backward(kp, corr, logit, seg_off)
+        ctx.n_pairs = n_pairs
+        return pose
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_pose):
+        kp, corr, logit, seg_off = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        with context.ForwardContext(kp.device):
+            d_corr, d_logit, _, _ = ops.weighted_procrustes_bwd(kp, corr, logit, seg_off, ctx.n_pairs,
+                                                                d_pose.detach().to(torch.float32).contiguous(), want_logit=need[2])
+        return None, d_corr if need[1] else None, d_logit, None, None
+
+
+class PoseTensor(torch.Tensor):
+    """What RegTR.forward_grad returns as pred['pose'].  Until the pose solve had a backward that entry was a gradient-free tensor, and
+    callers read it as one -- `pred['pose'][0].cpu().numpy()` in logging and in comparisons with a recorded pose.  It now carries a
+    grad_fn, on which torch.Tensor.numpy() raises; this subclass keeps those callers working: numpy() (and with it np.asarray) detaches
+    first.  Everything else, autograd included, is torch.Tensor's."""
+
+    def numpy(self, *args, **kwargs):
+        return self.detach().as_subclass(torch.Tensor).numpy(*args, **kwargs)
+
+
+def procrustes_forward_grad(kp, corr, logit, seg_off, n_pairs):
+    """ops.weighted_procrustes(kp, corr, logit, seg_off, n_pairs) -- the very call, the same bits -- as a differentiable call: pose
+    (L, B, 3, 4) carries a gradient to corr (L, N, 3) and logit (L, N), none to kp.  A pair whose pose is no differentiable function of
+    its inputs (docs/PARITY.md) contributes exactly zero."""
+    for name, t in (('kp', kp), ('corr', corr), ('logit', logit), ('seg_off', seg_off)):
+        if not isinstance(t, torch.Tensor) or t.device.type != 'cuda':
+            raise RuntimeError(f'procrustes_forward_grad: {name} must be a GPU tensor (got {getattr(t, "device", type(t))}); there is no CPU fallback')
+    if kp.requires_grad:
+        raise NotImplementedError('procrustes_forward_grad: kp.requires_grad (a gradient with respect to the key points) is not implemented '
+                                  'here; regtr_amd.se3.compute_rigid_transform differentiates both point sets')
+    return _Procrustes.apply(kp, corr.contiguous(), logit.contiguous(), seg_off, int(n_pairs))
+
+
 class _PosembMLP(torch.autograd.Function):
     """(xyz (n, 3), the five Linears' weight and bias) -> pe (n, d_model) by ops.posemb_mlp with save=True: one launch, the four
     activations after their ReLUs kept as one (n, 480) buffer.  Backward: transformer_grad.linear_bwd per layer, last to first, on

@@ -13,6 +13,7 @@ of csrc/losses.hip (regtr_infonce_rows / regtr_infonce_bwd / regtr_gemm_tn, regt
 (regtr_bce_logits_bwd) and the exact-f32 GEMM; torch only packs the per-pair lists and forms the scalar means.  Nothing here synchronises with the host.
 
 Reference semantics are kept: a pair without an anchor inside r_p gives NaN (0 / 0), and its gradient contributions are exactly 0.
+PoseCriterion is this project's own opt-in pose term (cfg.wt_pose), a few torch ops, not a reference loss.
 Refused: metric='mse', overlap_weights=None, CircleLossFull's dist_type other than 'euclidean', coordinates / poses / weights that require grad, double backward, tensors off the GPU.
 """
 import torch
@@ -278,3 +279,21 @@ class OverlapCriterion(nn.Module):
         zeros = torch.zeros((n, 3), dtype=torch.float32, device=dev)
         pose = torch.eye(3, 4, dtype=torch.float32, device=dev).expand(B, 3, 4).contiguous()
         return _OverlapBCE.apply(logit.contiguous(), target.contiguous(), seg_off, zeros, zeros, pose)
+
+
+class PoseCriterion(nn.Module):
+    """mean over pairs of ||R_pred - R_gt||_F^2 + ||t_pred - t_gt||^2: the opt-in pose term of RegTR.compute_loss / compute_loss_grad
+    (cfg.wt_pose > 0).  NOT a loss of the reference (its RegTR.compute_loss never reads pred['pose']): the simplest supervision of the
+    pose that regtr_weighted_procrustes_bwd makes trainable.  A few plain torch ops on (B, 3, 4) tensors, no kernel.
+    forward(pose_pred (B, 3, 4), pose_gt (B, 3, 4) or (B, 4, 4), per_pair=False) -> 0-dim, or (B,) with per_pair=True.  Gradients go to
+    pose_pred."""
+
+    def forward(self, pose_pred, pose_gt, per_pair=False):
+        _on_gpu('PoseCriterion', [pose_pred, pose_gt])
+        _no_grad_inputs('PoseCriterion', [pose_gt])
+        if pose_pred.dim() != 3 or tuple(pose_pred.shape[1:]) != (3, 4) or pose_gt.dim() != 3 or pose_gt.shape[0] != pose_pred.shape[0] or \
+                tuple(pose_gt.shape[1:]) not in ((3, 4), (4, 4)):
+            raise RuntimeError(f'PoseCriterion: pose_pred (B, 3, 4) and pose_gt (B, 3, 4) or (B, 4, 4) expected, got {tuple(pose_pred.shape)}, '
+                               f'{tuple(pose_gt.shape)}')
+        per = ((pose_pred.as_subclass(torch.Tensor) - pose_gt[:, :3, :].to(torch.float32)) ** 2).sum(dim=(1, 2))
+        return per if per_pair else per.mean()

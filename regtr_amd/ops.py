@@ -717,6 +717,29 @@ def weighted_procrustes(kp, corr, logit, seg_off, n_pairs):
     return pose
 
 
+def weighted_procrustes_bwd(kp, corr, logit, seg_off, n_pairs, d_pose, want_logit=True, want_kp=False, want_weight=False):
+    """The backward of weighted_procrustes (regtr_weighted_procrustes_bwd): its inputs and d_pose (L, B, 3, 4) ->
+    (d_corr (L, N, 3), d_logit (L, N) | None, d_kp (L, N, 3) | None, d_weight (L, N) | None).  d_kp is per layer (kp's gradient is its sum
+    over L); d_weight is the gradient with respect to sigmoid(logit).  Nothing is saved by the forward; a pair whose pose is not
+    differentiable (include/regtr_hip.h) gets zero rows."""
+    for t in (kp, corr, logit, seg_off, d_pose):
+        if not isinstance(t, torch.Tensor) or t.device.type != 'cuda':
+            raise RuntimeError(f'weighted_procrustes_bwd: every tensor must be on the GPU (got {getattr(t, "device", type(t))}); there is no CPU fallback')
+    Lyr, N = logit.shape
+    if tuple(corr.shape) != (Lyr, N, 3) or tuple(kp.shape) != (N, 3) or tuple(d_pose.shape) != (Lyr, n_pairs, 3, 4) or \
+            seg_off.numel() != 2 * n_pairs + 1:
+        raise RuntimeError(f'weighted_procrustes_bwd: kp (N, 3), corr (L, N, 3), logit (L, N), seg_off (2B + 1,), d_pose (L, B, 3, 4) expected, '
+                           f'got {tuple(kp.shape)}, {tuple(corr.shape)}, {tuple(logit.shape)}, {tuple(seg_off.shape)}, {tuple(d_pose.shape)}')
+    new = lambda *s: torch.empty(s, dtype=torch.float32, device=kp.device)
+    d_corr = new(Lyr, N, 3)
+    d_logit = new(Lyr, N) if want_logit else None
+    d_kp = new(Lyr, N, 3) if want_kp else None
+    d_weight = new(Lyr, N) if want_weight else None
+    check(_lib.lib().regtr_weighted_procrustes_bwd(ptr(kp), ptr(corr), ptr(logit), iptr(seg_off), n_pairs, N, Lyr, ptr(d_pose), ptr(d_corr),
+                                                   ptr(d_logit), ptr(d_kp), ptr(d_weight), stream()), 'regtr_weighted_procrustes_bwd')
+    return d_corr, d_logit, d_kp, d_weight
+
+
 # ------------------------------------------------------------------------------------------------ losses (validation / test)
 def infonce(anc, pos_t, anc_xyz, pos_xyz, anc_seg_off, pos_seg_off, max_anc, r_p, r_n, anc_pose=None, rows=False):
     """InfoNCE feature loss of packed, ragged pairs (regtr_infonce).  anc (N_anc, D) and pos_t (N_pos, D) row-strided views (pos_t: the

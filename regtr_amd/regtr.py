@@ -170,7 +170,15 @@ def loss_weight_dict(cfg):
         for i in cfg.get(f'{k}_loss_on', [cfg.num_encoder_layers - 1]):
             wd[f'{k}_{i}'] = cfg.get(f'wt_{k}')
     wd['feature_un'] = cfg.wt_feature_un
+    if pose_loss_on(cfg):
+        wd[f'pose_{cfg.num_encoder_layers - 1}'] = cfg.wt_pose
     return wd
+
+
+def pose_loss_on(cfg):
+    """cfg.wt_pose > 0: the opt-in pose term (losses.PoseCriterion on the last decoder layer's pose; NOT a loss of the reference, whose
+    configs have no such key).  Absent or 0: no key, no launch, nothing changes anywhere."""
+    return float(cfg.get('wt_pose', 0) or 0) > 0
 
 
 def _packed_rows(views):
@@ -488,8 +496,12 @@ class RegTR(nn.Module):
             raise KeyError(f'{what} needs the losses section of the config (regtr_amd/conf/*.yaml); missing: {missing}')
 
     def head_layers(self):
-        """The decoder layers a loss reads the head's outputs of: cfg.overlap_loss_on | cfg.corr_loss_on, ascending."""
-        return sorted(set(self.cfg.overlap_loss_on) | set(self.cfg.corr_loss_on))
+        """The decoder layers a loss reads the head's outputs of: cfg.overlap_loss_on | cfg.corr_loss_on, ascending; with the pose term
+        on (cfg.wt_pose > 0) always the last layer as well, whose pose it reads."""
+        layers = set(self.cfg.overlap_loss_on) | set(self.cfg.corr_loss_on)
+        if pose_loss_on(self.cfg):
+            layers.add(self.cfg.num_encoder_layers - 1)
+        return sorted(layers)
 
     def forward_grad(self, batch, backbone_grad=False, train_backbone=False):
         """forward(batch) as a differentiable call, by default above a FROZEN backbone: the preprocessor and kpf_encoder run under torch.no_grad()
@@ -500,8 +512,9 @@ class RegTR(nn.Module):
         that arithmetic, with two differences:
           * '*_kp_warped' / '*_overlap': per pair a dict {decoder layer: (n, 3) / (n, 1)} over head_layers() -- indexed [b][i] like
             forward's (L, n, .) tensors, the layers no loss reads absent;
-          * 'pose': (1, B, 3, 4), the LAST decoder layer's, computed without gradient (the reference's loss never reads it); absent
-            when the last layer is not in head_layers().
+          * 'pose': (1, B, 3, 4), the LAST decoder layer's, through head_grad.procrustes_forward_grad: the same launch and bits as
+            forward's, with a gradient to that layer's warped points and overlap logits (regtr_weighted_procrustes_bwd, launched only
+            when a loss reads the pose; the reference's own loss never does).  Absent when the last layer is not in head_layers().
         backbone_grad=True: feats_un, the backbone's output, becomes a leaf that requires grad and is returned as pred['_feats_un'];
         its .grad after backward() is what a backbone backward starts from.
         train_backbone=True: the preprocessor runs without gradient on one stream and the encoder through KPFEncoder.forward_grad
@@ -536,8 +549,7 @@ class RegTR(nn.Module):
                 self.correspondence_decoder, feats_un, xyz_c, seg_c, kv_self, kv_cross, max(slens_c), layers, cache=self._cache)
             pose = None
             if layers[-1] == self.cfg.num_encoder_layers - 1:
-                with torch.no_grad():
-                    pose = ops.weighted_procrustes(xyz_c, corr[-1:].detach(), logit[-1:].detach(), seg_c, B)
+                pose = head_grad.procrustes_forward_grad(xyz_c, corr[-1:], logit[-1:], seg_c, B).as_subclass(head_grad.PoseTensor)
         off = [0]
         for n in slens_c:
             off.append(off[-1] + n)
@@ -567,7 +579,9 @@ class RegTR(nn.Module):
         from the training criteria of regtr_amd/losses.py: the overlap terms on OverlapCriterion's Function (bit-equal to compute_loss's),
         the feature terms on InfoNCELossFull's with this model's feature_criterion.W / feature_criterion_un.W (or on CircleLossFull's
         under feature_loss_type 'circle', with the shared criterion's margins and radii), the correspondence terms
-        on CorrCriterion's in both directions (the inverse GT pose for tgt), the total weighted by loss_weight_dict(cfg).  Gradients go
+        on CorrCriterion's in both directions (the inverse GT pose for tgt), under cfg.wt_pose > 0 the opt-in pose term
+        losses.PoseCriterion on pred['pose'] (a few torch ops; its gradient reaches the head through regtr_weighted_procrustes_bwd),
+        the total weighted by loss_weight_dict(cfg).  Gradients go
         to the features, the warped points, the overlap logits and the two W.  No host wait, forward or backward."""
         from . import losses as L
         self._check_trainable('compute_loss_grad')
@@ -620,6 +634,8 @@ class RegTR(nn.Module):
             warped = rows('kp_warped', i)
             losses[f'corr_{i}'] = (L._CorrL1.apply(warped[:n_src], xyz[:n_src], gt_c[:n_src], seg_s, seg2_s, pose) +
                                    L._CorrL1.apply(warped[n_src:], xyz[n_src:], gt_c[n_src:], seg_t, seg2_t, pose_inv))
+        if pose_loss_on(cfg):                                                                     # opt-in, not a reference loss
+            losses[f'pose_{cfg.num_encoder_layers - 1}'] = L.PoseCriterion()(pred['pose'][-1], pose)
         losses['total'] = torch.sum(torch.stack([losses[k] * wd[k] for k in losses]), dim=0)     # :292-293
         return losses
 
@@ -698,11 +714,12 @@ class RegTR(nn.Module):
         """The keys of compute_loss's result, in its order."""
         cfg = self.cfg
         return ([f'overlap_{i}' for i in cfg.overlap_loss_on] + [f'feature_{i}' for i in cfg.feature_loss_on] + ['feature_un'] +
-                [f'corr_{i}' for i in cfg.corr_loss_on] + ['total'])
+                [f'corr_{i}' for i in cfg.corr_loss_on] + ([f'pose_{cfg.num_encoder_layers - 1}'] if pose_loss_on(cfg) else []) + ['total'])
 
     @torch.no_grad()
     def compute_loss(self, pred, batch, per_pair=False):
-        """regtr.py:237-294 without gradients: {'overlap_i', 'feature_i', 'feature_un', 'corr_i', 'total'} -> 0-dim device tensors,
+        """regtr.py:237-294 without gradients: {'overlap_i', 'feature_i', 'feature_un', 'corr_i', 'total'} (and 'pose_{L-1}', this
+        project's opt-in pose term, under cfg.wt_pose > 0: losses.PoseCriterion on pred['pose'][-1]) -> 0-dim device tensors,
         or (B,) tensors of every term per pair with per_pair=True (what the reference computes with one pair per batch).
         batch: 'pose' (B, 3, 4) or (B, 4, 4), 'src_overlap' / 'tgt_overlap' level-0 masks, 'kpconv_meta' from the preceding forward
         (batch['overlap_pyr'] is set as the reference does).  Reference semantics kept, NaN included: a pair without an anchor inside
@@ -762,6 +779,9 @@ class RegTR(nn.Module):
                 else:
                     s = t.sum(0)
                     losses[f'corr_{i}'] = s[1] / s[2].clamp_min(1e-6) + s[3] / s[4].clamp_min(1e-6)
+            if pose_loss_on(cfg):                                                                 # opt-in, not a reference loss
+                from .losses import PoseCriterion
+                losses[f'pose_{cfg.num_encoder_layers - 1}'] = PoseCriterion()(pred['pose'][-1], pose, per_pair=per_pair)
             losses['total'] = torch.sum(torch.stack([losses[k] * wd[k] for k in losses]), dim=0)   # :292-293
         return losses
 
