@@ -23,8 +23,9 @@ F64 = torch.float64
 KP = 15
 
 
-def t64(a, device='cpu'):
-    return torch.as_tensor(np.asarray(a), dtype=F64).to(device)
+def t64(a, device='cpu', dtype=F64):
+    """a as a tensor of `dtype` on `device`: float64, the yardstick, unless a caller asks for the float32 evaluation of the same code."""
+    return torch.as_tensor(np.asarray(a), dtype=dtype).to(device)
 
 
 def inorm(x, lens, eps=EPS32):
@@ -60,7 +61,7 @@ def lrelu(z, sides, slope=SLOPE32):
     if z.numel():
         sides.margin = min(sides.margin, float(z.detach().abs().min()))
     mask = sides.take('masks', own).to(torch.bool)
-    return z * torch.where(mask, 1.0, slope).to(F64)
+    return z * torch.where(mask, 1.0, slope).to(z.dtype)
 
 
 def max_pool(x, nbr, width, sides):
@@ -93,13 +94,13 @@ def kpconv(q_pts, s_pts, nbr, x, W, kp, extent, sides):
     wf = torch.bmm(w.transpose(1, 2), nx)                                        # (Nq, KP, Cin)
     own = x.detach().sum(1) > 0
     pos = sides.take('pos', own).to(torch.bool)
-    num = torch.cat([pos, torch.zeros_like(pos[:1])])[idx].sum(1).clamp(min=1).to(F64)
+    num = torch.cat([pos, torch.zeros_like(pos[:1])])[idx].sum(1).clamp(min=1).to(x.dtype)
     return (wf.reshape(wf.shape[0], -1) @ W.reshape(-1, W.shape[2])) / num[:, None]
 
 
-def _view(blk, meta, device):
+def _view(blk, meta, device, dtype=F64):
     l, strided = blk['layer'], blk['strided']
-    return dict(s_pts=t64(meta['points'][l], device), q_pts=t64(meta['points'][l + 1 if strided else l], device),
+    return dict(s_pts=t64(meta['points'][l], device, dtype), q_pts=t64(meta['points'][l + 1 if strided else l], device, dtype),
                 inds=torch.as_tensor(np.asarray(meta['pools'][l] if strided else meta['neighbors'][l])).to(device),
                 lens_pre=meta['lens'][l], lens_post=meta['lens'][l + 1 if strided else l],
                 width=int(meta['pool_width'][l]) if strided else None)
@@ -110,8 +111,8 @@ def block_forward(blk, W, x, meta, sides):
     if blk['kind'] == 'unary':
         z = inorm(x @ W['mlp.weight'].t(), meta['lens'][blk['layer']])
         return z if blk.get('no_relu') else lrelu(z, sides)
-    v = _view(blk, meta, x.device)
-    kp = t64(blk['kp'], x.device)
+    v = _view(blk, meta, x.device, x.dtype)
+    kp = t64(blk['kp'], x.device, x.dtype)
     conv = lambda f: kpconv(v['q_pts'], v['s_pts'], v['inds'], f, W['KPConv.weights'], kp, blk['extent'], sides)
     if blk['kind'] == 'simple':
         return lrelu(inorm(conv(x), v['lens_post']), sides)
@@ -128,14 +129,16 @@ def block_forward(blk, W, x, meta, sides):
 WEIGHT_NAMES = ('mlp.weight', 'KPConv.weights', 'unary1.mlp.weight', 'unary2.mlp.weight', 'unary_shortcut.mlp.weight')
 
 
-def run(blocks, x, meta, d_out, sides=None, x_grad=False, backward=True, device='cpu'):
-    """Forward through `blocks` in order and backward of sum(out * d_out), all float64.  sides: per block a dict (or None) of 'masks',
+def run(blocks, x, meta, d_out, sides=None, x_grad=False, backward=True, device='cpu', dtype=F64):
+    """Forward through `blocks` in order and backward of sum(out * d_out), all in `dtype` (float64).  d_out: an array, or a callable that is handed the
+    forward's output (a detached tensor) and returns its upstream gradient -- what a loss computed ON that output needs
+    (tests/training_step_ref.py).  dtype: torch.float32 evaluates the same code in float32.  sides: per block a dict (or None) of 'masks',
     'winners', 'pos' lists in call order.  -> dict 'out', 'grads' {(block index, weight name): array}, 'dx' (x_grad), 'margin', and
     'sides': the float64 run's own choices per block (same layout).  backward=False: the forward only ('out', 'margin', 'sides').
     device: where the float64 torch ops run -- 'cpu' (the host test pins this very code to finite differences there), or 'cuda' in the
     GPU tests (stock torch float64 ops; the full crop's encoder takes 12 s on 16 CPU threads)."""
-    ws = [{k: t64(b[k], device).requires_grad_() for k in WEIGHT_NAMES if k in b} for b in blocks]
-    x = t64(x, device)
+    ws = [{k: t64(b[k], device, dtype).requires_grad_() for k in WEIGHT_NAMES if k in b} for b in blocks]
+    x = t64(x, device, dtype)
     if x_grad:
         x.requires_grad_()
     cur, own, margin = x, [], float('inf')
@@ -146,7 +149,8 @@ def run(blocks, x, meta, d_out, sides=None, x_grad=False, backward=True, device=
         margin = min(margin, s.margin)
     if not backward:
         return {'out': cur.detach().cpu().numpy(), 'margin': margin, 'sides': own}
-    (cur * t64(d_out, device)).sum().backward()
+    d = d_out(cur.detach()).to(cur) if callable(d_out) else t64(d_out, device, dtype)
+    (cur * d).sum().backward()
     return {'out': cur.detach().cpu().numpy(), 'grads': {(i, k): w.grad.cpu().numpy() for i, W in enumerate(ws) for k, w in W.items()},
             'dx': x.grad.cpu().numpy() if x_grad else None, 'margin': margin, 'sides': own}
 
