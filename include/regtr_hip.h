@@ -68,6 +68,7 @@
  *   regtr_nearest +
  *   regtr_segment_mean        the modified Chamfer distance (nearest neighbours, per-cloud means)   benchmark/benchmark_modelnet.py:69-76
  *   regtr_pose_metrics        se3_compare; the RPMNet / DCP pose metrics   utils/se3_torch.py:93-105, benchmark/benchmark_modelnet.py:51-67
+ *   regtr_gather_segments     (no reference counterpart) packs the cached per-cloud tokens of the pairs of one RegTR.register call
  */
 #ifndef REGTR_HIP_H
 #define REGTR_HIP_H
@@ -879,6 +880,24 @@ int regtr_grad_norm_finish(const double* partials, long long n_partials, float m
  * Refused: negative counts, NULLs with work to do, misaligned pointers, bias corrections that are not positive, a negative eps, NaN
  * scalars. */
 int regtr_adam_step(const regtr_optim_tensor_t* tensors, int n_tensors, const float* clip_coef, int decoupled, void* stream);
+
+/* ---- the cloud bank (regtr_amd/cloud_bank.py, RegTR.encode_clouds / register; csrc/cloud_bank.hip) ------------------------------------
+ * A new entry point only: no existing signature changes, REGTR_ABI_VERSION stays as it is. */
+
+/* Packs whole clouds of a bank into a new order, one launch for up to three row arrays.  The bank holds n_bank_clouds packed ragged
+ * clouds (bank_seg [n_bank_clouds + 1], n_bank rows in all); destination cloud d (0 <= d < n_dst) is bank cloud cloud_of[d], and its
+ * rows go to rows dst_seg[d] ... of the outputs (n_out rows in all; the caller's dst_seg is the running sum of the selected clouds'
+ * lengths).  feats -> out_feats and pe -> out_pe are [*, D] rows (pe / out_pe optional: both or neither), xyz -> out_xyz [*, 3] rows
+ * (optional likewise).  max_len: the longest selected cloud (the caller knows the lengths; rows of a cloud beyond max_len are not
+ * copied).  A wide row moves as D / 4 aligned 16-byte pieces; the xyz rows as single floats.  Every destination row is written once;
+ * no atomics, no workspace; bit-reproducible.  cloud_of entries are clamped to the bank and all rows to n_bank / n_out, so no table
+ * can make an access leave the arrays.  No selected row (n_dst == 0, n_out == 0 or max_len == 0): nothing is launched and no pointer
+ * is looked at (empty arrays often have NULL bases), REGTR_OK.  Refused
+ * (REGTR_ERR_ARG, nothing launched): D < 4 or D % 4 != 0, a negative count, n_dst > 65535, pe without out_pe or xyz without out_xyz
+ * (or the reverse), a wide array's base that is not 16-byte aligned, NULL feats / out_feats / tables with work to do. */
+int regtr_gather_segments(const float* feats, const float* pe, const float* xyz, int D, const int* bank_seg, int n_bank_clouds, int n_bank,
+                          const int* cloud_of, const int* dst_seg, int n_dst, int n_out, int max_len, float* out_feats, float* out_pe,
+                          float* out_xyz, void* stream);
 
 #ifdef __cplusplus
 }

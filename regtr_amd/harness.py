@@ -87,7 +87,7 @@ def read_ply_xyz(fname):
 
 
 def load_point_cloud(fname, cache_dir=None):
-    """demo.py:142-153: .pth (torch-saved array), .ply, .bin (KITTI float32 x y z r); returns (N, 3).
+    """demo.py:142-153: .pth (torch-saved array), .ply, .bin (KITTI float32 x y z r), and .npy (a plain array); returns (N, 3).
     cache_dir: `.pth` fragments (a zip + pickle: ~2 ms each to open, 3562 of them in the 3DLoMatch list) are mirrored there once as
     float32 `.npy` files and read back with np.load (~0.1 ms); a cache entry older than its source is rebuilt."""
     if cache_dir is not None and fname.endswith('.pth'):
@@ -110,6 +110,8 @@ def load_point_cloud(fname, cache_dir=None):
         data = read_ply_xyz(fname)
     elif fname.endswith('.bin'):
         data = np.fromfile(fname, dtype=np.float32).reshape(-1, 4)
+    elif fname.endswith('.npy'):
+        data = np.load(fname)
     else:
         raise AssertionError('Cannot recognize point cloud format')
     return data[:, :3]
@@ -134,6 +136,15 @@ class ThreeDMatchPairs:
         return {'src_xyz': np.ascontiguousarray(load_point_cloud(os.path.join(self.root, src_path), self.cache_dir), dtype=np.float32),
                 'tgt_xyz': np.ascontiguousarray(load_point_cloud(os.path.join(self.root, tgt_path), self.cache_dir), dtype=np.float32),
                 'pose': pose, 'idx': i, 'src_path': src_path, 'tgt_path': tgt_path}
+
+    # the fragment protocol of run_test_shared: a pair names its two fragments, a fragment is loaded by its name
+    def fragment_keys(self, i):
+        """(src_key, tgt_key) of pair i: the fragments' paths relative to `root`."""
+        return self.infos['src'][i], self.infos['tgt'][i]
+
+    def load_fragment(self, key):
+        """The (n, 3) float32 cloud of fragment `key` (through load_point_cloud and its .npy cache)."""
+        return np.ascontiguousarray(load_point_cloud(os.path.join(self.root, key), self.cache_dir), dtype=np.float32)
 
 
 class SyntheticPairs:
@@ -219,6 +230,94 @@ def materialize_synthetic(root, n, points=20000, overlap=None, logger=None, rank
 def _synthetic_paths(src, i):
     scene, k = i // src.pps, i % src.pps
     return (f'test/synthetic-scene{scene:03d}/cloud_bin_{2 * k + 1}.pth', f'test/synthetic-scene{scene:03d}/cloud_bin_{2 * k}.pth')
+
+
+class SyntheticScenePairs:
+    """Scene-style synthetic pairs: n_scenes rooms of fragments_per_scene fragments each (regtr_amd.synthetic.synth_fragments: occluded,
+    rigidly moved views of ONE room) and pairs_per_scene pairs of them per room -- the shape of the 3DMatch test lists, where a few hundred
+    fragments make 1623 / 1781 pairs.  A scene's pairs are its (a, b), a < b, in lexicographic order, then the same reversed, cyclically; pair
+    i is pair i // n_scenes of scene i % n_scenes (consecutive pairs come from different scenes: the order that is hardest on a small
+    bank).  Laid out like the 3DMatch test set (scene folders, cloud_bin_<k>.pth names) so that the est.log writer is exercised unchanged.
+    Serves both protocols: pairs[i] (a plain pair, what run_test and the LoaderPool processes read; the source pickles) and
+    fragment_keys / load_fragment (run_test_shared).  meta(i) gives a pair's paths and ground-truth pose without generating a cloud.
+    cache_scenes: generated scenes kept (least recently used dropped; a scene is F clouds of `points` points); since consecutive pairs
+    walk the scenes, it should cover the scenes one window of pairs touches -- default min(n_scenes, 64)."""
+
+    _PREFIX = 'synthetic-scene'
+
+    def __init__(self, n_scenes, fragments_per_scene, pairs_per_scene, points=20000, cache_scenes=None):
+        if n_scenes < 1 or fragments_per_scene < 2 or pairs_per_scene < 1:
+            raise ValueError('SyntheticScenePairs: at least one scene, two fragments per scene and one pair per scene')
+        self.n_scenes, self.fps, self.pps, self.points = n_scenes, fragments_per_scene, pairs_per_scene, points
+        self.cache_scenes = max(1, min(n_scenes, 64) if cache_scenes is None else int(cache_scenes))
+        F = fragments_per_scene
+        fwd = [(a, b) for a in range(F) for b in range(a + 1, F)]
+        self._scene_pairs = fwd + [(b, a) for a, b in fwd]
+        self._scenes, self._lock = {}, threading.Lock()
+
+    def __getstate__(self):                   # (LoaderPool.set_source pickles the source: neither the lock nor the generated scenes travel)
+        state = dict(self.__dict__)
+        del state['_scenes'], state['_lock']
+        return state
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+        self._scenes, self._lock = {}, threading.Lock()
+
+    def __len__(self):
+        return self.n_scenes * self.pps
+
+    def _scene(self, s):
+        """The clouds of scene s, generated on first use."""
+        with self._lock:                      # (the loader thread and the consumer may both ask)
+            ent = self._scenes.pop(s, None)
+            if ent is None:
+                from .synthetic import synth_fragments
+                while len(self._scenes) >= self.cache_scenes:
+                    self._scenes.pop(next(iter(self._scenes)))       # the least recently used: hits are re-inserted at the end
+                ent = synth_fragments(s, self.fps, self.points)[0]
+            self._scenes[s] = ent
+            return ent
+
+    def _pair(self, i):
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        s, k = i % self.n_scenes, i // self.n_scenes
+        a, b = self._scene_pairs[k % len(self._scene_pairs)]
+        return s, a, b
+
+    @classmethod
+    def _key(cls, s, k):
+        return f'test/{cls._PREFIX}{s:03d}/cloud_bin_{k}.pth'
+
+    def fragment_keys(self, i):
+        s, a, b = self._pair(i)
+        return self._key(s, a), self._key(s, b)
+
+    def load_fragment(self, key):
+        scene, name = key.split('/')[1:3]
+        if not scene.startswith(self._PREFIX):
+            raise KeyError(key)
+        s, k = int(scene[len(self._PREFIX):]), int(name[:-4].split('_')[-1])
+        if not (0 <= s < self.n_scenes and 0 <= k < self.fps):
+            raise KeyError(key)
+        return self._scene(s)[k]
+
+    def pose(self, i):
+        """The ground-truth (3, 4) float32 transform taking pair i's source into its target's frame (no cloud is generated)."""
+        from .synthetic import synth_fragment_poses
+        s, a, b = self._pair(i)
+        return synth_fragment_poses(s, self.fps)[1][a, b, :3].astype(np.float32)
+
+    def meta(self, i):
+        """Pair i without its clouds: {'src_path', 'tgt_path', 'pose', 'idx'}."""
+        sk, tk = self.fragment_keys(i)
+        return {'pose': self.pose(i), 'idx': i, 'src_path': sk, 'tgt_path': tk}
+
+    def __getitem__(self, i):
+        item = self.meta(i)
+        item['src_xyz'], item['tgt_xyz'] = self.load_fragment(item['src_path']), self.load_fragment(item['tgt_path'])
+        return item
 
 
 # ------------------------------------------------------------------------------------------------------ streaming
@@ -872,4 +971,142 @@ def run_test(model, pairs, batch, device, logger=None, max_pairs=None, num_worke
     timing = {'elapsed_s': elapsed, 'pairs': n, 'world': world, 'loader': getattr(loader_pool, 'last_timing', None), 'forward_ms': fwd_ms}
     if losses:
         timing['losses'] = loss_means
+    return poses_np, all_ids.cpu().numpy(), timing
+
+
+# ------------------------------------------------------------------------------------------------------ the test loop on a cloud bank
+def plan_windows(pair_keys, batch, max_bank_clouds):
+    """The schedule of run_test_shared, pure Python: walks `pair_keys` -- a list of (src_key, tgt_key), any hashable keys -- in its given
+    order, `batch` pairs per window, over a bank of at most max_bank_clouds clouds, and yields one dict per window:
+        'first', 'count'   the window's pairs: pair_keys[first : first + count]
+        'evict'            keys dropped from the bank before this window: the least recently used ones (by the last window that read
+                           them; the older bank position first among equals), never one this window reads, and only as many as the bank
+                           would otherwise exceed max_bank_clouds by
+        'keep'             the surviving clouds' indices in the bank as it stood, ascending (CloudBank.select's argument); None when
+                           nothing is evicted
+        'encode'           keys to encode, in order of first appearance: the window's fragments that are not in the bank; they are
+                           appended behind the surviving clouds
+        'src', 'tgt'       per pair the bank index, in that new bank, of its source and its target
+    ValueError when one window reads more distinct fragments than max_bank_clouds, naming the number it needs."""
+    if batch < 1:
+        raise ValueError(f'plan_windows: batch must be positive, got {batch}')
+    bank, last_use = [], {}
+    for w, first in enumerate(range(0, len(pair_keys), batch)):
+        win = pair_keys[first:first + batch]
+        need = list(dict.fromkeys(k for pair in win for k in pair))
+        if len(need) > max_bank_clouds:
+            raise ValueError(f'plan_windows: pairs {first} .. {first + len(win) - 1} read {len(need)} distinct fragments; max_bank_clouds must '
+                             f'be at least {len(need)} (got {max_bank_clouds})')
+        here = set(bank)
+        encode = [k for k in need if k not in here]
+        over = len(bank) + len(encode) - max_bank_clouds
+        evict, keep = [], None
+        if over > 0:
+            wanted = set(need)
+            cand = sorted((i for i, k in enumerate(bank) if k not in wanted), key=lambda i: (last_use[bank[i]], i))
+            gone = set(cand[:over])
+            evict = [bank[i] for i in cand[:over]]
+            keep = [i for i in range(len(bank)) if i not in gone]
+            bank = [bank[i] for i in keep]
+            for k in evict:
+                del last_use[k]
+        bank = bank + encode
+        at = {k: i for i, k in enumerate(bank)}
+        for k in need:
+            last_use[k] = w
+        yield {'first': first, 'count': len(win), 'evict': evict, 'keep': keep, 'encode': encode,
+               'src': [at[s] for s, _ in win], 'tgt': [at[t] for _, t in win]}
+
+
+def run_test_shared(model, pairs, batch, device, logger=None, max_pairs=None, max_bank_clouds=1024, losses=False):
+    """run_test over a pair source that names its fragments (pairs.fragment_keys(i) -> (src_key, tgt_key), pairs.load_fragment(key) ->
+    (n, 3) float32: ThreeDMatchPairs, SyntheticScenePairs), with every fragment's backbone run ONCE for as long as it stays in a bank of
+    at most max_bank_clouds clouds: per window of `batch` pairs (plan_windows) the missing fragments are loaded and encoded in one
+    RegTR.encode_clouds, joined to the bank (CloudBank.cat; on eviction CloudBank.select first) and the window's pairs registered in one
+    RegTR.register.  A loader thread reads the next windows' missing fragments and copies them up on a side stream while the current
+    window runs (as Prefetcher does for pairs; the LoaderPool processes are not used).  Under a process group every rank takes pairs i %
+    world as run_test does and encodes the fragments of its own shard.  Returns what run_test returns, through gather_poses; timing
+    additionally carries clouds_encoded, distinct_fragments and pair_slots (= 2 x pairs) of this rank.
+    Refused: a list of replicas, losses=True."""
+    import torch.distributed as dist
+    if isinstance(model, (list, tuple)):
+        raise NotImplementedError('run_test_shared: replicas are not implemented on the shared path (one model, one stream)')
+    if losses:
+        raise NotImplementedError('run_test_shared: losses=True is not implemented on the shared path (use run_test)')
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise RuntimeError('run_test_shared runs on an MI355X (HIP) device only; there is no CPU path')
+    rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+    world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    n = len(pairs) if max_pairs is None else min(len(pairs), max_pairs)
+    mine = shard_pairs(n, rank, world)
+    model.eval()
+    t0 = time.perf_counter()
+    keys = [tuple(pairs.fragment_keys(i)) for i in mine]
+    plan = list(plan_windows(keys, batch, max_bank_clouds))          # (a capacity below one window's need raises here, before any work)
+    q = queue.Queue(maxsize=2)
+    copy_stream = torch.cuda.Stream(device=device, priority=-1)
+    stop = threading.Event()
+
+    def load():
+        try:
+            for w in plan:
+                if stop.is_set():
+                    return
+                host = [np.ascontiguousarray(pairs.load_fragment(k), dtype=np.float32) for k in w['encode']]
+                item = {}
+                with torch.cuda.stream(copy_stream):
+                    item['clouds'] = [torch.from_numpy(a).pin_memory().to(device, non_blocking=True) for a in host]
+                    item['ready'] = torch.cuda.Event()
+                    item['ready'].record(copy_stream)
+                q.put(item)
+        except BaseException as e:      # noqa: BLE001  (surfaced in the consumer)
+            q.put(e)
+    th = threading.Thread(target=load, daemon=True)
+    th.start()
+    bank, done, win_ms = None, [], []
+    try:
+        with torch.cuda.device(device), torch.no_grad():
+            for w in plan:
+                item = q.get()
+                if isinstance(item, BaseException):
+                    raise item
+                t_w = time.perf_counter()
+                cur = torch.cuda.current_stream(device)
+                cur.wait_event(item['ready'])
+                for t in item['clouds']:                     # allocated on the copy stream
+                    t.record_stream(cur)
+                if w['keep'] is not None:
+                    bank = bank.select(w['keep'])
+                if item['clouds']:
+                    new = model.encode_clouds(item['clouds'])
+                    bank = new if bank is None else type(new).cat([bank, new])
+                out = model.register(bank, w['src'], w['tgt'])
+                done.append(out['pose'][-1])                 # (count, 3, 4), stays on the device
+                win_ms.append(round((time.perf_counter() - t_w) * 1e3, 1))
+    finally:
+        stop.set()
+        while th.is_alive():                                 # (a loader blocked on a full queue after an error here)
+            try:
+                q.get_nowait()
+            except queue.Empty:
+                pass
+            th.join(timeout=0.05)
+    pose_t = torch.cat(done).reshape(-1, 12) if done else torch.zeros((0, 12), dtype=torch.float32, device=device)
+    id_t = torch.tensor(mine, dtype=torch.int32, device=device)
+    all_poses, all_ids = gather_poses(pose_t, id_t, n)
+    torch.cuda.synchronize(device)
+    elapsed = time.perf_counter() - t0
+    encoded = sum(len(w['encode']) for w in plan)
+    distinct = len({k for pair in keys for k in pair})
+    if logger and rank == 0:
+        logger.info(f'{n} pairs on {world} GPU(s) in {elapsed:.2f} s = {n / elapsed:.1f} pairs/s (incl. loading); rank 0 encoded {encoded} clouds '
+                    f'for {2 * len(mine)} pair slots ({distinct} distinct fragments)')
+    poses_np = all_poses.reshape(-1, 3, 4).cpu().numpy()
+    if not np.isfinite(poses_np).all():
+        bad = np.unique(np.nonzero(~np.isfinite(poses_np))[0])
+        raise RuntimeError(f'{len(bad)} of {len(poses_np)} predicted poses are not finite (first pair ids: {all_ids.cpu().numpy()[bad[:5]].tolist()}); '
+                           'check the inputs and the checkpoint for non-finite values')
+    timing = {'elapsed_s': elapsed, 'pairs': n, 'world': world, 'loader': None, 'forward_ms': win_ms, 'clouds_encoded': encoded,
+              'distinct_fragments': distinct, 'pair_slots': 2 * len(mine)}
     return poses_np, all_ids.cpu().numpy(), timing

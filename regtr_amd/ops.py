@@ -1468,3 +1468,32 @@ def clip_adam_step(params, grads, exp_avgs, exp_avg_sqs, scalars, max_norm, deco
     check(_lib.lib().regtr_adam_step(tab.ctypes.data if len(keep) else None, len(keep), ptr(norm_coef[1:]), 1 if decoupled else 0, stream()),
           'regtr_adam_step')
     return norm_coef
+
+
+# ------------------------------------------------------------------------------------------------ the cloud bank
+def gather_segments(feats, bank_seg, cloud_of, dst_seg, n_out, max_len, pe=None, xyz=None, out=None):
+    """Whole clouds of a packed bank in a new order, one launch (regtr_gather_segments): destination cloud d is bank cloud cloud_of[d],
+    its rows copied from bank_seg[cloud_of[d]] ... to dst_seg[d] ....  feats (N, D) float32 with D % 4 == 0, pe (N, D) and xyz (N, 3)
+    optional; bank_seg (C + 1,), cloud_of (n_dst,), dst_seg (n_dst [+ 1],) int32 device tensors; n_out = the selected clouds' rows,
+    max_len = the longest selected cloud, both known to the host.  -> (feats', pe' | None, xyz' | None) with n_out rows each; out: the
+    same triple preallocated.  Bit-exact copies; nothing here synchronises."""
+    for t in (feats, bank_seg, cloud_of, dst_seg, pe, xyz):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.device.type != 'cuda'):
+            raise RuntimeError(f'gather_segments: every tensor must be on the GPU (got {getattr(t, "device", type(t))}); there is no CPU fallback')
+    N, D = feats.shape
+    if (pe is not None and tuple(pe.shape) != (N, D)) or (xyz is not None and tuple(xyz.shape) != (N, 3)):
+        raise RuntimeError(f'gather_segments: feats (N, D), pe (N, D), xyz (N, 3) expected, got {tuple(feats.shape)}, '
+                           f'{None if pe is None else tuple(pe.shape)}, {None if xyz is None else tuple(xyz.shape)}')
+    n_dst, n_out, max_len = cloud_of.numel(), int(n_out), int(max_len)
+    if dst_seg.numel() < n_dst or bank_seg.numel() < 1:
+        raise RuntimeError(f'gather_segments: dst_seg needs {n_dst} entries and bank_seg at least one, got {dst_seg.numel()}, {bank_seg.numel()}')
+    if out is None:
+        new = lambda src, w: None if src is None else torch.empty((n_out, w), dtype=torch.float32, device=feats.device)
+        out = (new(feats, D), new(pe, D), new(xyz, 3))
+    o_f, o_p, o_x = out
+    if tuple(o_f.shape) != (n_out, D) or (pe is not None and tuple(o_p.shape) != (n_out, D)) or (xyz is not None and tuple(o_x.shape) != (n_out, 3)):
+        raise RuntimeError(f'gather_segments: the outputs must have {n_out} rows of the inputs\' widths')
+    check(_lib.lib().regtr_gather_segments(ptr(feats), ptr(pe), ptr(xyz), D, iptr(bank_seg), bank_seg.numel() - 1, N, iptr(cloud_of),
+                                           iptr(dst_seg), n_dst, n_out, max_len, ptr(o_f), ptr(o_p) if pe is not None else None,
+                                           ptr(o_x) if xyz is not None else None, stream()), 'regtr_gather_segments')
+    return o_f, (o_p if pe is not None else None), (o_x if xyz is not None else None)

@@ -317,6 +317,8 @@ class RegTR(nn.Module):
     def device(self):
         return next(self.parameters()).device
 
+    # (forward's placement checks and its status-word / fp32x3 fallback policy have a twin for encode_clouds / register below:
+    #  _check_placement and _run_checked.  A change to the policy here belongs there too.)
     @torch.no_grad()
     def forward(self, batch):
         dev = batch['src_xyz'][0].device
@@ -484,6 +486,157 @@ class RegTR(nn.Module):
             'pose': pose,
         }
         return outputs
+
+    # ------------------------------------------------------------------------------------------ encode each cloud once, register many pairs
+    def _check_placement(self, dev, tensors, what):
+        """forward's checks, for the calls below: float32 parameters, the model and every tensor on one GPU."""
+        if dev.type != 'cuda':
+            raise RuntimeError('regtr_amd.RegTR runs on an MI355X (HIP) device only; there is no CPU path')
+        if not self._params_checked:
+            bad = [n for n, p in self.named_parameters() if p.dtype != torch.float32]
+            if bad:
+                raise RuntimeError(f'regtr_amd.RegTR computes in float32; non-float32 parameters: {bad[:3]} ...')
+            self._model_device = next(self.parameters()).device
+            self._params_checked = True
+        if any(t.device != dev for t in tensors) or self._model_device != dev:
+            raise RuntimeError(f'RegTR.{what}: the model ({self._model_device}) and every input must live on one GPU ({dev})')
+
+    def _run_checked(self, dev, run, what, pose_of=None):
+        """run() under forward's arithmetic policy: the model's compute_dtype, the f16 status word read ONCE at the end (the call's only
+        host wait of its own), on a range trip the whole of run() again in fp32x3 arithmetic (f16_range_fallbacks), a non-finite pose
+        with every f16 product finite reported and returned as it is (nonfinite_pose_forwards; the first time, as in forward, checked
+        by one fp32x3 re-run whose finite result would be returned).  pose_of: run()'s result -> its pose tensor."""
+        check = self._f16_pair and self._range_check
+        with context.forward(dev, f16_pair=self._f16_pair, status=None) as ctx:
+            if not check:
+                return run()
+            st_dev, st_host = self._status_word(dev)
+            ctx.status = st_dev
+            st_dev.zero_()
+            out = run()
+            st_host.copy_(st_dev, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record()
+            done.synchronize()
+            bits = int(st_host[0])
+        if bits == 0:
+            return out
+        if not bits & context.STATUS_F16_RANGE:
+            self.nonfinite_pose_forwards += 1
+            if self.nonfinite_pose_forwards == 1 and self._f16_pair and pose_of is not None:
+                with context.forward(dev, f16_pair=False, force_x3=True, status=None):
+                    again = run()
+                if bool(torch.isfinite(pose_of(again)).all()):
+                    self.logger.error("%s: non-finite pose with NO f16 range bit set, but the fp32x3 re-run is finite: an f16 pair kernel missed its "
+                                      "range report (status %d) -- returning the fp32x3 result; set cfg.compute_dtype: fp32x3 and report this", what, bits)
+                    return again
+                self.logger.warning('%s: non-finite pose (status %d): the fp32x3 re-run is non-finite too -- the inputs or the checkpoint hold NaN / Inf',
+                                    what, bits)
+            if _throttled(self.nonfinite_pose_forwards):
+                self.logger.warning('%s: non-finite pose in the output (status %d; call no. %d with this condition): every f16 pair product was '
+                                    'finite, so check the input clouds and the checkpoint for NaN / Inf -- returned as is, not re-run',
+                                    what, bits, self.nonfinite_pose_forwards)
+            return out
+        self.f16_range_fallbacks += 1
+        if _throttled(self.f16_range_fallbacks):
+            self.logger.warning('%s: f16 pair operand range exceeded (status %d; fallback no. %d) -- re-run with six-term bf16 splits '
+                                "(compute_dtype 'fp32x3' arithmetic); set cfg.compute_dtype: fp32x3 to skip the first attempt",
+                                what, bits, self.f16_range_fallbacks)
+        with context.forward(dev, f16_pair=False, force_x3=True, status=None):
+            return run()
+
+    def _needs_pe(self):
+        return bool(self.cfg.transformer_encoder_has_pos_emb) or isinstance(self.correspondence_decoder, CorrespondenceDecoder)
+
+    @torch.no_grad()
+    def encode_clouds(self, clouds):
+        """Everything forward computes of a cloud before it meets a partner, for any number of clouds (nothing is paired, the count
+        need not be even): -> regtr_amd.CloudBank with the coarsest key points, feat_proj's output and (when the cross-encoder or the
+        attention-valued head reads one) the positional embedding of every cloud, in the order given.  clouds: a list of (n, 3) float32
+        GPU tensors.  Runs forward's own code -- _backbone (the two-stream path and the capacity-overflow rebuild included; parity mode
+        cfg.kpconv_ref_row_order as it is), the feat_proj GEMM on the prepared weight, pos_embed -- under forward's arithmetic policy
+        (_run_checked).  The bank is valid for this model until one of its kpf_encoder / feat_proj / pos_embed weights changes."""
+        from .cloud_bank import CloudBank, model_stamp
+        clouds = list(clouds)
+        if not clouds:
+            raise ValueError('RegTR.encode_clouds: no clouds')
+        if any(not isinstance(c, torch.Tensor) for c in clouds):
+            raise TypeError('RegTR.encode_clouds: clouds must be a list of (n, 3) float32 GPU tensors')
+        dev = clouds[0].device
+        self._check_placement(dev, clouds, 'encode_clouds')
+        stamp = model_stamp(self)
+
+        def run():
+            batch = {'src_xyz': clouds, 'tgt_xyz': []}
+            feats_un, meta = self._backbone(batch, dev)
+            wt = _prepared(self._cache, 'feat_proj', self.feat_proj.weight, lambda w: ops.SplitWeight(w, 'nk'))
+            feats = ops.gemm(feats_un, wt, bias=self.feat_proj.bias.detach())
+            xyz_c = meta['points'][-1].clone()       # (a row slice of the pyramid's capacity-sized buffer: the bank keeps its own N x 12 bytes)
+            pe = self.pos_embed(xyz_c) if self._needs_pe() else None
+            return CloudBank(xyz_c, feats, pe, meta['_seg_off'][-1].clone(), meta['_lens_host'][-1], stamp)
+        return self._run_checked(dev, run, 'encode_clouds')
+
+    @torch.no_grad()
+    def register(self, bank, src_idx, tgt_idx):
+        """The P pairs (bank cloud src_idx[k], bank cloud tgt_idx[k]) through everything forward runs after the projection: the
+        cross-encoder, the correspondence head and the pose solve -> the dict forward returns for the batch
+        {'src_xyz': [cloud src_idx[k]], 'tgt_xyz': [cloud tgt_idx[k]]}, as views of the packed results.  A cloud may appear any number
+        of times, on either side; i == j is allowed.  One regtr_gather_segments launch lays the 2P clouds' cached rows out in forward's
+        order (sources, then their partners), its tables built from bank.lens on the host and sent in one pinned, non-blocking copy;
+        register adds no host wait beyond forward's status read.  A range trip re-runs the call in fp32x3 arithmetic on the SAME bank.
+        Refused before any launch: an empty pair list, index lists of different lengths, an index outside the bank, a bank from
+        another model, another device or stale weights (CloudBank.check)."""
+        from .cloud_bank import CloudBank, upload_tables
+        if not isinstance(bank, CloudBank):
+            raise TypeError(f'RegTR.register: bank must be a regtr_amd.CloudBank (RegTR.encode_clouds), got {type(bank).__name__}')
+        src_idx, tgt_idx = [int(i) for i in src_idx], [int(i) for i in tgt_idx]
+        if len(src_idx) != len(tgt_idx):
+            raise ValueError(f'RegTR.register: {len(src_idx)} source and {len(tgt_idx)} target indices')
+        P = len(src_idx)
+        if P == 0:
+            raise ValueError('RegTR.register: no pairs')
+        bad = [i for i in src_idx + tgt_idx if not 0 <= i < len(bank)]
+        if bad:
+            raise IndexError(f'RegTR.register: cloud {bad[0]} is not in a bank of {len(bank)}')
+        dev = bank.device
+        self._check_placement(dev, (bank.feats,), 'register')
+        bank.check(self, 'RegTR.register')
+        if self._needs_pe() and bank.pe is None:
+            raise RuntimeError('RegTR.register: the bank carries no positional embedding but this model reads one')
+        order = src_idx + tgt_idx
+        lens = [bank.lens[c] for c in order]
+
+        def run():
+            seg_c, cloud_of, N, max_len = upload_tables(bank.lens, order, dev)
+            both_feats_un, pe_c, xyz_c = ops.gather_segments(bank.feats, bank.seg_off, cloud_of, seg_c, N, max_len, pe=bank.pe, xyz=bank.xyz)
+            pe = pe_c if self.cfg.transformer_encoder_has_pos_emb else None
+            kv_self, kv_cross = self._kv_tables(P, dev)
+            feats_cond = self.transformer_encoder(both_feats_un, pe, seg_c, kv_self, kv_cross, max_len)
+            if isinstance(self.correspondence_decoder, CorrespondenceRegressor):
+                corr, logit = self.correspondence_decoder(feats_cond)
+            else:
+                corr, logit = self.correspondence_decoder(feats_cond, pe_c, xyz_c, seg_c, kv_cross, max_len)
+            pose = ops.weighted_procrustes(xyz_c, corr, logit, seg_c, P)
+            return both_feats_un, feats_cond, xyz_c, corr, logit, pose
+        both_feats_un, feats_cond, xyz_c, corr, logit, pose = self._run_checked(dev, run, 'register', pose_of=lambda r: r[-1])
+        off = [0]
+        for n in lens:
+            off.append(off[-1] + n)
+        sl = lambda c: slice(off[c], off[c + 1])
+        logit3 = logit.unsqueeze(-1)
+        return {
+            'src_feat_un': tuple(both_feats_un[sl(b)] for b in range(P)),
+            'tgt_feat_un': tuple(both_feats_un[sl(P + b)] for b in range(P)),
+            'src_feat': [feats_cond[:, sl(b)] for b in range(P)],
+            'tgt_feat': [feats_cond[:, sl(P + b)] for b in range(P)],
+            'src_kp': tuple(xyz_c[sl(b)] for b in range(P)),
+            'src_kp_warped': [corr[:, sl(b)] for b in range(P)],
+            'tgt_kp': tuple(xyz_c[sl(P + b)] for b in range(P)),
+            'tgt_kp_warped': [corr[:, sl(P + b)] for b in range(P)],
+            'src_overlap': [logit3[:, sl(b)] for b in range(P)],
+            'tgt_overlap': [logit3[:, sl(P + b)] for b in range(P)],
+            'pose': pose,
+        }
 
     # ------------------------------------------------------------------------------------------ training above a frozen backbone
     def _check_trainable(self, what):

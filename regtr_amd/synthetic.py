@@ -163,3 +163,40 @@ def synth_modelnet_cloud(cloud_id, num_points=2048):
     pts = np.concatenate([box, ball])
     pts /= max(1.0, float(np.linalg.norm(pts, axis=1).max()))
     return pts.astype(np.float32)[rng.permutation(num_points)]
+
+
+def synth_fragment_poses(scene_id, n_fragments):
+    """The world-to-fragment transforms of synth_fragments(scene_id, n_fragments, ...) -- random SE(3), rotation <= 45 deg, |t| <= 0.5 m,
+    from a generator of their own, so that they cost nothing to recompute and do not depend on the points -- and the ground truth they
+    imply: -> (world (F, 4, 4), rel (F, F, 4, 4)) float64, rel[a, b] = W_b W_a^-1 taking fragment a's frame into fragment b's, so
+    rel[b, c] rel[a, b] = rel[a, c]."""
+    if n_fragments < 1:
+        raise ValueError('synth_fragments: at least one fragment')
+    rng = np.random.default_rng([4243, int(scene_id)])
+    world = np.tile(np.eye(4), (n_fragments, 1, 1))
+    for k in range(n_fragments):
+        world[k, :3, :3], world[k, :3, 3] = random_se3(rng)
+    inv = np.linalg.inv(world)
+    rel = np.stack([np.stack([world[b] @ inv[a] for b in range(n_fragments)]) for a in range(n_fragments)])
+    return world, rel
+
+
+def synth_fragments(scene_id, n_fragments, pts=20000, view=0.6):
+    """n_fragments scans of ONE synthetic room (synth_scene), as a sensor sweeping along it would give them: fragment k sees the slab
+    [lo_k, lo_k + view] of the room's length (lo_k evenly spaced, so neighbours overlap most and the two ends least), loses cells to an
+    occlusion mask of its own, is moved into a frame of its own (synth_fragment_poses) and jittered by N(0, 5 mm).  The scene is sized
+    for ~pts points per slab before the uneven density along the room takes its share: fragments hold roughly 0.75 - 0.9 pts points.
+    Deterministic in (scene_id, n_fragments, pts, view).
+    -> (fragments: list of (n_k, 3) float32, rel: (F, F, 4, 4) float64, synth_fragment_poses' ground truth)."""
+    world, rel = synth_fragment_poses(scene_id, n_fragments)
+    rng = np.random.default_rng([4242, int(scene_id)])
+    kept = float(np.prod([1.0 - q for _, q in OCCLUSION]))       # what a fragment's own occlusion mask leaves of its slab
+    scene, X = synth_scene(rng, int(pts / (view * kept)))
+    frags = []
+    for k in range(n_fragments):
+        lo = (1.0 - view) * (k / (n_fragments - 1) if n_fragments > 1 else 0.5)
+        p = scene[(scene[:, 0] >= lo * X) & (scene[:, 0] <= (lo + view) * X)]
+        p = p[_occlusion_mask(rng, p)]
+        R, t = world[k, :3, :3], world[k, :3, 3]
+        frags.append((p @ R.T + t + rng.normal(scale=0.005, size=p.shape)).astype(np.float32))
+    return frags, rel

@@ -7,7 +7,9 @@
 Runs the MI355X-native RegTR inference path over the benchmark's pairs and writes `<log>/<benchmark>/<scene>/est.log`
 (3DMatch / 3DLoMatch) or `<log>/pred_transforms.npy` (ModelNet / ModelLoNet) in the reference's formats
 (models/generic_reg_model.py:194-195, 260-281), which the reference's evaluation scripts read unchanged.
-Inference only: no training, no tensorboard; --losses adds the reference's test losses ([Losses] line).  Extra flags: --batch (pairs per forward), --data_root, --synthetic N
+Inference only: no training, no tensorboard; --losses adds the reference's test losses ([Losses] line).  --share_backbone runs every
+fragment's backbone once and registers all its pairs against the cached result (RegTR.encode_clouds / register through
+harness.run_test_shared; --max_bank_clouds bounds the cache, --synthetic N --fragments F gives scene-style synthetic pairs).  Extra flags: --batch (pairs per forward), --data_root, --synthetic N
 (N deterministic synthetic pairs instead of the dataset files), --max_pairs, --preprocessor (cpu | gpu: which reference preprocessor's semantics;
 --neighbor_order / --voxel_key set its two rules one by one), --benchmark_dir (gt.log / gt.info folder: the
 Predator registration-recall table of benchmark/benchmark_predator.py is then printed, computed in process).
@@ -58,6 +60,13 @@ parser.add_argument('--max_pairs', type=int, default=None)
 parser.add_argument('--losses', action='store_true',
                     help='also compute the reference\'s test losses (RegTR.compute_loss per pair on GT overlap masks) and log a [Losses] line; '
                          '3DMatch-style pair sources only')
+parser.add_argument('--share_backbone', action='store_true',
+                    help='encode every fragment once and register all its pairs against the cached result (RegTR.encode_clouds / register, '
+                         'harness.run_test_shared): one model, one loader thread; not with --losses or --replicas')
+parser.add_argument('--fragments', type=int, default=0,
+                    help='with --synthetic N: scene-style pairs (harness.SyntheticScenePairs) -- rooms of F fragments each, 4 F pairs per room (the '
+                         "3DMatch lists' ~4 pairs per fragment), as many rooms as N pairs need")
+parser.add_argument('--max_bank_clouds', type=int, default=1024, help='--share_backbone: clouds kept encoded on the device (least recently used evicted)')
 parser.add_argument('--warmup_points', type=int, default=24000, help='points per cloud of the warm-up batch (larger than the data so that later batches fit the allocator\'s blocks)')
 parser.add_argument('--alloc_conf', type=str, default='', help='torch caching-allocator settings for the run (e.g. roundup_power2_divisions:8)')
 parser.add_argument('--reserve_gb', type=float, default=0, help='GiB reserved once and returned to the caching allocator\'s pool before the run (default 0 = off; measured: no effect on the forward-time spikes, which were GIL hand-offs, not hipMalloc)')
@@ -147,6 +156,15 @@ def main():
         logger.error('--losses: ModelNet losses are not implemented (3DMatch-style pair sources only, synthetic included)')
         sys.exit(-4)
 
+    if opt.share_backbone and (opt.losses or opt.replicas > 1):
+        logger.error('--share_backbone runs one model without the test losses: drop --losses / --replicas')
+        sys.exit(-4)
+    if opt.fragments and (opt.synthetic <= 0 or opt.materialize or opt.fragments < 2 or cfg.dataset != '3dmatch'):
+        logger.error('--fragments F (F >= 2) goes with --synthetic N on a 3dmatch config, without --materialize')
+        sys.exit(-4)
+    if opt.share_backbone:
+        opt.num_workers = 0            # the shared path has its own loader thread; the LoaderPool processes are not used
+
     if not torch.cuda.is_available():
         logger.error('regtr_amd runs on an MI355X (HIP) device only; there is no CPU path')
         sys.exit(-3)
@@ -179,6 +197,11 @@ def main():
         info = harness.materialize_synthetic(opt.materialize, opt.synthetic, overlap=opt.overlap, logger=logger if rank == 0 else None,
                                              rank=rank, world=world, distinct=opt.distinct)
         pairs = harness.ThreeDMatchPairs(info, opt.materialize, cache_dir=opt.cache_dir)
+    elif opt.synthetic > 0 and opt.fragments:
+        pps = min(4 * opt.fragments, opt.fragments * (opt.fragments - 1))
+        n_scenes = -(-opt.synthetic // pps)
+        pairs = harness.SyntheticScenePairs(n_scenes, opt.fragments, pps, points=20000, cache_scenes=min(n_scenes, max(opt.batch, 8)))      # (consecutive pairs walk the scenes: one window's worth stays generated)
+        opt.max_pairs = min(opt.synthetic, opt.max_pairs or opt.synthetic)
     elif opt.synthetic > 0:
         pairs = harness.SyntheticPairs(opt.synthetic, points=20000 if cfg.dataset == '3dmatch' else 717, overlap=opt.overlap)
     elif cfg.dataset == '3dmatch':
@@ -208,6 +231,11 @@ def main():
     # forwards in flight (round 6): replicas with the same weights, one per host thread / HIP stream (harness.run_test)
     from regtr_amd.workload import replicate
     n_rep = opt.replicas if opt.replicas > 0 else 3      # (also for --batch 1, the reference's loop: 349 -> 607 pairs/s end to end, profiles/r06_y_*)
+    if opt.share_backbone:
+        n_rep = 1
+        if not hasattr(pairs, 'fragment_keys'):
+            logger.error('--share_backbone needs a pair source that names its fragments (the dataset files, or --synthetic N --fragments F)')
+            sys.exit(-4)
     models = replicate(model.eval(), cfg, n_rep, device)
 
     if not opt.no_warmup:
@@ -226,9 +254,21 @@ def main():
         torch.cuda.synchronize(device)
         del wb
         logger.info(f'warm-up forward ({opt.batch} synthetic pairs, untimed): {time.perf_counter() - t_w:.2f} s')
+        if opt.share_backbone:       # the shared path's own launches (the gather, a register-sized cross-encoder) once, untimed
+            wc = [torch.from_numpy(gen[i % 2][i // 2 % 2]).to(device) for i in range(4)]
+            wbank = model.encode_clouds(wc)
+            model.register(wbank.select([0, 1, 2, 3]), [i % 4 for i in range(opt.batch)], [(i + 1) % 4 for i in range(opt.batch)])
+            torch.cuda.synchronize(device)
+            del wc, wbank
     t_run = time.perf_counter()
-    poses, ids, timing = harness.run_test(models if len(models) > 1 else model, pairs, opt.batch, device, logger, opt.max_pairs, loader_pool=pool,
-                                         losses=opt.losses)
+    if opt.share_backbone:
+        poses, ids, timing = harness.run_test_shared(model, pairs, opt.batch, device, logger, opt.max_pairs, max_bank_clouds=opt.max_bank_clouds)
+        logger.info(f'[Shared backbone] clouds_encoded / pair_slots = {timing["clouds_encoded"]} / {timing["pair_slots"]} = '
+                    f'{timing["clouds_encoded"] / max(timing["pair_slots"], 1):.3f} ({timing["distinct_fragments"]} distinct fragments, bank of at most '
+                    f'{opt.max_bank_clouds} clouds; this rank)')
+    else:
+        poses, ids, timing = harness.run_test(models if len(models) > 1 else model, pairs, opt.batch, device, logger, opt.max_pairs, loader_pool=pool,
+                                             losses=opt.losses)
     if pool is not None:
         logger.info(f'loader: {timing["loader"]}; forward ms (host clock, incl. the end-of-forward status wait): {timing["forward_ms"]}')
         pool.close()
@@ -236,7 +276,7 @@ def main():
     if rank == 0:
         recs, gts = [], []
         for pose, i in zip(poses, ids):
-            meta = pairs[int(i)] if not from_files else {'src_path': pairs.infos['src'][int(i)], 'tgt_path': pairs.infos['tgt'][int(i)],
+            meta = (pairs.meta(int(i)) if hasattr(pairs, 'meta') else pairs[int(i)]) if not from_files else {'src_path': pairs.infos['src'][int(i)], 'tgt_path': pairs.infos['tgt'][int(i)],
                                                             'pose': np.concatenate([pairs.infos['rot'][int(i)], pairs.infos['trans'][int(i)].reshape(3, 1)], 1)}
             recs.append({'src_path': meta['src_path'], 'tgt_path': meta['tgt_path'], 'pose': pose})
             gts.append(meta['pose'])
