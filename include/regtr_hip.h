@@ -899,6 +899,33 @@ int regtr_gather_segments(const float* feats, const float* pe, const float* xyz,
                           const int* cloud_of, const int* dst_seg, int n_dst, int n_out, int max_len, float* out_feats, float* out_pe,
                           float* out_xyz, void* stream);
 
+/* ---- the gradient bucket (regtr_amd/grad_bucket.py; csrc/grad_bucket.hip) -------------------------------------------------------------
+ * Gradient accumulation and the payload of data-parallel training's one all-reduce.  New entry points only: no existing signature
+ * changes, REGTR_ABI_VERSION stays as it is. */
+
+/* One tensor of regtr_grad_pack, filled on the HOST and read there (chunks of regtr_optim_chunk_tensors() tensors travel to the kernel
+ * by value: no device-side table, no copy, nothing kept between calls).  g: device pointer to n float32 elements, 4-byte aligned (16-byte
+ * alignment selects the 16-byte loads), or NULL; offset: the tensor's first element in the bucket, a multiple of 4. */
+typedef struct {
+    const float* g;
+    long long n;
+    long long offset;
+} regtr_bucket_tensor_t;
+
+/* Host only: elements per workgroup of regtr_grad_pack. */
+int regtr_grad_pack_slice(void);
+
+/* For every tensor t and element i < n_t of a float32 bucket of n_bucket elements:
+ *   accumulate == 0:  bucket[offset_t + i] = scale g_t[i]                                 (g_t NULL: 0)
+ *   accumulate != 0:  bucket[offset_t + i] = fmaf(scale, g_t[i], bucket[offset_t + i])    (g_t NULL: nothing is written)
+ * Elements of the bucket outside every segment are never written.  One owner per element, no atomics, no workspace, no host wait; the
+ * result depends on neither the grid nor a pointer's alignment (bit-reproducible).  Refused (REGTR_ERR_ARG, nothing launched): a
+ * negative count, NULL tensors with n_tensors > 0, a NULL bucket with an element to write to, an offset that is not a multiple of 4, a
+ * segment outside [0, n_bucket), segments that are not in ascending order or overlap, a bucket that is not 16-byte aligned, a g that is
+ * not 4-byte aligned, a NaN scale. */
+int regtr_grad_pack(const regtr_bucket_tensor_t* tensors, int n_tensors, float* bucket, long long n_bucket, float scale, int accumulate,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

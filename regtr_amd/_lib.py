@@ -162,6 +162,8 @@ SIGNATURES = {
     'regtr_grad_norm_finish': (_I, [_P, _c.c_longlong, _F, _P, _P]),
     'regtr_adam_step': (_I, [_P, _I, _P, _I, _P]),
     'regtr_gather_segments': (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    'regtr_grad_pack_slice': (_I, []),
+    'regtr_grad_pack': (_I, [_P, _I, _P, _c.c_longlong, _F, _I, _P]),
 }
 
 COMPOSITE = ('regtr_encoder_fwd', 'regtr_cross_encoder_fwd')      # bound through a GIL-releasing handle (see _load)

@@ -4,6 +4,9 @@ all_gather_into_tensor of (pose | pair id) rows padded to the common shard capac
 
 The reference has no distributed code at all (single process, one pair per step: trainer.py:177-211, conf
 test_batch_size: 1); this is the shard point its test loop offers.  No collective runs inside the forward.
+
+Training shards micro-batches instead (regtr_amd/grad_bucket.py, harness.train_loop): ONE all_reduce of the flat gradient bucket per
+optimiser step (all_reduce_sum), a start-up broadcast of rank 0's parameters, and one all_gather_object per validation pass.
 """
 import torch
 import torch.distributed as dist
@@ -55,3 +58,38 @@ def gather_poses(poses, pair_ids, n_total=None):
     ids = rows[:, 12].to(torch.int32)
     order = torch.argsort(ids)
     return rows[order, :12].contiguous(), ids[order]
+
+
+# ------------------------------------------------------------------------------------------------------ data-parallel training
+def rank_world():
+    """(rank, world size) of the initialised process group, (0, 1) without one."""
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_rank(), dist.get_world_size()
+    return 0, 1
+
+
+def all_reduce_sum(flat):
+    """The ONE collective of an optimiser step: the whole flat gradient bucket (segments, padding and the loss tail) summed over the ranks
+    in place.  Every rank scaled its share by 1 / (accumulate x world) when it packed it, so the sum is the mean; padding is zero on
+    every rank and stays zero.  Runs at world size 1 too (the same code path); without a process group it does nothing.  -> flat"""
+    if dist.is_available() and dist.is_initialized():
+        dist.all_reduce(flat, op=dist.ReduceOp.SUM)
+    return flat
+
+
+def broadcast_parameters(module):
+    """Start-up, off the hot path: rank 0's parameters and buffers to every rank, one broadcast per tensor."""
+    if dist.is_available() and dist.is_initialized():
+        with torch.no_grad():
+            for t in list(module.parameters()) + list(module.buffers()):
+                dist.broadcast(t, 0)
+
+
+def gather_in_order(indexed):
+    """indexed: this rank's [(global index, picklable object)] -> on EVERY rank the objects of all ranks ordered by index, through one
+    all_gather_object (validation outputs: a few scalars per batch).  Without a process group: this rank's, ordered."""
+    if dist.is_available() and dist.is_initialized():
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, list(indexed))
+        indexed = [x for part in parts for x in part]
+    return [obj for _, obj in sorted(indexed, key=lambda x: x[0])]

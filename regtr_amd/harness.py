@@ -680,7 +680,34 @@ def pose_errors(pred, gt):
 
 
 # ------------------------------------------------------------------------------------------------------ training input
-def train_batches(source, cfg, batch_size, seed, epochs=1, device=None, num_workers=4, loader_pool=None, first_step=0):
+def rank_batch_indices(n_items, batch_size, epochs, accumulate=1, rank=0, world=1, first_step=0):
+    """THE BATCH SEQUENCE of accumulated / data-parallel training, as plain host arithmetic.  The unsharded run's batches are numbered
+    j = 0, 1, ... across epochs (an epoch holds ceil(n_items / batch_size) of them).  Optimiser step s (from 1) with accumulate = k on
+    W ranks consumes the k W micro-batches j = ((s - 1) k + m) W + r, micro-step m on rank r: rank r gets the j with j % W == r, up to
+    the last COMPLETE group of k W batches -- a count every rank knows without communication.  first_step counts micro-batches: the
+    j below it are left out.  -> rank r's j, ascending.  (k, W) and (k W, 1) therefore average the same micro-batches per step."""
+    k, W = int(accumulate), int(world)
+    if k < 1 or W < 1 or not 0 <= int(rank) < W:
+        raise ValueError(f'accumulate >= 1, world >= 1 and 0 <= rank < world expected, got {accumulate}, {world}, {rank}')
+    total = int(epochs) * -(-int(n_items) // int(batch_size))
+    stop = total // (k * W) * (k * W)
+    return [j for j in range(int(first_step), stop) if j % W == int(rank)]
+
+
+def _epoch_batches(order, batch_size, epoch_first, wanted):
+    """The part of one epoch's visiting order that makes up the batches `wanted` (a set of global batch indices), and those indices in
+    order.  epoch_first: the index of the epoch's first batch.  Only the epoch's last batch can be short, so cutting the result into
+    batch_size pieces again gives back exactly the wanted batches."""
+    keep, js = [], []
+    for b in range(-(-len(order) // batch_size)):
+        if epoch_first + b in wanted:
+            keep += order[b * batch_size:(b + 1) * batch_size]
+            js.append(epoch_first + b)
+    return keep, js
+
+
+def train_batches(source, cfg, batch_size, seed, epochs=1, device=None, num_workers=4, loader_pool=None, first_step=0, accumulate=1,
+                  rank=0, world=1):
     """Generator of augmented training batches over a 3DMatch-style pair source (`source[i]` -> {'src_xyz', 'tgt_xyz', 'pose', 'idx'}:
     ThreeDMatchPairs, SyntheticPairs): the loader pool, pinned staging and side-stream H2D copy run_test reads its pairs through, then
     augment.train_batch on the resident raw clouds -- overlap masks of the clean pair, the reference's augmentation chain -- with
@@ -689,57 +716,52 @@ def train_batches(source, cfg, batch_size, seed, epochs=1, device=None, num_work
     caller (e.g. before the GPU was initialised); else one of num_workers processes is made here and closed at the end (0: one loader
     thread).  Each batch goes straight into RegTR.training_step; 'ids' names its pairs.  first_step: start the (seed, step) sequence at
     that batch (a resumed run): batches 0 .. first_step - 1 are neither loaded nor built, batch first_step is the one an unbroken run
-    yields there."""
+    yields there.  accumulate, rank, world: this rank's share of THE BATCH SEQUENCE (rank_batch_indices): only the batches j with
+    j % world == rank, up to the last complete group of accumulate x world, are loaded and built -- each still from (seed, j), so batch j
+    is the batch an unsharded run builds at j; first_step keeps counting micro-batches j.  The defaults yield every batch."""
     from .augment import train_batch
     device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    wanted = set(rank_batch_indices(len(source), batch_size, epochs, accumulate, rank, world, first_step))
+    per_epoch = -(-len(source) // int(batch_size))
     pool = loader_pool
     if pool is None and num_workers > 0:
         pool = LoaderPool(source, device, workers=num_workers, max_batch=batch_size)
-    step = 0
     try:
         for epoch in range(int(epochs)):
             order = np.random.default_rng([int(seed) & ((1 << 64) - 1), epoch]).permutation(len(source)).tolist()
-            order, step = _skip_batches(order, int(batch_size), step, int(first_step))
+            order, js = _epoch_batches(order, int(batch_size), epoch * per_epoch, wanted)
             if not order:
                 continue
             loader = pool.iterate(order, batch_size) if pool is not None else Prefetcher(source, order, batch_size, device)
-            for b in loader:
+            for b, step in zip(loader, js):            # (the loader first: it is run to its end, as many batches as js has entries)
                 gp = b['gt_pose'] if 'gt_pose' in b else [i_['pose'] for i_ in b['items']]
                 if any(g_ is None for g_ in gp):
                     raise RuntimeError('train_batches: the pair source gives no ground-truth pose')
                 pose = torch.from_numpy(np.stack([np.asarray(g_, dtype=np.float32)[:3] for g_ in gp])).to(device, non_blocking=True)
                 out = train_batch(b['src_xyz'], b['tgt_xyz'], pose, cfg, seed, step)
                 out['ids'] = b['ids'] if 'ids' in b else [i_['idx'] for i_ in b['items']]
-                step += 1
                 yield out
     finally:
         if pool is not None and loader_pool is None:
             pool.close()
 
 
-def _skip_batches(order, batch_size, step, first_step):
-    """An epoch's visiting order without the batches that lie before first_step, and the step its first remaining batch has."""
-    if step >= first_step:
-        return order, step
-    skip = min(first_step - step, -(-len(order) // batch_size))
-    return order[skip * batch_size:], step + skip
-
-
-def modelnet_train_batches(source, cfg, batch_size, seed, epochs=1, device=None, first_step=0):
+def modelnet_train_batches(source, cfg, batch_size, seed, epochs=1, device=None, first_step=0, accumulate=1, rank=0, world=1):
     """Generator of ModelNet training batches over any indexable source of (n, 3) arrays (`source[i]`; further columns such as ModelNet40's
     normals are dropped, data_loaders/modelnet.py:176-177): the clouds of a batch go to the device in one pinned copy, then
     augment.modelnet_train_batch builds the cropped, moved, resampled, jittered and shuffled pairs with their masks and pose there.
     `step` counts up from 0 across epochs, so batch k of a run is a function of (source, seed, k) alone.  Every epoch visits every cloud
     once in an order drawn from (seed, epoch); a last short batch is yielded as it is.  Each batch goes straight into
     RegTR.training_step; 'ids' names its clouds.  (A 2048-point cloud is 24 KB: there is nothing for a loader pool to hide.  No HDF5
-    reader here: hand in the arrays.)  first_step: as train_batches'."""
+    reader here: hand in the arrays.)  first_step, accumulate, rank, world: as train_batches'."""
     from .augment import modelnet_train_batch
     device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-    step = 0
+    wanted = set(rank_batch_indices(len(source), batch_size, epochs, accumulate, rank, world, first_step))
+    per_epoch = -(-len(source) // int(batch_size))
     for epoch in range(int(epochs)):
         order = np.random.default_rng([int(seed) & ((1 << 64) - 1), epoch]).permutation(len(source)).tolist()
-        order, step = _skip_batches(order, int(batch_size), step, int(first_step))
-        for lo in range(0, len(order), int(batch_size)):
+        order, js = _epoch_batches(order, int(batch_size), epoch * per_epoch, wanted)
+        for step, lo in zip(js, range(0, len(order), int(batch_size))):
             ids = order[lo:lo + int(batch_size)]
             clouds = [np.ascontiguousarray(np.asarray(source[i], dtype=np.float32)[:, :3]) for i in ids]
             lens = [len(c) for c in clouds]
@@ -748,7 +770,6 @@ def modelnet_train_batches(source, cfg, batch_size, seed, epochs=1, device=None,
                 flat = flat.pin_memory()
             out = modelnet_train_batch(list(torch.split(flat.to(device, non_blocking=True), lens)), cfg, seed, step)
             out['ids'] = ids
-            step += 1
             yield out
 
 
@@ -805,9 +826,40 @@ class CheckpointSaver:
                 obj.load_state_dict(state[k])
         return int(state.get('step', 0))
 
+    @staticmethod
+    def batching(path):
+        """(accumulate, world) a checkpoint (a file, or a directory as load() takes it) was written with; (1, 1) for a checkpoint of the
+        plain loop, which carries neither key."""
+        if os.path.isdir(path):
+            with open(os.path.join(path, 'checkpoints.txt')) as f:
+                path = os.path.join(path, f'model-{int(f.readline().split(":")[1])}.pth')
+        state = torch.load(path, map_location='cpu', weights_only=False)
+        return int(state.get('accumulate', 1)), int(state.get('world', 1))
+
+
+def _validate(model, val_batches):
+    """validation_step over this rank's share of the validation batches (batch i on rank i % world), the per-batch outputs gathered to
+    every rank in batch order by one all_gather_object (regtr_amd.distributed.gather_in_order; as host tensors, put back on their
+    device), then validation_epoch_end: every rank computes the same score.  Without a process group: the plain loop over all batches."""
+    from .distributed import gather_in_order, rank_world
+    rank, world = rank_world()
+    if world == 1 and not torch.distributed.is_initialized():
+        return model.validation_epoch_end([model.validation_step(vb, i) for i, vb in enumerate(val_batches())])
+    mine, dev = [], None
+    for i, vb in enumerate(val_batches()):
+        if i % world != rank:
+            continue
+        out = model.validation_step(vb, i)
+        dev = next(iter(out[0].values())).device
+        mine.append((i, tuple({k: v.cpu() for k, v in d.items()} for d in out)))
+    outputs = gather_in_order(mine)
+    if dev is None and outputs:              # (a rank without a batch of its own)
+        dev = next(model.parameters()).device
+    return model.validation_epoch_end([tuple({k: v.to(dev) for k, v in d.items()} for d in out) for out in outputs])
+
 
 def train_loop(model, batches, steps, first_step=0, train_backbone=True, validate_every=0, val_batches=None, saver=None, logger=None,
-               log_every=50):
+               log_every=50, accumulate=1):
     """The reference's training loop (trainer.py:95-161) without tqdm and tensorboard: for each of `steps` batches of the iterable
     `batches` -- optimizer.zero_grad(), RegTR.training_step, backward, optimizer.step() (the gradient clip is inside it),
     scheduler.step() -- with model.optimizer / model.scheduler from RegTR.configure_optimizers (called here if the model has none yet).
@@ -816,24 +868,71 @@ def train_loop(model, batches, steps, first_step=0, train_backbone=True, validat
     log_every steps prints it.  validate_every > 0 with val_batches (a callable returning an iterable of batches): every
     validate_every-th global step runs validation_step over them, validation_epoch_end, and saver.save(model, step, score,
     optimizer=, scheduler=) (a CheckpointSaver).  -> {'step', 'loss_smooth' (device scalar), 'loss_avg' {key: device scalar},
-    'scores' [(step, score)], 'validation' the last validation_epoch_end outputs}."""
+    'scores' [(step, score)], 'validation' the last validation_epoch_end outputs}.
+    accumulate = k > 1, or an initialised process group (W ranks; `batches` is then this rank's share, train_batches(..., accumulate=,
+    rank=, world=)): THE BUCKET PATH.  An optimiser step is k x (training_step, backward, GradBucket.add(1 / (k W), the stacked
+    losses), gradients back to None), ONE all-reduce of the flat bucket, GradBucket.attach(), optimizer.step(), scheduler.step(); `steps`
+    and the global step count optimiser steps, and the logged and averaged losses are the bucket tail's: the mean over the step's micro-
+    batches and ranks.  Rank 0's parameters are broadcast once at the start; validation is sharded over the ranks (_validate) and rank 0
+    alone logs and saves -- checkpoints then carry 'accumulate' and 'world'.  With accumulate == 1 and no process group the loop is
+    the plain one: no bucket, the same launches, the same four checkpoint keys."""
     if getattr(model, 'optimizer', None) is None:
         model.configure_optimizers(train_backbone=train_backbone)
     opt, sched = model.optimizer, model.scheduler
     step = int(first_step)
     sums, smooth, n_done, scores, last_val = {}, None, 0, [], None
     it = iter(batches)
+    from .distributed import broadcast_parameters, rank_world
+    n_acc = int(accumulate)
+    if n_acc < 1:
+        raise ValueError(f'train_loop: accumulate must be at least 1, got {accumulate}')
+    rank, world = rank_world()
+    grouped = torch.distributed.is_available() and torch.distributed.is_initialized()
+    bucketed = n_acc > 1 or grouped
+    bucket, keys = None, None
+    extra_ckpt = {'accumulate': n_acc, 'world': world} if n_acc * world > 1 else {}
+    if grouped:
+        broadcast_parameters(model)
+    if rank != 0:
+        logger, saver = None, None
     while n_done < int(steps):
-        try:
-            batch = next(it)
-        except StopIteration:
-            break
-        step += 1
-        opt.zero_grad()
-        _, losses = model.training_step(batch, step, train_backbone=train_backbone)
-        losses['total'].backward()
-        opt.step()
-        sched.step()
+        if bucketed:
+            for _ in range(n_acc):
+                try:
+                    batch = next(it)
+                except StopIteration:        # (the generators end on a complete group; an iterable that ends inside one ends the run,
+                    batch = None             #  and that group's micro-batches are dropped)
+                    break
+                opt.zero_grad()
+                _, losses = model.training_step(batch, step + 1, train_backbone=train_backbone)
+                losses['total'].backward()
+                if bucket is None:
+                    from .grad_bucket import GradBucket
+                    keys = list(losses)
+                    bucket = GradBucket(list(model.named_parameters()), n_extra=len(keys))
+                bucket.add(1.0 / (n_acc * world), torch.stack([losses[k_].detach() for k_ in keys]))
+            opt.zero_grad()
+            if batch is None:
+                if bucket is not None:
+                    bucket.reset()           # (the incomplete group's partial sums are not a step)
+                break
+            step += 1
+            bucket.all_reduce()
+            bucket.attach()
+            opt.step()
+            sched.step()
+            losses = dict(zip(keys, bucket.extra().clone().unbind(0)))
+        else:
+            try:
+                batch = next(it)
+            except StopIteration:
+                break
+            step += 1
+            opt.zero_grad()
+            _, losses = model.training_step(batch, step, train_backbone=train_backbone)
+            losses['total'].backward()
+            opt.step()
+            sched.step()
         n_done += 1
         with torch.no_grad():
             for k, v in losses.items():
@@ -844,13 +943,12 @@ def train_loop(model, batches, steps, first_step=0, train_backbone=True, validat
         if logger is not None and (n_done == 1 or step % int(log_every) == 0):
             logger.info(f'step {step}: smoothed total loss {smooth.item():.4g}, lr {opt.param_groups[0]["lr"]:.3g}')      # the one host read
         if validate_every > 0 and val_batches is not None and step % int(validate_every) == 0:
-            outputs = [model.validation_step(vb, i) for i, vb in enumerate(val_batches())]
-            score, last_val = model.validation_epoch_end(outputs)
+            score, last_val = _validate(model, val_batches)
             scores.append((step, score))
             if logger is not None:
                 logger.info(f'validation at step {step}: score {score:.4f}, total loss {float(last_val["losses"]["total"]):.4g}')
             if saver is not None:
-                path = saver.save(model, step, score, optimizer=opt, scheduler=sched)
+                path = saver.save(model, step, score, optimizer=opt, scheduler=sched, **extra_ckpt)
                 if logger is not None:
                     logger.info(f'Saved checkpoint: {path} (best step {saver.best_step})')
     return {'step': step, 'loss_smooth': smooth, 'loss_avg': {k: v / max(n_done, 1) for k, v in sums.items()}, 'scores': scores,

@@ -1470,6 +1470,50 @@ def clip_adam_step(params, grads, exp_avgs, exp_avg_sqs, scalars, max_norm, deco
     return norm_coef
 
 
+# ------------------------------------------------------------------------------------------------ gradient bucket (csrc/grad_bucket.hip)
+_BUCKET_DTYPE = None
+
+
+def grad_pack_slice():
+    """Elements per workgroup of grad_pack -- tests straddle it."""
+    return int(_lib.lib().regtr_grad_pack_slice())
+
+
+def grad_pack(grads, offsets, bucket, scale, accumulate, sizes=None):
+    """One launch per 48 tensors (regtr_grad_pack): bucket[offsets[t] + i] = scale grads[t][i], or with accumulate
+    fmaf(scale, grads[t][i], bucket[offsets[t] + i]).  grads: float32 GPU tensors or None (None: zeros under assign, untouched under
+    accumulate; its length then comes from sizes[t]); offsets: ascending multiples of 4, the segments inside the bucket and disjoint;
+    bucket: a contiguous float32 GPU tensor.  Checked once, on the current stream, no host wait.  Elements of the bucket outside every
+    segment are not written.  Refused with a Python exception: CPU tensors, tensors that are not float32 or sit on another device; what
+    the library refuses (include/regtr_hip.h).  A non-contiguous gradient is made contiguous."""
+    global _BUCKET_DTYPE
+    import numpy as np
+    if _BUCKET_DTYPE is None:
+        _BUCKET_DTYPE = np.dtype([('g', np.uint64), ('n', np.int64), ('offset', np.int64)], align=True)
+        assert _BUCKET_DTYPE.itemsize == 24
+    n = len(grads)
+    if len(offsets) != n or (sizes is not None and len(sizes) != n):
+        raise RuntimeError('grad_pack: grads, offsets (and sizes) must have one entry per tensor')
+    if not isinstance(bucket, torch.Tensor) or not bucket.is_cuda:
+        raise RuntimeError(f'grad_pack: the bucket must be a GPU tensor (got {getattr(bucket, "device", type(bucket))}); there is no CPU fallback')
+    have = [g for g in grads if g is not None]
+    with _lib.on_device(bucket.device):
+        if have and not _optim_all_ok((have,)):
+            _optim_explain(have, None, None, None, 'grad_pack')
+        keep = [g if g is None or g.is_contiguous() else g.contiguous() for g in grads]
+        tab = np.zeros(n, dtype=_BUCKET_DTYPE)
+        if n:
+            if sizes is None and len(have) != n:
+                raise RuntimeError('grad_pack: a None gradient needs its length in sizes')
+            tab['g'] = [0 if g is None else g.data_ptr() for g in keep]
+            tab['n'] = [int(sizes[i]) if g is None else g.numel() for i, g in enumerate(keep)]
+            tab['offset'] = offsets
+            if sizes is not None and tab['n'].tolist() != [int(s) for s in sizes]:
+                raise RuntimeError('grad_pack: a gradient\'s element count differs from its entry in sizes')
+        check(_lib.lib().regtr_grad_pack(tab.ctypes.data if n else None, n, ptr(bucket), bucket.numel(), float(scale), 1 if accumulate else 0,
+                                         stream()), 'regtr_grad_pack')
+
+
 # ------------------------------------------------------------------------------------------------ the cloud bank
 def gather_segments(feats, bank_seg, cloud_of, dst_seg, n_out, max_len, pe=None, xyz=None, out=None):
     """Whole clouds of a packed bank in a new order, one launch (regtr_gather_segments): destination cloud d is bank cloud cloud_of[d],

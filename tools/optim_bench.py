@@ -71,6 +71,7 @@ def build(name, dev):
         model.optimizer.zero_grad()
         _, losses = model.training_step(make(), train_backbone=True)
         losses['total'].backward()
+        return losses
     return model, fwd_bwd
 
 
