@@ -867,8 +867,8 @@ int regtr_grad_sumsq(const regtr_optim_tensor_t* tensors, int n_tensors, double*
 
 /* Second half: one workgroup adds the partials in float64 in a fixed order; norm_coef [2] (float32, device) = {total_norm =
  * sqrt(sum), clip_coef = min(1, max_norm / (total_norm + 1e-6))} -- torch.nn.utils.clip_grad_norm_'s formula in float32.  max_norm
- * <= 0: no clipping, clip_coef = 1 and the norm is still written.  A NaN norm gives a NaN coefficient (no skip logic).  n_partials
- * == 0 gives a norm of 0.  Refused: a negative count, a NaN max_norm, NULLs. */
+ * <= 0: no clipping, clip_coef = 1 and the norm is still written.  A NaN norm gives a NaN coefficient (no skip logic here: that is
+ * regtr_grad_norm_finish_guarded below).  n_partials == 0 gives a norm of 0.  Refused: a negative count, a NaN max_norm, NULLs. */
 int regtr_grad_norm_finish(const double* partials, long long n_partials, float max_norm, float* norm_coef, void* stream);
 
 /* torch's single-tensor AdamW (decoupled != 0) or Adam (decoupled == 0, weight decay added to the gradient) on every tensor, per
@@ -880,6 +880,62 @@ int regtr_grad_norm_finish(const double* partials, long long n_partials, float m
  * Refused: negative counts, NULLs with work to do, misaligned pointers, bias corrections that are not positive, a negative eps, NaN
  * scalars. */
 int regtr_adam_step(const regtr_optim_tensor_t* tensors, int n_tensors, const float* clip_coef, int decoupled, void* stream);
+
+/* ---- the guarded optimiser step (FusedAdamW(skip_nonfinite=True); csrc/optim.hip) -----------------------------------------------------
+ * torch's GradScaler / fused-optimiser found_inf behaviour: a step whose gradient is not finite is left out ON THE DEVICE -- no host
+ * read, no host decision.  New entry points beside the ones above: no existing signature changes, REGTR_ABI_VERSION stays as it is.
+ *
+ * THE GUARD WORD: four int32 on the device, {ok, applied_steps, skipped_steps, reserved}, zeroed by the caller once.  It is written by
+ * ONE lane of ONE workgroup (regtr_grad_norm_finish_guarded) with ordinary stores -- no atomics -- and read, guard[0] only and once per
+ * workgroup, by regtr_adam_step_guarded (and, as a per-micro-batch flag, by regtr_grad_pack_guarded). */
+
+/* One tensor of regtr_adam_step_guarded, filled on the HOST.  p, g, m, v, n as in regtr_optim_tensor_t.  The hyper-parameters stay
+ * float64 all the way into the kernel, which forms every float32 scalar itself, each rounded once and in regtr_adam_step's order:
+ * (float)(1 - lr wd), (float)wd, (float)beta, (float)(1 - beta), (float)eps and, from the tensor's own step count t on the device,
+ * (float)(lr / (1 - beta1^t)) and (float)sqrt(1 - beta2^t), with beta^t formed by binary exponentiation over the integer t (r = 1; while
+ * t: if t odd r = r b; b = b b; t >>= 1) -- never the math library's pow -- every product a double-double one (Dekker's, from float64
+ * multiplies, adds and subtracts in a fixed order, no fma): within 1 ulp of the correctly rounded power, and a numpy restatement
+ * reproduces it bit for bit (plain float64 squarings were up to 5e4 ulp off at t <= 2^20).  step_index: the tensor's entry in the
+ * step-count vector; distinct within a call. */
+typedef struct {
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    long long n;
+    double lr, weight_decay, beta1, beta2, eps;
+    int step_index;
+} regtr_optim_guarded_tensor_t;
+
+/* Host only: tensors per launch of regtr_adam_step_guarded (fewer than regtr_optim_chunk_tensors(): the entries are larger and the
+ * descriptor still travels by value inside the 4 KiB kernel-argument segment). */
+int regtr_optim_guarded_chunk_tensors(void);
+
+/* regtr_grad_norm_finish with three changes.  grad_scale: an optional device float32 (NULL = 1) that multiplies the norm BEFORE the
+ * clip coefficient is formed: norm_coef = {total_norm = (float)sqrt(sum) grad_scale, clip_coef = min(1, max_norm / (total_norm + 1e-6))}.
+ * guard[0] = ok = 1 exactly when (float)sqrt(sum) * grad_scale is finite and grad_scale is finite, else 0; guard[1] += ok; guard[2] +=
+ * 1 - ok.  With grad_scale NULL or exactly 1.0, norm_coef has regtr_grad_norm_finish's bits.  A gradient whose elements are all finite
+ * but whose float32 norm overflows (3e38 in every element) counts as NON-FINITE: the coefficient could not be formed from it.  Refused:
+ * a negative count, a NaN max_norm, NULL partials with n_partials > 0, a NULL norm_coef or guard, pointers that are not 4-byte aligned. */
+int regtr_grad_norm_finish_guarded(const double* partials, long long n_partials, float max_norm, const float* grad_scale, float* norm_coef,
+                                   int* guard, void* stream);
+
+/* regtr_adam_step under the guard.  guard[0] == 0: returns without writing a single byte of p, m, v, steps or step_scalars.  guard[0]
+ * != 0: first steps[step_index] += 1 for every tensor of the call (float32 counts, torch's layout; an empty tensor's too) and the
+ * tensor's two per-step scalars from the advanced count (see regtr_optim_guarded_tensor_t) into step_scalars[2 step_index ..], once per
+ * tensor; then regtr_adam_step's update with g' = (g grad_scale) clip_coef (grad_scale: device float32, NULL = 1; exactly 1.0 leaves
+ * g's bits) and those scalars.  steps [n_steps], step_scalars [2 n_steps]: device float32, the second a workspace the call owns while
+ * it runs (nothing is read from it that the call did not write).  g is not modified.  The launches per
+ * regtr_optim_guarded_chunk_tensors() tensors: one tiny one for the counts and scalars, one for the update.  Bit-reproducible.  Refused:
+ * negative counts, NULLs with work to do (tensors, steps, step_scalars, guard; p, g, m, v of a non-empty tensor), misaligned pointers,
+ * a step_index outside [0, n_steps), a negative or NaN eps, NaN lr or weight_decay, a beta outside [0, 1). */
+int regtr_adam_step_guarded(const regtr_optim_guarded_tensor_t* tensors, int n_tensors, float* steps, float* step_scalars, long long n_steps,
+                            const float* clip_coef, const float* grad_scale, const int* guard, int decoupled, void* stream);
+
+/* out [2 n] (device float32) = for every step count steps[i] (device float32, integer-valued) the two scalars regtr_adam_step_guarded
+ * forms from it: {(float)(lr / (1 - beta1^t)), (float)sqrt(1 - beta2^t)} -- the same device function, for tests and restatements.
+ * Refused: a negative count, NULLs with n > 0, misaligned pointers. */
+int regtr_adam_bias_scalars(double lr, double beta1, double beta2, const float* steps, int n, float* out, void* stream);
 
 /* ---- the cloud bank (regtr_amd/cloud_bank.py, RegTR.encode_clouds / register; csrc/cloud_bank.hip) ------------------------------------
  * A new entry point only: no existing signature changes, REGTR_ABI_VERSION stays as it is. */
@@ -925,6 +981,16 @@ int regtr_grad_pack_slice(void);
  * not 4-byte aligned, a NaN scale. */
 int regtr_grad_pack(const regtr_bucket_tensor_t* tensors, int n_tensors, float* bucket, long long n_bucket, float scale, int accumulate,
                     void* stream);
+
+/* regtr_grad_pack under a device flag (GradBucket(skip_nonfinite=True)): flag[0] != 0 -- regtr_grad_pack's arithmetic exactly; flag[0]
+ * == 0 -- zeros in every segment under assign (accumulate == 0), nothing written under accumulate.  Elements outside every segment are
+ * never written, as above.  flag: device int32 (a guard word's ok, from regtr_grad_sumsq + regtr_grad_norm_finish_guarded over the
+ * micro-batch's gradients), read once per workgroup.  n_good: an optional device float32 outside every segment (NULL: none); one lane
+ * of one workgroup writes n_good = (accumulate ? n_good : 0) + (flag != 0) with ordinary stores -- the count of micro-batches the bucket
+ * holds, never scaled; it is written even when no tensor has an element.  Refused: what regtr_grad_pack refuses, a NULL flag, a flag or
+ * n_good that is not 4-byte aligned. */
+int regtr_grad_pack_guarded(const regtr_bucket_tensor_t* tensors, int n_tensors, float* bucket, long long n_bucket, float scale,
+                            int accumulate, const int* flag, float* n_good, void* stream);
 
 #ifdef __cplusplus
 }

@@ -164,6 +164,11 @@ SIGNATURES = {
     'regtr_gather_segments': (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     'regtr_grad_pack_slice': (_I, []),
     'regtr_grad_pack': (_I, [_P, _I, _P, _c.c_longlong, _F, _I, _P]),
+    'regtr_grad_pack_guarded': (_I, [_P, _I, _P, _c.c_longlong, _F, _I, _P, _P, _P]),
+    'regtr_optim_guarded_chunk_tensors': (_I, []),
+    'regtr_grad_norm_finish_guarded': (_I, [_P, _c.c_longlong, _F, _P, _P, _P, _P]),
+    'regtr_adam_step_guarded': (_I, [_P, _I, _P, _P, _c.c_longlong, _P, _P, _P, _I, _P]),
+    'regtr_adam_bias_scalars': (_I, [_c.c_double, _c.c_double, _c.c_double, _P, _I, _P, _P]),
 }
 
 COMPOSITE = ('regtr_encoder_fwd', 'regtr_cross_encoder_fwd')      # bound through a GIL-releasing handle (see _load)

@@ -115,6 +115,52 @@ __global__ __launch_bounds__(GB_THREADS) void k_grad_pack(const GbChunk c, float
     }
 }
 
+// k_grad_pack under a device flag (skip_nonfinite): flag[0] != 0 -- k_grad_pack's arithmetic exactly; flag[0] == 0 -- zeros in every
+// segment under assign, nothing written under accumulate.  The flag is wave-uniform and read once per workgroup.  n_good (optional, the
+// first launch of a call only): thread 0 of workgroup 0 counts the flag into it with ordinary stores -- set under assign, added under
+// accumulate, never scaled.  The grid holds at least one workgroup so that a call without an element to pack still counts.
+__global__ __launch_bounds__(GB_THREADS) void k_grad_pack_guarded(const GbChunk c, float scale, int accumulate, const int* __restrict__ flag,
+                                                                  float* __restrict__ n_good)
+{
+    const int b = blockIdx.x;
+    const int ok = __builtin_amdgcn_readfirstlane(flag[0]);
+    if (n_good != nullptr && b == 0 && threadIdx.x == 0) n_good[0] = (accumulate != 0 ? n_good[0] : 0.0f) + (ok != 0 ? 1.0f : 0.0f);
+    if (b >= c.n_wg) return;
+    if (ok == 0 && accumulate != 0) return;
+    const int ei = gb_find_entry(c, b);
+    const float* g = c.e[ei].g;
+    float* dst = c.e[ei].dst;
+    const long long n = c.e[ei].n;
+    const long long lo = (long long)(b - c.e[ei].wg0) * GB_SLICE;
+    const long long hi = lo + GB_SLICE < n ? lo + GB_SLICE : n;
+    if (ok == 0 || g == nullptr) {                                             // (accumulate == 0 here: an accumulate call makes no NULL entry)
+        gb_slice<true, true, false>(g, dst, lo, hi, scale);
+    } else if (((uintptr_t)g & 15) == 0) {
+        if (accumulate != 0) gb_slice<true, false, true>(g, dst, lo, hi, scale);
+        else gb_slice<true, false, false>(g, dst, lo, hi, scale);
+    } else {
+        if (accumulate != 0) gb_slice<false, false, true>(g, dst, lo, hi, scale);
+        else gb_slice<false, false, false>(g, dst, lo, hi, scale);
+    }
+}
+
+// regtr_grad_pack's argument checks (shared by the guarded entry point; regtr_grad_pack keeps its own lines)
+int gb_check(const regtr_bucket_tensor_t* t, int n_tensors, float* bucket, long long n_bucket, float scale)
+{
+    if (n_tensors < 0 || n_bucket < 0 || (n_tensors > 0 && !t) || scale != scale || ((uintptr_t)bucket & 15)) return RG_ERR_ARG;
+    long long end = 0;
+    bool work = false;
+    for (int i = 0; i < n_tensors; i++) {
+        if (t[i].n < 0 || t[i].n >= (1ll << 40) || ((uintptr_t)t[i].g & 3)) return RG_ERR_ARG;
+        if (t[i].offset < 0 || (t[i].offset & 3) || t[i].offset < end || t[i].offset > n_bucket || t[i].n > n_bucket - t[i].offset)
+            return RG_ERR_ARG;
+        end = t[i].offset + t[i].n;
+        work = work || t[i].n > 0;
+    }
+    if (work && !bucket) return RG_ERR_ARG;
+    return RG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -144,6 +190,34 @@ int regtr_grad_pack(const regtr_bucket_tensor_t* t, int n_tensors, float* bucket
         if (flush && c.n_entries > 0) {
             k_grad_pack<<<c.n_wg, GB_THREADS, 0, (hipStream_t)stream>>>(c, scale, accumulate);
             RG_RETURN_IF_LAUNCH_FAILED();
+            c.n_entries = 0; c.n_wg = 0;
+        }
+        if (skip) continue;
+        GbEntry& e = c.e[c.n_entries++];
+        e.g = t[i].g; e.dst = bucket + t[i].offset; e.n = t[i].n; e.wg0 = c.n_wg; e.pad_ = 0;
+        c.n_wg += (int)wgs;
+    }
+    return RG_OK;
+}
+
+int regtr_grad_pack_guarded(const regtr_bucket_tensor_t* t, int n_tensors, float* bucket, long long n_bucket, float scale, int accumulate,
+                            const int* flag, float* n_good, void* stream)
+{
+    if (!flag || (((uintptr_t)flag | (uintptr_t)n_good) & 3)) return RG_ERR_ARG;
+    const int st = gb_check(t, n_tensors, bucket, n_bucket, scale);
+    if (st != RG_OK) return st;
+    GbChunk c;
+    c.n_entries = 0; c.n_wg = 0;
+    bool first = true;
+    for (int i = 0; i <= n_tensors; i++) {
+        const bool skip = i == n_tensors || t[i].n == 0 || (!t[i].g && accumulate != 0);      // (nothing to write)
+        const long long wgs = skip ? 0 : (t[i].n + GB_SLICE - 1) / GB_SLICE;
+        const bool flush = i == n_tensors || c.n_entries == GB_CHUNK || (long long)c.n_wg + wgs > 0x7fffffffll;
+        if (flush && (c.n_entries > 0 || (i == n_tensors && first && n_good))) {
+            k_grad_pack_guarded<<<c.n_wg > 0 ? c.n_wg : 1, GB_THREADS, 0, (hipStream_t)stream>>>(c, scale, accumulate, flag,
+                                                                                              first ? n_good : nullptr);
+            RG_RETURN_IF_LAUNCH_FAILED();
+            first = false;
             c.n_entries = 0; c.n_wg = 0;
         }
         if (skip) continue;

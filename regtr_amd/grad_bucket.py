@@ -8,7 +8,15 @@ payload of data-parallel training's single all-reduce (csrc/grad_bucket.hip pack
 A run with (k, W) and a run with (k W, 1) average the same micro-batches.  Bit for bit the two agree only where the additions are the
 same: accumulation computes fmaf(s, g1, fl(s g0)), the rank sum fl(s g0) + fl(s g1), which are one number where s g is exact (k W a
 power of two, no underflow) and may differ in the last bit otherwise.  The mean is over micro-batches of each micro-batch's own loss (torch
-DDP's rule), not a re-weighting by pair count.  There is no skip logic: a non-finite gradient on one rank reaches every rank."""
+DDP's rule), not a re-weighting by pair count.
+
+Without skip_nonfinite a non-finite gradient on one rank reaches every rank.  With GradBucket(..., skip_nonfinite=True) every add() first
+forms a device flag from the micro-batch's GRADIENTS alone (one more read of them: grad_sumsq and a guarded finish; a NaN loss with finite
+gradients does not count) and packs under it: a micro-batch whose gradient norm is not finite contributes nothing -- neither to the
+segments nor to the `extra` tail -- and the flag is counted into one private tail slot, n_good, which rides the same all-reduce
+unscaled, so every rank sees the same count.  attach(n_expected, optimizer) hands the optimiser grad_scale = n_expected / n_good on the
+device: exactly 1.0 when nothing was excluded (the unguarded path's bits), the mean over the good micro-batches otherwise, and
+non-finite when there is none, which makes FusedAdamW(skip_nonfinite=True) skip the step.  No host read anywhere."""
 import torch
 
 from . import ops
@@ -21,9 +29,11 @@ class GradBucket:
     segment starts on a multiple of 4 floats (its length rounded up to 4), and a tail of n_extra floats follows the last segment -- the
     stacked loss scalars ride the same collective as one more row of the same table.  Parameters without a gradient (a frozen backbone,
     kernel_points) are simply not in the layout, as FusedAdamW skips them.  The flat tensor is zeroed once, when it is allocated, and
-    its padding is never written afterwards."""
+    its padding is never written afterwards.  skip_nonfinite=True (the module docstring): one more tail float after the n_extra ones
+    holds n_good; `skipped_micro_batches` is then a float32 device scalar, the cumulative n_expected - n_good over the attach() calls
+    (over all ranks: it is formed after the all-reduce)."""
 
-    def __init__(self, params, n_extra=0):
+    def __init__(self, params, n_extra=0, skip_nonfinite=False):
         params = list(params)
         self.names = [p[0] if isinstance(p, (tuple, list)) else None for p in params]
         self.params = [p[1] if isinstance(p, (tuple, list)) else p for p in params]
@@ -35,6 +45,11 @@ class GradBucket:
         self.offsets = None           # their first elements in `flat`; one more entry: the tail's
         self.sizes = None
         self._filled = False          # the current optimiser step has had its first add()
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._flag = None             # skip_nonfinite: the scratch guard word of the per-micro-batch flag, (4,) int32
+        self._scale = None            # ... the (1,) float32 grad_scale attach() computes
+        self.skipped_micro_batches = None
+        self._n_expected = None       # ... (value, its (1,) device tensor)
 
     def _name(self, i):
         return self.names[i] if self.names[i] is not None else f'params[{i}] {tuple(self.params[i].shape)}'
@@ -54,8 +69,13 @@ class GradBucket:
             raise RuntimeError('GradBucket.add: no parameter holds a gradient (call it after backward())')
         self.index = held
         self.sizes = [self.params[i].numel() for i in held]
-        self.offsets, total = self.layout(self.sizes, self.n_extra)
-        self.flat = torch.zeros(total, dtype=torch.float32, device=self.params[held[0]].device)
+        self.offsets, total = self.layout(self.sizes, self.n_extra + (1 if self.skip_nonfinite else 0))
+        dev = self.params[held[0]].device
+        self.flat = torch.zeros(total, dtype=torch.float32, device=dev)
+        if self.skip_nonfinite:
+            self._flag = ops.new_guard(dev)
+            self._scale = torch.ones(1, dtype=torch.float32, device=dev)
+            self.skipped_micro_batches = torch.zeros((), dtype=torch.float32, device=dev)
 
     def add(self, scale, extra=None):
         """One grad_pack over the current p.grad's (and `extra`, n_extra float32 values on the device, into the tail): the first call of
@@ -78,7 +98,12 @@ class GradBucket:
             sizes = sizes + [self.n_extra]
         elif extra is not None:
             raise RuntimeError('GradBucket.add: extra given but n_extra = 0')
-        ops.grad_pack(grads, self.offsets[:len(grads)], self.flat, scale, self._filled, sizes=sizes)
+        if self.skip_nonfinite:
+            with ops._lib.on_device(self.flat.device):
+                ops.grad_finite_flag(grads[:len(held)], self._flag)           # the gradients only: not `extra`
+            ops.grad_pack(grads, self.offsets[:len(grads)], self.flat, scale, self._filled, sizes=sizes, flag=self._flag, n_good=self.n_good())
+        else:
+            ops.grad_pack(grads, self.offsets[:len(grads)], self.flat, scale, self._filled, sizes=sizes)
         self._filled = True
 
     def all_reduce(self):
@@ -89,13 +114,32 @@ class GradBucket:
         """The parameters' views of the bucket, in layout order, each of its parameter's shape."""
         return [self.flat[o:o + n].view(self.params[i].shape) for i, o, n in zip(self.index, self.offsets, self.sizes)]
 
-    def attach(self):
+    def attach(self, n_expected=None, optimizer=None):
         """p.grad = the parameter's view of the bucket, and the step is over: the next add() assigns.  FusedAdamW.step() then runs
         unchanged on the averaged gradient (its last_grad_norm is the averaged gradient's norm; clipping acts after averaging, as
-        clip_grad_norm_ after DDP).  The views stay valid until that next add()."""
+        clip_grad_norm_ after DDP).  The views stay valid until that next add().
+        skip_nonfinite: n_expected = the micro-batches of the step over all ranks (k W, what the scales of add() divided by); -> the
+        (1,) float32 device tensor grad_scale = n_expected / n_good, also set as optimizer.grad_scale when an optimiser is given."""
         for i, v in zip(self.index, self.views()):
             self.params[i].grad = v
         self._filled = False
+        if not self.skip_nonfinite:
+            return None
+        if n_expected is None:
+            raise RuntimeError('GradBucket.attach: a skip_nonfinite bucket needs n_expected (the micro-batches of the step over all ranks)')
+        n_good = self.n_good()
+        if self._n_expected is None or float(n_expected) != self._n_expected[0]:
+            self._n_expected = (float(n_expected), torch.full((1,), float(n_expected), dtype=torch.float32, device=self.flat.device))
+        torch.div(self._n_expected[1], n_good, out=self._scale)               # n_good == 0: inf, and the optimiser skips the step
+        self.skipped_micro_batches += self._n_expected[1][0] - n_good[0]
+        if optimizer is not None:
+            optimizer.grad_scale = self._scale
+        return self._scale
+
+    def n_good(self):
+        """skip_nonfinite: the (1,) view of the tail slot that counts the micro-batches the bucket holds (after all_reduce: of all ranks)."""
+        o = self.offsets[-1] + self.n_extra
+        return self.flat[o:o + 1]
 
     def reset(self):
         """Abandons the current optimiser step: what was added so far is dropped, the next add() assigns."""

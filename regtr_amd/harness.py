@@ -827,6 +827,15 @@ class CheckpointSaver:
         return int(state.get('step', 0))
 
     @staticmethod
+    def counters(path):
+        """The 'nonfinite_guard' entry of a checkpoint written by train_loop(skip_nonfinite=True) -- {'skipped_steps',
+        'skipped_micro_batches'} -- or None."""
+        if os.path.isdir(path):
+            with open(os.path.join(path, 'checkpoints.txt')) as f:
+                path = os.path.join(path, f'model-{int(f.readline().split(":")[1])}.pth')
+        return torch.load(path, map_location='cpu', weights_only=False).get('nonfinite_guard', None)
+
+    @staticmethod
     def batching(path):
         """(accumulate, world) a checkpoint (a file, or a directory as load() takes it) was written with; (1, 1) for a checkpoint of the
         plain loop, which carries neither key."""
@@ -859,7 +868,7 @@ def _validate(model, val_batches):
 
 
 def train_loop(model, batches, steps, first_step=0, train_backbone=True, validate_every=0, val_batches=None, saver=None, logger=None,
-               log_every=50, accumulate=1):
+               log_every=50, accumulate=1, skip_nonfinite=False, counters=None):
     """The reference's training loop (trainer.py:95-161) without tqdm and tensorboard: for each of `steps` batches of the iterable
     `batches` -- optimizer.zero_grad(), RegTR.training_step, backward, optimizer.step() (the gradient clip is inside it),
     scheduler.step() -- with model.optimizer / model.scheduler from RegTR.configure_optimizers (called here if the model has none yet).
@@ -875,12 +884,36 @@ def train_loop(model, batches, steps, first_step=0, train_backbone=True, validat
     and the global step count optimiser steps, and the logged and averaged losses are the bucket tail's: the mean over the step's micro-
     batches and ranks.  Rank 0's parameters are broadcast once at the start; validation is sharded over the ranks (_validate) and rank 0
     alone logs and saves -- checkpoints then carry 'accumulate' and 'world'.  With accumulate == 1 and no process group the loop is
-    the plain one: no bucket, the same launches, the same four checkpoint keys."""
+    the plain one: no bucket, the same launches, the same four checkpoint keys.
+    skip_nonfinite=True (off: everything above, launch for launch): the optimiser must be a FusedAdamW(skip_nonfinite=True) (the config
+    key `skip_nonfinite` makes configure_optimizers build one) and the bucket path uses GradBucket(skip_nonfinite=True): a step whose
+    gradient is not finite is left out on the device, a micro-batch whose gradient is not finite is left out of the bucket, and the host
+    is never asked.  The scheduler, the global step and the batch sequence advance on a skipped step (GradScaler's semantics).  Loss
+    statistics then are finite-only: per key a sum and a count on the device -- on the bucket path the tail carries
+    [where(isfinite(l), l, 0) ..., isfinite(l) ...] and the means are ratios taken after the all-reduce; on the plain path a skipped
+    step's losses are left out as an excluded micro-batch's are -- so loss_avg[k] is the mean over the finite values and NaN only when
+    there are none.  The result gains 'skipped_steps' and 'skipped_micro_batches' (device scalars, cumulative from `counters`, a
+    {'skipped_steps', 'skipped_micro_batches'} dict of a resumed run's checkpoint); the log line prints both from its one host read;
+    checkpoints carry them as 'nonfinite_guard'."""
     if getattr(model, 'optimizer', None) is None:
         model.configure_optimizers(train_backbone=train_backbone)
     opt, sched = model.optimizer, model.scheduler
     step = int(first_step)
     sums, smooth, n_done, scores, last_val = {}, None, 0, [], None
+    guarded = bool(skip_nonfinite)
+    if guarded and not getattr(opt, 'skip_nonfinite', False):
+        raise RuntimeError('train_loop(skip_nonfinite=True) needs an optimiser built with skip_nonfinite=True (FusedAdamW; the config key '
+                           '`skip_nonfinite` makes RegTR.configure_optimizers build one)')
+    fin_sum = fin_cnt = None              # guarded: per key, the finite-only sum and count (device vectors in `keys` order)
+    base = {k_: float((counters or {}).get(k_, 0)) for k_ in ('skipped_steps', 'skipped_micro_batches')}
+    opt_skipped0 = None                   # the optimiser's cumulative count when this loop took its first step
+
+    def skipped():
+        """(skipped_steps, skipped_micro_batches) as float32 device scalars, cumulative over the run and its resumed ancestors."""
+        s_ = opt.skipped_steps.to(torch.float32) - opt_skipped0 + base['skipped_steps']
+        if bucket is not None:
+            return s_, bucket.skipped_micro_batches + base['skipped_micro_batches']
+        return s_, s_ - base['skipped_steps'] + base['skipped_micro_batches']
     it = iter(batches)
     from .distributed import broadcast_parameters, rank_world
     n_acc = int(accumulate)
@@ -909,8 +942,12 @@ def train_loop(model, batches, steps, first_step=0, train_backbone=True, validat
                 if bucket is None:
                     from .grad_bucket import GradBucket
                     keys = list(losses)
-                    bucket = GradBucket(list(model.named_parameters()), n_extra=len(keys))
-                bucket.add(1.0 / (n_acc * world), torch.stack([losses[k_].detach() for k_ in keys]))
+                    bucket = GradBucket(list(model.named_parameters()), n_extra=len(keys) * (2 if guarded else 1), skip_nonfinite=guarded)
+                stacked = torch.stack([losses[k_].detach() for k_ in keys])
+                if guarded:
+                    fin = torch.isfinite(stacked)
+                    stacked = torch.cat([torch.where(fin, stacked, torch.zeros_like(stacked)), fin.to(stacked.dtype)])
+                bucket.add(1.0 / (n_acc * world), stacked)
             opt.zero_grad()
             if batch is None:
                 if bucket is not None:
@@ -918,10 +955,20 @@ def train_loop(model, batches, steps, first_step=0, train_backbone=True, validat
                 break
             step += 1
             bucket.all_reduce()
-            bucket.attach()
+            if guarded:
+                bucket.attach(n_acc * world, opt)
+                if opt_skipped0 is None:
+                    opt_skipped0 = opt.skipped_steps.to(torch.float32).clone() if opt.skipped_steps is not None else 0.0
+            else:
+                bucket.attach()
             opt.step()
             sched.step()
-            losses = dict(zip(keys, bucket.extra().clone().unbind(0)))
+            if guarded:
+                tail = bucket.extra().clone()
+                step_sum, step_cnt = tail[:len(keys)], tail[len(keys):]       # (both carry the 1 / (k W) of add(): the ratio does not)
+                losses = dict(zip(keys, (step_sum / step_cnt).unbind(0)))     # (no finite value: 0 / 0 = NaN)
+            else:
+                losses = dict(zip(keys, bucket.extra().clone().unbind(0)))
         else:
             try:
                 batch = next(it)
@@ -931,26 +978,54 @@ def train_loop(model, batches, steps, first_step=0, train_backbone=True, validat
             opt.zero_grad()
             _, losses = model.training_step(batch, step, train_backbone=train_backbone)
             losses['total'].backward()
+            if guarded and opt_skipped0 is None:
+                opt_skipped0 = opt.skipped_steps.to(torch.float32).clone() if opt.skipped_steps is not None else 0.0
             opt.step()
             sched.step()
+            if guarded:
+                if keys is None:
+                    keys = list(losses)
+                stacked = torch.stack([losses[k_].detach() for k_ in keys])
+                fin = torch.isfinite(stacked) & (opt.last_step_applied != 0)  # (a skipped step's losses are left out, as the bucket does)
+                step_sum, step_cnt = torch.where(fin, stacked, torch.zeros_like(stacked)), fin.to(stacked.dtype)
         n_done += 1
         with torch.no_grad():
-            for k, v in losses.items():
+            if guarded:
+                fin_sum = step_sum.clone() if fin_sum is None else fin_sum + step_sum
+                fin_cnt = step_cnt.clone() if fin_cnt is None else fin_cnt + step_cnt
+            for k, v in ({} if guarded else losses).items():
                 v = v.detach()
                 sums[k] = v.clone() if k not in sums else sums[k] + v
             total = losses['total'].detach()
             smooth = total.clone() if smooth is None else torch.where(torch.isfinite(total), 0.99 * smooth + 0.01 * total, smooth)
         if logger is not None and (n_done == 1 or step % int(log_every) == 0):
-            logger.info(f'step {step}: smoothed total loss {smooth.item():.4g}, lr {opt.param_groups[0]["lr"]:.3g}')      # the one host read
+            if guarded:
+                sm_, ss_, sb_ = torch.stack([smooth.to(torch.float32), *skipped()]).tolist()      # the one host read
+                logger.info(f'step {step}: smoothed total loss {sm_:.4g}, lr {opt.param_groups[0]["lr"]:.3g}, skipped steps {int(ss_)}, '
+                            f'skipped micro-batches {int(sb_)}')
+            else:
+                logger.info(f'step {step}: smoothed total loss {smooth.item():.4g}, lr {opt.param_groups[0]["lr"]:.3g}')      # the one host read
         if validate_every > 0 and val_batches is not None and step % int(validate_every) == 0:
             score, last_val = _validate(model, val_batches)
             scores.append((step, score))
             if logger is not None:
                 logger.info(f'validation at step {step}: score {score:.4f}, total loss {float(last_val["losses"]["total"]):.4g}')
             if saver is not None:
+                if guarded:
+                    extra_ckpt['nonfinite_guard'] = dict(zip(('skipped_steps', 'skipped_micro_batches'), (int(x) for x in skipped())))
                 path = saver.save(model, step, score, optimizer=opt, scheduler=sched, **extra_ckpt)
                 if logger is not None:
                     logger.info(f'Saved checkpoint: {path} (best step {saver.best_step})')
+    if guarded:
+        out = {'step': step, 'loss_smooth': smooth, 'scores': scores, 'validation': last_val,
+               'loss_avg': dict(zip(keys, (fin_sum / fin_cnt).unbind(0))) if fin_sum is not None else {}}
+        if opt_skipped0 is None:          # (no step was taken)
+            dev = next(model.parameters()).device
+            out['skipped_steps'] = torch.tensor(base['skipped_steps'], device=dev)
+            out['skipped_micro_batches'] = torch.tensor(base['skipped_micro_batches'], device=dev)
+        else:
+            out['skipped_steps'], out['skipped_micro_batches'] = skipped()
+        return out
     return {'step': step, 'loss_smooth': smooth, 'loss_avg': {k: v / max(n_done, 1) for k, v in sums.items()}, 'scores': scores,
             'validation': last_val}
 

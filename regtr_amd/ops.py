@@ -1470,6 +1470,136 @@ def clip_adam_step(params, grads, exp_avgs, exp_avg_sqs, scalars, max_norm, deco
     return norm_coef
 
 
+# ------------------------------------------------------------------------------------------------ the guarded step (skip_nonfinite)
+_OPTIM_GUARDED_DTYPE = None
+
+
+def optim_guarded_chunk():
+    """Tensors per launch of adam_step_guarded -- tests straddle it."""
+    return int(_lib.lib().regtr_optim_guarded_chunk_tensors())
+
+
+def new_guard(device):
+    """A zeroed guard word: (4,) int32 on the device, {ok, applied_steps, skipped_steps, reserved} (include/regtr_hip.h)."""
+    return torch.zeros(4, dtype=torch.int32, device=device)
+
+
+def _scalar_arg(t, name, dtype, numel=1):
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype is not dtype or t.numel() != numel or not t.is_contiguous():
+        raise RuntimeError(f'{name} must be a contiguous GPU tensor of {numel} {dtype} value(s), got {getattr(t, "shape", type(t))} '
+                           f'{getattr(t, "dtype", "")} on {getattr(t, "device", "?")}')
+    return t
+
+
+def grad_norm_finish_guarded(partials, max_norm, guard, grad_scale=None):
+    """grad_norm_finish under the guard (regtr_grad_norm_finish_guarded): -> (2,) float32 [total_norm * grad_scale, clip_coef]; guard (4,)
+    int32 device tensor: guard[0] = ok (the scaled norm and the scale are finite), guard[1] += ok, guard[2] += 1 - ok.  grad_scale: a
+    1-element float32 device tensor or None (= 1; then, and with exactly 1.0, the output has grad_norm_finish's bits).  No host read."""
+    _scalar_arg(guard, 'grad_norm_finish_guarded: guard', torch.int32, 4)
+    _scalar_arg(grad_scale, 'grad_norm_finish_guarded: grad_scale', torch.float32)
+    out = torch.empty(2, dtype=torch.float32, device=partials.device)
+    n = partials.numel()
+    check(_lib.lib().regtr_grad_norm_finish_guarded(dptr(partials) if n else None, n, float(max_norm), ptr(grad_scale), ptr(out),
+                                                    guard.data_ptr(), stream()), 'regtr_grad_norm_finish_guarded')
+    return out
+
+
+def _guarded_table(tab, hypers, step_index):
+    global _OPTIM_GUARDED_DTYPE
+    import numpy as np
+    if _OPTIM_GUARDED_DTYPE is None:
+        _OPTIM_GUARDED_DTYPE = np.dtype([('p', np.uint64), ('g', np.uint64), ('m', np.uint64), ('v', np.uint64), ('n', np.int64),
+                                         ('hyper', np.float64, (5,)), ('step_index', np.int32)], align=True)
+        assert _OPTIM_GUARDED_DTYPE.itemsize == 88
+    n = len(tab)
+    gtab = np.zeros(n, dtype=_OPTIM_GUARDED_DTYPE)
+    for k in ('p', 'g', 'm', 'v', 'n'):
+        gtab[k] = tab[k]
+    if n:
+        gtab['hyper'] = hypers
+        gtab['step_index'] = step_index
+    return gtab
+
+
+def _guarded_tables(params, grads, exp_avgs, exp_avg_sqs, hypers, step_index, what):
+    import numpy as np
+    n = len(grads)
+    if len(hypers) != n or len(step_index) != n:
+        raise RuntimeError(f'{what}: hypers and step_index must have one entry per tensor')
+    hyp = np.asarray(hypers, dtype=np.float64).reshape(n, 5)
+    tab, keep = _optim_table(grads, params, exp_avgs, exp_avg_sqs, np.concatenate([hyp, np.ones((n, 2))], axis=1), what=what)
+    return tab, _guarded_table(tab, hyp, step_index), keep
+
+
+def _adam_step_guarded(gtab, n, steps, step_scalars, guard, clip_coef, grad_scale, decoupled):
+    check(_lib.lib().regtr_adam_step_guarded(gtab.ctypes.data if n else None, n, ptr(steps), ptr(step_scalars), steps.numel(), ptr(clip_coef),
+                                             ptr(grad_scale), guard.data_ptr(), 1 if decoupled else 0, stream()), 'regtr_adam_step_guarded')
+
+
+def _guarded_args(steps, guard, grad_scale, what, step_scalars=None):
+    """-> the workspace for the per-tensor step scalars, (2 len(steps),) float32: the caller's, or a fresh one."""
+    if not isinstance(steps, torch.Tensor) or not steps.is_cuda or steps.dtype is not torch.float32 or not steps.is_contiguous():
+        raise RuntimeError(f'{what}: steps must be a contiguous float32 GPU vector; there is no CPU fallback')
+    if step_scalars is None:
+        step_scalars = torch.empty(2 * steps.numel(), dtype=torch.float32, device=steps.device)
+    elif (not isinstance(step_scalars, torch.Tensor) or step_scalars.device != steps.device or step_scalars.dtype is not torch.float32
+          or not step_scalars.is_contiguous() or step_scalars.numel() != 2 * steps.numel()):
+        raise RuntimeError(f'{what}: step_scalars must be a contiguous float32 vector of 2 x len(steps) on the steps\' device')
+    _scalar_arg(guard, f'{what}: guard', torch.int32, 4)
+    _scalar_arg(grad_scale, f'{what}: grad_scale', torch.float32)
+    return step_scalars
+
+
+def adam_step_guarded(params, grads, exp_avgs, exp_avg_sqs, hypers, step_index, steps, guard, clip_coef=None, grad_scale=None,
+                      decoupled=True, step_scalars=None):
+    """adam_step under the guard (regtr_adam_step_guarded).  guard[0] == 0: nothing is written.  Else steps[step_index[i]] += 1 for every
+    tensor, then adam_step's update with g' = (g grad_scale) clip_coef and the bias corrections formed ON THE DEVICE from the advanced
+    count.  hypers: per tensor (lr, weight_decay, beta1, beta2, eps), host float64; step_index: distinct positions in `steps`, a float32
+    device vector; guard: (4,) int32; clip_coef, grad_scale: 1-element float32 device tensors or None (= 1); step_scalars: the (2
+    len(steps),) float32 workspace of the per-tensor scalars (None: allocated here).  The tensor checks and the version-counter note of
+    adam_step apply."""
+    step_scalars = _guarded_args(steps, guard, grad_scale, 'adam_step_guarded', step_scalars)
+    if clip_coef is not None and clip_coef.numel() != 1:
+        raise RuntimeError(f'adam_step_guarded: clip_coef must hold one float32, got {tuple(clip_coef.shape)}')
+    _, gtab, keep = _guarded_tables(params, grads, exp_avgs, exp_avg_sqs, hypers, step_index, 'adam_step_guarded')
+    _adam_step_guarded(gtab, len(keep), steps, step_scalars, guard, clip_coef, grad_scale, decoupled)
+
+
+def clip_adam_step_guarded(params, grads, exp_avgs, exp_avg_sqs, hypers, step_index, steps, guard, max_norm, grad_scale=None,
+                           decoupled=True, step_scalars=None):
+    """grad_sumsq, grad_norm_finish_guarded(max_norm, grad_scale) and adam_step_guarded over ONE table of the tensors (checked once) ->
+    the (2,) float32 device tensor [total_norm * grad_scale before clipping, clip_coef].  What FusedAdamW(skip_nonfinite=True).step
+    runs."""
+    step_scalars = _guarded_args(steps, guard, grad_scale, 'clip_adam_step_guarded', step_scalars)
+    tab, gtab, keep = _guarded_tables(params, grads, exp_avgs, exp_avg_sqs, hypers, step_index, 'clip_adam_step_guarded')
+    norm_coef = grad_norm_finish_guarded(_sumsq(tab, keep), max_norm, guard, grad_scale)
+    _adam_step_guarded(gtab, len(keep), steps, step_scalars, guard, norm_coef[1:], grad_scale, decoupled)
+    return norm_coef
+
+
+def adam_bias_scalars(lr, beta1, beta2, steps):
+    """(n, 2) float32: for every count of the float32 device vector `steps` the two scalars the guarded step forms from it on the device,
+    [(float)(lr / (1 - beta1^t)), (float)sqrt(1 - beta2^t)] (regtr_adam_bias_scalars: the kernel's own device function)."""
+    if not isinstance(steps, torch.Tensor) or not steps.is_cuda or steps.dtype is not torch.float32 or not steps.is_contiguous():
+        raise RuntimeError('adam_bias_scalars: steps must be a contiguous float32 GPU vector; there is no CPU fallback')
+    out = torch.empty(steps.numel(), 2, dtype=torch.float32, device=steps.device)
+    n = steps.numel()
+    with _lib.on_device(steps.device):
+        check(_lib.lib().regtr_adam_bias_scalars(float(lr), float(beta1), float(beta2), ptr(steps) if n else None, n, ptr(out) if n else None,
+                                                 stream()), 'regtr_adam_bias_scalars')
+    return out
+
+
+def grad_finite_flag(grads, guard):
+    """The per-micro-batch flag of the guarded bucket: one grad_sumsq pass over `grads` and a guarded finish (no clip, no scale) into the
+    scratch guard word `guard` -- guard[0] = 1 exactly when the float32 norm of the gradients is finite; guard[1] / guard[2] count the
+    finite / non-finite calls.  No host read."""
+    _scalar_arg(guard, 'grad_finite_flag: guard', torch.int32, 4)
+    return grad_norm_finish_guarded(_sumsq(*_optim_table(grads, what='grad_finite_flag')), 0.0, guard)
+
+
 # ------------------------------------------------------------------------------------------------ gradient bucket (csrc/grad_bucket.hip)
 _BUCKET_DTYPE = None
 
@@ -1479,13 +1609,16 @@ def grad_pack_slice():
     return int(_lib.lib().regtr_grad_pack_slice())
 
 
-def grad_pack(grads, offsets, bucket, scale, accumulate, sizes=None):
+def grad_pack(grads, offsets, bucket, scale, accumulate, sizes=None, flag=None, n_good=None):
     """One launch per 48 tensors (regtr_grad_pack): bucket[offsets[t] + i] = scale grads[t][i], or with accumulate
     fmaf(scale, grads[t][i], bucket[offsets[t] + i]).  grads: float32 GPU tensors or None (None: zeros under assign, untouched under
     accumulate; its length then comes from sizes[t]); offsets: ascending multiples of 4, the segments inside the bucket and disjoint;
     bucket: a contiguous float32 GPU tensor.  Checked once, on the current stream, no host wait.  Elements of the bucket outside every
     segment are not written.  Refused with a Python exception: CPU tensors, tensors that are not float32 or sit on another device; what
-    the library refuses (include/regtr_hip.h).  A non-contiguous gradient is made contiguous."""
+    the library refuses (include/regtr_hip.h).  A non-contiguous gradient is made contiguous.
+    flag (a guard word, (4,) int32 on the device; None: the unguarded launch above): regtr_grad_pack_guarded -- flag[0] != 0 the same
+    arithmetic, flag[0] == 0 zeros under assign and nothing under accumulate; n_good (a 1-element float32 device tensor outside every
+    segment, or None) then receives (accumulate ? n_good : 0) + (flag[0] != 0), unscaled."""
     global _BUCKET_DTYPE
     import numpy as np
     if _BUCKET_DTYPE is None:
@@ -1510,6 +1643,15 @@ def grad_pack(grads, offsets, bucket, scale, accumulate, sizes=None):
             tab['offset'] = offsets
             if sizes is not None and tab['n'].tolist() != [int(s) for s in sizes]:
                 raise RuntimeError('grad_pack: a gradient\'s element count differs from its entry in sizes')
+        if flag is not None:
+            _scalar_arg(flag, 'grad_pack: flag', torch.int32, 4)
+            _scalar_arg(n_good, 'grad_pack: n_good', torch.float32)
+            check(_lib.lib().regtr_grad_pack_guarded(tab.ctypes.data if n else None, n, ptr(bucket), bucket.numel(), float(scale),
+                                                     1 if accumulate else 0, flag.data_ptr(), ptr(n_good), stream()),
+                  'regtr_grad_pack_guarded')
+            return
+        if n_good is not None:
+            raise RuntimeError('grad_pack: n_good needs a flag')
         check(_lib.lib().regtr_grad_pack(tab.ctypes.data if n else None, n, ptr(bucket), bucket.numel(), float(scale), 1 if accumulate else 0,
                                          stream()), 'regtr_grad_pack')
 

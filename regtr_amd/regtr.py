@@ -816,7 +816,8 @@ class RegTR(nn.Module):
         optimiser's state_dict are the reference's; the frozen kernel_points (and, with train_backbone=False, the backbone's weights)
         sit in the list and never get a gradient, hence no state.  The reference's clip_grad_norm_(model.parameters(), cfg.grad_clip)
         lives in the optimiser (max_grad_norm), so a step is: optimizer.zero_grad(), training_step(batch,
-        train_backbone=train_backbone), losses['total'].backward(), optimizer.step(), scheduler.step()."""
+        train_backbone=train_backbone), losses['total'].backward(), optimizer.step(), scheduler.step().  cfg.skip_nonfinite (absent:
+        off): FusedAdamW(skip_nonfinite=True), which leaves a step with a non-finite gradient out on the device."""
         from .optim import FusedAdamW
         cfg = self.cfg
         scheduler_type = cfg.get('scheduler', None)
@@ -828,7 +829,8 @@ class RegTR(nn.Module):
             raise NotImplementedError(f'optimizer {cfg.optimizer!r}: choose AdamW or Adam')
         self.trainable_parameters(backbone=train_backbone)          # turns requires_grad on for the two InfoNCE W
         self.optimizer = FusedAdamW(list(self.parameters()), lr=cfg.base_lr, weight_decay=cfg.weight_decay,
-                                    max_grad_norm=cfg.get('grad_clip', 0.0), decoupled=cfg.optimizer == 'AdamW')
+                                    max_grad_norm=cfg.get('grad_clip', 0.0), decoupled=cfg.optimizer == 'AdamW',
+                                    **({'skip_nonfinite': True} if cfg.get('skip_nonfinite', False) else {}))
         if scheduler_type == 'step':
             self.scheduler = torch.optim.lr_scheduler.StepLR(self.optimizer, cfg.scheduler_param[0], cfg.scheduler_param[1])
         else:

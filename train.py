@@ -2,6 +2,7 @@
 
     python train.py --config CFG [--logdir DIR] [--dev] [--name NAME] [--num_workers N] [--resume CKPT_OR_DIR]
                     [--batch B] [--steps K] [--validate_every V] [--seed S] [--freeze_backbone] [--accumulate K] [--gpus N]
+                    [--skip_nonfinite]
                     [--synthetic N | --data_root ROOT --info TRAIN_INFO.pkl]
 
 Every step: device-side training batch (regtr_amd.augment), RegTR.training_step, backward, the fused clip + AdamW step
@@ -19,6 +20,10 @@ ranks, one per GPU, started as a child `python -m torch.distributed.run` job wit
 GPU; every optimiser step then averages K x N micro-batches with ONE all-reduce, and a run with (K, N) averages the same micro-batches as
 a run with (K x N, 1).  --steps and the checkpoints' step count optimiser steps.  A checkpoint written with K x N > 1 carries both
 numbers, and --resume refuses another product.  Rank 0 alone logs and saves.
+--skip_nonfinite (or `skip_nonfinite: true` in the config): an optimiser step whose gradient is not finite is left out on the device, and
+with --accumulate / --gpus a micro-batch whose gradient is not finite is left out of the average on every rank alike
+(FusedAdamW / GradBucket / train_loop with skip_nonfinite=True); the scheduler and the batch sequence go on.  The log line then shows both
+counts, checkpoints carry them ('nonfinite_guard') and --resume restores them.
 No tensorboard summaries.  Validation batches go through the same augmentation chain as training ones, at a fixed seed."""
 import argparse
 import logging
@@ -53,6 +58,7 @@ parser.add_argument('--seed', type=int, default=0, help='seed of the batch order
 parser.add_argument('--freeze_backbone', action='store_true', help='train only what sits above the KPConv backbone')
 parser.add_argument('--log_every', type=int, default=50)
 parser.add_argument('--accumulate', type=int, default=1, help='micro-batches whose gradients are averaged into one optimiser step')
+parser.add_argument('--skip_nonfinite', action='store_true', help='leave non-finite optimiser steps and micro-batches out, on the device')
 parser.add_argument('--gpus', type=int, default=0, help='N ranks, one per GPU (1 .. 8), as a child torch.distributed.run job; 0: this process alone')
 
 
@@ -175,9 +181,12 @@ def main():
 
     torch.manual_seed(opt.seed)          # the initial weights (and numpy: the kernel points' random rotation) follow --seed, as setup_seed
     np.random.seed(opt.seed % (1 << 32))
+    if opt.skip_nonfinite:
+        cfg['skip_nonfinite'] = True
+    guarded = bool(cfg.get('skip_nonfinite', False))
     model = RegTR(cfg).to(device)
     model.configure_optimizers(train_backbone=not opt.freeze_backbone)
-    first_step = 0
+    first_step, counters = 0, None
     k, group = opt.accumulate, opt.accumulate * world
     if opt.resume:
         ck, cw = harness.CheckpointSaver.batching(opt.resume)
@@ -186,6 +195,7 @@ def main():
                          f'{k} x {world} = {group}; an optimiser step must average the same number of micro-batches')
             sys.exit(-5)
         first_step = harness.CheckpointSaver.load(opt.resume, model, map_location=device, optimizer=model.optimizer, scheduler=model.scheduler)
+        counters = harness.CheckpointSaver.counters(opt.resume) if guarded else None
         logger.info(f'Resumed from {opt.resume} at step {first_step}')
 
     per_epoch = -(-len(source) // batch)
@@ -203,7 +213,7 @@ def main():
     t0 = time.perf_counter()
     out = harness.train_loop(model, batches, opt.steps, first_step=first_step, train_backbone=not opt.freeze_backbone,
                              validate_every=opt.validate_every, val_batches=val_batches, saver=saver, logger=logger, log_every=opt.log_every,
-                             accumulate=k)
+                             accumulate=k, **(dict(skip_nonfinite=True, counters=counters) if guarded else {}))
     torch.cuda.synchronize(device)
     dt = time.perf_counter() - t0
     avg = ', '.join(f'{k} {float(v):.4g}' for k, v in out['loss_avg'].items())
