@@ -7,6 +7,8 @@ Cases
   3dmatch_kitchen : the full red-kitchen pair (18 977 + 19 084 pts), conf/3dmatch.yaml
   modelnet_postnorm : the ModelNet pair with pre_norm: False (forward_post), sa_val_has_pos_emb: False
   modelnet_attn_head : the ModelNet pair with direct_regress_coor: False (attention CorrespondenceDecoder)
+  modelnet_prenorm_plainval, modelnet_postnorm_peval, modelnet_nope, modelnet_attn_head_nope, modelnet_posemb_scale : the ModelNet pair
+                    under the config keys no shipped config sets (VARIANT_CASES below); GOLDEN_ONLY=variants makes these alone
   3dmatch_crop_b2 : TWO ragged red-kitchen crop pairs in ONE forward (B = 2): the reference's padded (N_max, B, D) tokens +
                     key_padding_mask path (regtr.py:147-172, transformers.py:197-226) against the packed-token path here
   3dmatch_hotel   : demo.py example 1, sun3d-hotel_umd-maryland_hotel3 cloud_bin_8 / 15 (demo.py:31-34)
@@ -32,6 +34,19 @@ from regtr_amd.kernel_points import K015_CENTER         # noqa: E402
 
 GOLD = os.path.join(ROOT, 'tests', 'golden')
 DATA = os.path.join(ref_loader.REF_ROOT, 'data')
+
+
+# config variants no shipped config sets: values without the pos-emb in pre-norm layers (the two-GEMM in-projection), post-norm layers
+# whose self-attention values carry it and whose cross-attention values do not, no pos-emb in the encoder at all, the attention head
+# without it, and a pos-emb scale other than 1 (PositionEmbeddingCoordsSine takes cfg.pos_emb_scaling as its `scale`, regtr.py:41-43,
+# and multiplies the coordinates by scale * 2 pi, position_embedding.py:27: 2.0 is used as given)
+VARIANT_CASES = {
+    'modelnet_prenorm_plainval': {'sa_val_has_pos_emb': False, 'ca_val_has_pos_emb': False},
+    'modelnet_postnorm_peval': {'pre_norm': False, 'sa_val_has_pos_emb': True, 'ca_val_has_pos_emb': False},
+    'modelnet_nope': {'transformer_encoder_has_pos_emb': False},
+    'modelnet_attn_head_nope': {'direct_regress_coor': False, 'corr_decoder_has_pos_emb': False},
+    'modelnet_posemb_scale': {'pos_emb_scaling': 2.0},
+}
 
 
 def read_ply_xyz(path):
@@ -143,6 +158,11 @@ def main():
         return p[np.linalg.norm(p - c, axis=1) < r]
     c0, c5 = crop(k0, 0.9), crop(k5, 0.9)
 
+    if os.environ.get('GOLDEN_ONLY') in (None, 'variants'):
+        for name, overrides in VARIANT_CASES.items():
+            run_case(name, 'modelnet', m0, m1, overrides=overrides)
+        if os.environ.get('GOLDEN_ONLY') == 'variants':
+            return
     native_case('modelnet', np.concatenate([m0, m1]), np.array([len(m0), len(m1)], np.int32), 0.06, 0.0825)
     n0, n5 = crop(k0, 0.5), crop(k5, 0.5)
     native_case('3dmatch_crop', np.concatenate([n0, n5]), np.array([len(n0), len(n5)], np.int32), 0.05, 0.0625)

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from oracle import native, regtr_ref
+from oracle.make_golden import VARIANT_CASES
 from tests.util import canon_rows, gold, load_cfg, seeded_sd, synth_cloud
 
 
@@ -70,10 +71,12 @@ POSTNORM = {'pre_norm': False, 'sa_val_has_pos_emb': False, 'ca_val_has_pos_emb'
 @pytest.mark.parametrize('case,cfgn,overrides', [('modelnet_demo', 'modelnet', {}), ('3dmatch_crop', '3dmatch', {}),
                                                  ('modelnet_630', 'modelnet', {}), ('3dmatch_home_at', '3dmatch', {}),
                                                  ('modelnet_postnorm', 'modelnet', POSTNORM),
-                                                 ('modelnet_attn_head', 'modelnet', {'direct_regress_coor': False})])
+                                                 ('modelnet_attn_head', 'modelnet', {'direct_regress_coor': False})]
+                         + [(case, 'modelnet', overrides) for case, overrides in VARIANT_CASES.items()])
 def test_float_restatement_vs_reference_golden(case, cfgn, overrides):
     """oracle/regtr_ref.py driven in the REFERENCE's row order reproduces the reference module's outputs
-    (pre-norm layers of both shipped configs, the post-norm forward_post variant, the attention CorrespondenceDecoder)."""
+    (pre-norm layers of both shipped configs, the post-norm forward_post variant, the attention CorrespondenceDecoder, and the config
+    keys no shipped config sets: oracle/make_golden.py VARIANT_CASES)."""
     if not native.ref_available():
         pytest.skip('needs oracle/_ref or the recorded reference outputs for the reference row order')
     g = gold(case)
