@@ -214,18 +214,6 @@ __device__ __forceinline__ float sigmoid_f(float x) { return __fdiv_rn(1.f, 1.f 
 
 constexpr int CR_THREADS = 256;
 
-__device__ __forceinline__ double block_sum_cr(double v, double* sh)
-{
-    v = rg_wave_sum(v);
-    __syncthreads();
-    if (rg_lane() == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-#pragma unroll
-    for (int w = 0; w < CR_THREADS / RG_WAVE; w++) t += sh[w];
-    return t;
-}
-
 // pair_out[b] = (sum of selected row_i, number of selected rows, sum of selected col_j, number of selected columns)
 __global__ __launch_bounds__(CR_THREADS) void k_circle_reduce(CirArgs g, int max_anc, int max_pos, float* __restrict__ out)
 {
@@ -248,8 +236,8 @@ __global__ __launch_bounds__(CR_THREADS) void k_circle_reduce(CirArgs g, int max
                 cnt += 1.0;
             }
         }
-        sum = block_sum_cr(sum, sh);
-        cnt = block_sum_cr(cnt, sh);
+        sum = rg_block_sum<CR_THREADS>(sum, sh);
+        cnt = rg_block_sum<CR_THREADS>(cnt, sh);
         if (threadIdx.x == 0) { out[4 * b + 2 * side] = (float)sum; out[4 * b + 2 * side + 1] = (float)cnt; }
     }
 }

@@ -139,6 +139,22 @@ __device__ __forceinline__ float rg_wave_max(float v)
     return v;
 }
 
+// Sum over the THREADS values of the calling workgroup in float64, in a fixed order (every thread calls it; every thread gets the sum):
+// the xor tree over each wave, then the waves in order.  sh: THREADS / RG_WAVE doubles of LDS.  The leading barrier lets consecutive
+// calls share them; a kernel that calls this once and touches sh nowhere else passes REUSE = false and does without it.
+template <int THREADS, bool REUSE = true>
+__device__ __forceinline__ double rg_block_sum(double v, double* sh)
+{
+    v = rg_wave_sum(v);
+    if (REUSE) __syncthreads();
+    if (rg_lane() == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = 0.0;
+#pragma unroll
+    for (int w = 0; w < THREADS / RG_WAVE; w++) t += sh[w];
+    return t;
+}
+
 // Exclusive scan over the THREADS values of the calling workgroup (every thread calls it; any integer type); *total = their sum.
 // sh: THREADS / RG_WAVE values of LDS, free for reuse when the call returns.
 template <int THREADS, typename T>

@@ -4,10 +4,9 @@
 //   accumulate != 0:  bucket[offset_t + i] = fmaf(scale, g_t[i], bucket[...])   (g_t NULL: nothing is written)
 // and nothing else of the bucket is touched: the padding between the segments keeps the zeros it was allocated with.
 //
-// The structure is csrc/optim.hip's: GbChunk, a plain struct passed BY VALUE as the kernel argument, holds up to GB_CHUNK entries of
-// (g, destination, n, wg0 = the tensor's first workgroup within the launch); the host entry point fills one chunk after another on the
-// stack and launches each.  No device-side pointer table, no copy, nothing kept between calls.  A workgroup owns one slice of GB_SLICE
-// elements of one tensor and finds it by a binary search of blockIdx.x in the wg0 prefix (wave-uniform, read through readfirstlane).
+// MANY TENSORS PER LAUNCH as csrc/multi_tensor.h describes it (the by-value descriptor, the host walk, a workgroup's search for its
+// tensor and slice); this file adds the entry -- GbEntry: (g, destination, n), GB_CHUNK per launch -- and the kernel body.  A workgroup
+// owns one slice of GB_SLICE elements of one tensor.
 // The destination of every group of four elements is 16-byte aligned (the bucket is, offsets are multiples of 4): 16-byte stores always,
 // 16-byte loads of g where g sits on a 16-byte boundary (global_load_dwordx4 in the built ISA: check it after a change, the compiler
 // folds a less explicit form into single-dword loads) and four 4-byte-aligned loads otherwise -- the same numbers either way.  One owner
@@ -16,6 +15,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "multi_tensor.h"
 
 namespace {
 
@@ -32,23 +32,8 @@ struct GbEntry {
 };
 static_assert(sizeof(GbEntry) == 32, "GbEntry layout");
 
-struct GbChunk {
-    GbEntry e[GB_CHUNK];
-    int n_entries;
-    int n_wg;
-};
+typedef MtChunk<GbEntry, GB_CHUNK> GbChunk;
 static_assert(sizeof(GbChunk) <= 4096 - 64, "the descriptor and the other arguments must fit the 4 KiB kernel-argument segment");
-
-// the entry whose workgroup range holds block b: the last one with wg0 <= b (entries hold at least one workgroup each)
-__device__ __forceinline__ int gb_find_entry(const GbChunk& c, int b)
-{
-    int lo = 0, hi = c.n_entries;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (c.e[mid].wg0 <= b) lo = mid; else hi = mid;
-    }
-    return __builtin_amdgcn_readfirstlane(lo);
-}
 
 typedef float gb_f4 __attribute__((ext_vector_type(4)));       // a 16-byte-aligned vector: one global_load / store_dwordx4
 
@@ -93,18 +78,16 @@ __device__ __forceinline__ void gb_slice(const float* __restrict__ g, float* __r
     }
 }
 
-__global__ __launch_bounds__(GB_THREADS) void k_grad_pack(const GbChunk c, float scale, int accumulate)
+// Block b < n_wg of a launch, both kernels' body.  ok == 0 (the guarded kernel under a cleared flag; accumulate == 0 then): zeros.
+__device__ __forceinline__ void gb_block(const GbChunk& c, int b, float scale, int accumulate, int ok)
 {
-    const int b = blockIdx.x;
-    if (b >= c.n_wg) return;
-    const int ei = gb_find_entry(c, b);
-    const float* g = c.e[ei].g;
-    float* dst = c.e[ei].dst;
-    const long long n = c.e[ei].n;
-    const long long lo = (long long)(b - c.e[ei].wg0) * GB_SLICE;
-    const long long hi = lo + GB_SLICE < n ? lo + GB_SLICE : n;
+    const GbEntry& e = c.e[mt_find_entry(c, b)];
+    const float* g = e.g;
+    float* dst = e.dst;
+    long long lo, hi;
+    mt_slice<GB_SLICE>(b, e, lo, hi);
     // one choice per workgroup (per tensor: wave-uniform)
-    if (g == nullptr) {                                                        // (only under assign: an accumulate call makes no entry)
+    if (ok == 0 || g == nullptr) {                                             // (a NULL g only under assign: an accumulate call makes no entry)
         gb_slice<true, true, false>(g, dst, lo, hi, scale);
     } else if (((uintptr_t)g & 15) == 0) {
         if (accumulate != 0) gb_slice<true, false, true>(g, dst, lo, hi, scale);
@@ -113,6 +96,11 @@ __global__ __launch_bounds__(GB_THREADS) void k_grad_pack(const GbChunk c, float
         if (accumulate != 0) gb_slice<false, false, true>(g, dst, lo, hi, scale);
         else gb_slice<false, false, false>(g, dst, lo, hi, scale);
     }
+}
+
+__global__ __launch_bounds__(GB_THREADS) void k_grad_pack(const GbChunk c, float scale, int accumulate)
+{
+    if ((int)blockIdx.x < c.n_wg) gb_block(c, blockIdx.x, scale, accumulate, 1);
 }
 
 // k_grad_pack under a device flag (skip_nonfinite): flag[0] != 0 -- k_grad_pack's arithmetic exactly; flag[0] == 0 -- zeros in every
@@ -127,48 +115,11 @@ __global__ __launch_bounds__(GB_THREADS) void k_grad_pack_guarded(const GbChunk 
     if (n_good != nullptr && b == 0 && threadIdx.x == 0) n_good[0] = (accumulate != 0 ? n_good[0] : 0.0f) + (ok != 0 ? 1.0f : 0.0f);
     if (b >= c.n_wg) return;
     if (ok == 0 && accumulate != 0) return;
-    const int ei = gb_find_entry(c, b);
-    const float* g = c.e[ei].g;
-    float* dst = c.e[ei].dst;
-    const long long n = c.e[ei].n;
-    const long long lo = (long long)(b - c.e[ei].wg0) * GB_SLICE;
-    const long long hi = lo + GB_SLICE < n ? lo + GB_SLICE : n;
-    if (ok == 0 || g == nullptr) {                                             // (accumulate == 0 here: an accumulate call makes no NULL entry)
-        gb_slice<true, true, false>(g, dst, lo, hi, scale);
-    } else if (((uintptr_t)g & 15) == 0) {
-        if (accumulate != 0) gb_slice<true, false, true>(g, dst, lo, hi, scale);
-        else gb_slice<true, false, false>(g, dst, lo, hi, scale);
-    } else {
-        if (accumulate != 0) gb_slice<false, false, true>(g, dst, lo, hi, scale);
-        else gb_slice<false, false, false>(g, dst, lo, hi, scale);
-    }
+    gb_block(c, b, scale, accumulate, ok);
 }
 
-// regtr_grad_pack's argument checks (shared by the guarded entry point; regtr_grad_pack keeps its own lines)
+// both entry points' argument checks
 int gb_check(const regtr_bucket_tensor_t* t, int n_tensors, float* bucket, long long n_bucket, float scale)
-{
-    if (n_tensors < 0 || n_bucket < 0 || (n_tensors > 0 && !t) || scale != scale || ((uintptr_t)bucket & 15)) return RG_ERR_ARG;
-    long long end = 0;
-    bool work = false;
-    for (int i = 0; i < n_tensors; i++) {
-        if (t[i].n < 0 || t[i].n >= (1ll << 40) || ((uintptr_t)t[i].g & 3)) return RG_ERR_ARG;
-        if (t[i].offset < 0 || (t[i].offset & 3) || t[i].offset < end || t[i].offset > n_bucket || t[i].n > n_bucket - t[i].offset)
-            return RG_ERR_ARG;
-        end = t[i].offset + t[i].n;
-        work = work || t[i].n > 0;
-    }
-    if (work && !bucket) return RG_ERR_ARG;
-    return RG_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int regtr_grad_pack_slice(void) { return GB_SLICE; }
-
-int regtr_grad_pack(const regtr_bucket_tensor_t* t, int n_tensors, float* bucket, long long n_bucket, float scale, int accumulate,
-                    void* stream)
 {
     if (n_tensors < 0 || n_bucket < 0 || (n_tensors > 0 && !t) || scale != scale || ((uintptr_t)bucket & 15)) return RG_ERR_ARG;
     long long end = 0;                                                         // one past the previous segment
@@ -181,23 +132,34 @@ int regtr_grad_pack(const regtr_bucket_tensor_t* t, int n_tensors, float* bucket
         work = work || t[i].n > 0;
     }
     if (work && !bucket) return RG_ERR_ARG;
-    GbChunk c;
-    c.n_entries = 0; c.n_wg = 0;
-    for (int i = 0; i <= n_tensors; i++) {
-        const bool skip = i == n_tensors || t[i].n == 0 || (!t[i].g && accumulate != 0);      // (nothing to write)
-        const long long wgs = skip ? 0 : (t[i].n + GB_SLICE - 1) / GB_SLICE;
-        const bool flush = i == n_tensors || c.n_entries == GB_CHUNK || (long long)c.n_wg + wgs > 0x7fffffffll;
-        if (flush && c.n_entries > 0) {
-            k_grad_pack<<<c.n_wg, GB_THREADS, 0, (hipStream_t)stream>>>(c, scale, accumulate);
-            RG_RETURN_IF_LAUNCH_FAILED();
-            c.n_entries = 0; c.n_wg = 0;
-        }
-        if (skip) continue;
-        GbEntry& e = c.e[c.n_entries++];
-        e.g = t[i].g; e.dst = bucket + t[i].offset; e.n = t[i].n; e.wg0 = c.n_wg; e.pad_ = 0;
-        c.n_wg += (int)wgs;
-    }
     return RG_OK;
+}
+
+// the walk over a checked table: a tensor with nothing to write (no element; no gradient under accumulate) makes no entry
+template <typename Launch>
+int gb_walk(const regtr_bucket_tensor_t* t, int n_tensors, float* bucket, int accumulate, Launch launch)
+{
+    return mt_walk<GbChunk>(
+        n_tensors, false, [&](int i) { return !t[i].g && accumulate != 0 ? 0 : (t[i].n + GB_SLICE - 1) / GB_SLICE; },
+        [&](int i, GbEntry& e) { e.g = t[i].g; e.dst = bucket + t[i].offset; e.n = t[i].n; e.pad_ = 0; }, launch);
+}
+
+}  // namespace
+
+extern "C" {
+
+int regtr_grad_pack_slice(void) { return GB_SLICE; }
+
+int regtr_grad_pack(const regtr_bucket_tensor_t* t, int n_tensors, float* bucket, long long n_bucket, float scale, int accumulate,
+                    void* stream)
+{
+    const int st = gb_check(t, n_tensors, bucket, n_bucket, scale);
+    if (st != RG_OK) return st;
+    return gb_walk(t, n_tensors, bucket, accumulate, [&](const GbChunk& c) {
+        k_grad_pack<<<c.n_wg, GB_THREADS, 0, (hipStream_t)stream>>>(c, scale, accumulate);
+        RG_RETURN_IF_LAUNCH_FAILED();
+        return RG_OK;
+    });
 }
 
 int regtr_grad_pack_guarded(const regtr_bucket_tensor_t* t, int n_tensors, float* bucket, long long n_bucket, float scale, int accumulate,
@@ -206,26 +168,16 @@ int regtr_grad_pack_guarded(const regtr_bucket_tensor_t* t, int n_tensors, float
     if (!flag || (((uintptr_t)flag | (uintptr_t)n_good) & 3)) return RG_ERR_ARG;
     const int st = gb_check(t, n_tensors, bucket, n_bucket, scale);
     if (st != RG_OK) return st;
-    GbChunk c;
-    c.n_entries = 0; c.n_wg = 0;
-    bool first = true;
-    for (int i = 0; i <= n_tensors; i++) {
-        const bool skip = i == n_tensors || t[i].n == 0 || (!t[i].g && accumulate != 0);      // (nothing to write)
-        const long long wgs = skip ? 0 : (t[i].n + GB_SLICE - 1) / GB_SLICE;
-        const bool flush = i == n_tensors || c.n_entries == GB_CHUNK || (long long)c.n_wg + wgs > 0x7fffffffll;
-        if (flush && (c.n_entries > 0 || (i == n_tensors && first && n_good))) {
-            k_grad_pack_guarded<<<c.n_wg > 0 ? c.n_wg : 1, GB_THREADS, 0, (hipStream_t)stream>>>(c, scale, accumulate, flag,
-                                                                                              first ? n_good : nullptr);
-            RG_RETURN_IF_LAUNCH_FAILED();
-            first = false;
-            c.n_entries = 0; c.n_wg = 0;
-        }
-        if (skip) continue;
-        GbEntry& e = c.e[c.n_entries++];
-        e.g = t[i].g; e.dst = bucket + t[i].offset; e.n = t[i].n; e.wg0 = c.n_wg; e.pad_ = 0;
-        c.n_wg += (int)wgs;
-    }
-    return RG_OK;
+    bool first = true;                                                         // the call's first launch counts the flag into n_good
+    auto launch = [&](const GbChunk& c) {
+        k_grad_pack_guarded<<<c.n_wg > 0 ? c.n_wg : 1, GB_THREADS, 0, (hipStream_t)stream>>>(c, scale, accumulate, flag, first ? n_good : nullptr);
+        RG_RETURN_IF_LAUNCH_FAILED();
+        first = false;
+        return RG_OK;
+    };
+    const int walked = gb_walk(t, n_tensors, bucket, accumulate, launch);
+    if (walked != RG_OK || !first || !n_good) return walked;
+    return launch(GbChunk{});                                                  // nothing to pack: one workgroup, for the count alone
 }
 
 }  // extern "C"

@@ -266,19 +266,6 @@ int launch_infonce(const InfArgs& g, hipStream_t s)
 // ---------------------------------------------------------------------------------------------------------------- O(N) terms
 constexpr int LT_THREADS = 256;
 
-__device__ __forceinline__ double block_sum_d(double v, double* sh)
-{
-    v = rg_wave_sum(v);
-    const int wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (rg_lane() == 0) sh[wave] = v;
-    __syncthreads();
-    double t = 0.0;
-#pragma unroll
-    for (int w = 0; w < LT_THREADS / RG_WAVE; w++) t += sh[w];
-    return t;
-}
-
 __global__ __launch_bounds__(LT_THREADS) void k_loss_terms(const float* __restrict__ logit, const float* __restrict__ gt,
                                                            const float* __restrict__ kp, const float* __restrict__ warped,
                                                            const int* __restrict__ seg_off, int n_pairs, int n_total,
@@ -322,8 +309,8 @@ __global__ __launch_bounds__(LT_THREADS) void k_loss_terms(const float* __restri
             wsum[side] += (double)w;
         }
     }
-    const double v0 = block_sum_d(bce, sh), v1 = block_sum_d(err[0], sh), v2 = block_sum_d(wsum[0], sh);
-    const double v3 = block_sum_d(err[1], sh), v4 = block_sum_d(wsum[1], sh);
+    const double v0 = rg_block_sum<LT_THREADS>(bce, sh), v1 = rg_block_sum<LT_THREADS>(err[0], sh), v2 = rg_block_sum<LT_THREADS>(wsum[0], sh);
+    const double v3 = rg_block_sum<LT_THREADS>(err[1], sh), v4 = rg_block_sum<LT_THREADS>(wsum[1], sh);
     if (threadIdx.x == 0) {
         out[5 * b] = (float)v0; out[5 * b + 1] = (float)v1; out[5 * b + 2] = (float)v2;
         out[5 * b + 3] = (float)v3; out[5 * b + 4] = (float)v4;

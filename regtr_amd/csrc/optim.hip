@@ -2,13 +2,10 @@
 // AdamW / Adam update of torch.optim, over MANY tensors per launch (the reference's trainer.py:104-121 step over 140-157 parameter
 // tensors).
 //
-// MULTI-TENSOR DESCRIPTOR -- OptChunk, a plain struct passed BY VALUE as the kernel argument: up to OPT_CHUNK entries of
-//   (p, g, m, v, n, the per-tensor scalars, wg0 = the first workgroup index of the tensor within the launch)
-// plus the entry count.  3856 bytes: with the other arguments it stays inside the 4 KiB kernel-argument segment.  There is no
-// device-side pointer table, no host-to-device copy and nothing cached across steps: the host entry point walks the caller's tensor
-// list, fills one chunk after another on the stack and launches each; 157 tensors are four launches.  A workgroup finds its (tensor,
-// slice) by a binary search of blockIdx.x in the entries' wg0 prefix -- scalar loads from the argument segment, the index wave-uniform
-// by construction and passed through readfirstlane so that everything read from the entry stays in SGPRs.
+// MANY TENSORS PER LAUNCH as csrc/multi_tensor.h describes it: the descriptor (MtChunk, by value in the kernel-argument segment), the
+// host walk that fills and launches one chunk after another (mt_walk) and a workgroup's search for its (tensor, slice) (mt_find_entry,
+// mt_slice) live there, once.  This file adds the entries -- OptEntry: (p, g, m, v, n, nine float32 scalars), 48 per launch, 157 tensors
+// are four launches; OptGuardEntry: the guarded step's, with the float64 hyper-parameters, 40 per launch -- and the kernels.
 //
 // regtr_grad_sumsq       -- workgroup w of tensor t sums the squares of slice [s OPT_NORM_SLICE, (s + 1) OPT_NORM_SLICE) of g_t in float64:
 //                           lane l takes elements 1024 j + 4 l + (0..3) for j ascending, then the fixed xor tree over the wave and the
@@ -32,6 +29,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "multi_tensor.h"
 
 namespace {
 
@@ -51,49 +49,18 @@ struct OptEntry {
 };
 static_assert(sizeof(OptEntry) == 80, "OptEntry layout");
 
-struct OptChunk {
-    OptEntry e[OPT_CHUNK];
-    int n_entries;
-    int n_wg;
-    long long part0;                      // regtr_grad_sumsq: index of the chunk's first partial
-};
+typedef MtChunk<OptEntry, OPT_CHUNK> OptChunk;                                // (3856 bytes)
 static_assert(sizeof(OptChunk) <= 4096 - 64, "the descriptor and the other arguments must fit the 4 KiB kernel-argument segment");
-
-// the entry whose workgroup range holds block b: the last one with wg0 <= b (OptChunk's entries hold at least one workgroup each; an
-// empty entry of an OptGuardChunk shares its wg0 with the entry after it, or has n_wg: it is never the LAST one with wg0 <= b)
-template <typename Chunk>
-__device__ __forceinline__ int opt_find_entry(const Chunk& c, int b)
-{
-    int lo = 0, hi = c.n_entries;         // invariant: e[lo].wg0 <= b < e[hi].wg0 (e[n_entries].wg0 = n_wg)
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (c.e[mid].wg0 <= b) lo = mid; else hi = mid;
-    }
-    return __builtin_amdgcn_readfirstlane(lo);
-}
-
-__device__ __forceinline__ double opt_block_sum(double s, double* sh)
-{
-    s = rg_wave_sum(s);                                                        // fixed xor tree
-    if (rg_lane() == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    double t = 0.0;
-#pragma unroll
-    for (int w = 0; w < OPT_THREADS / RG_WAVE; w++) t += sh[w];               // waves in order
-    return t;
-}
 
 __global__ __launch_bounds__(OPT_THREADS) void k_grad_sumsq(const OptChunk c, double* __restrict__ partials)
 {
     __shared__ double sh[OPT_THREADS / RG_WAVE];
     const int b = blockIdx.x;
     if (b >= c.n_wg) return;
-    const int ei = opt_find_entry(c, b);
+    const int ei = mt_find_entry(c, b);
     const float* __restrict__ g = c.e[ei].g;
-    const long long n = c.e[ei].n;
-    const int slice = b - c.e[ei].wg0;
-    const long long lo = (long long)slice * OPT_NORM_SLICE;
-    const long long hi = lo + OPT_NORM_SLICE < n ? lo + OPT_NORM_SLICE : n;
+    long long lo, hi;
+    mt_slice<OPT_NORM_SLICE>(b, c.e[ei], lo, hi);
     const bool vec = ((uintptr_t)g & 15) == 0;                                 // (per tensor: wave-uniform)
     double s = 0.0;
     for (long long i = lo + 4 * (long long)threadIdx.x; i < hi; i += 4 * OPT_THREADS) {
@@ -114,19 +81,27 @@ __global__ __launch_bounds__(OPT_THREADS) void k_grad_sumsq(const OptChunk c, do
 #pragma unroll
         for (int k = 0; k < 4; k++) s += (double)x[k] * (double)x[k];
     }
-    const double t = opt_block_sum(s, sh);
+    const double t = rg_block_sum<OPT_THREADS, false>(s, sh);      // (sh is used this once: no leading barrier)
     if (threadIdx.x == 0) partials[c.part0 + b] = t;
 }
 
+// Both finishes.  grad_scale (NULL: none) multiplies the norm before the coefficient is formed; guard (NULL: none) is the guard word,
+// four int32 on the device, {ok, applied_steps, skipped_steps, reserved}: ONE lane of ONE workgroup -- thread 0 here -- writes it with
+// ordinary stores; every other kernel only reads guard[0], once per workgroup.
 __global__ __launch_bounds__(OPT_THREADS) void k_grad_norm_finish(const double* __restrict__ partials, long long n_partials, float max_norm,
-                                                                  float* __restrict__ out)
+                                                                  const float* __restrict__ grad_scale, float* __restrict__ out,
+                                                                  int* __restrict__ guard)
 {
     __shared__ double sh[OPT_THREADS / RG_WAVE];
     double s = 0.0;
     for (long long i = threadIdx.x; i < n_partials; i += OPT_THREADS) s += partials[i];
-    const double t = opt_block_sum(s, sh);
+    const double t = rg_block_sum<OPT_THREADS, false>(s, sh);      // (sh is used this once: no leading barrier)
     if (threadIdx.x == 0) {
-        const float norm = (float)sqrt(t);
+        float norm = (float)sqrt(t), gs = 1.0f;
+        if (grad_scale) {
+            gs = grad_scale[0];
+            norm = norm * gs;                                                  // (gs == 1: the unscaled bits)
+        }
         float coef = 1.0f;
         if (max_norm > 0.0f) {
             const float c = max_norm / (norm + 1e-6f);
@@ -134,6 +109,12 @@ __global__ __launch_bounds__(OPT_THREADS) void k_grad_norm_finish(const double* 
         }
         out[0] = norm;
         out[1] = coef;
+        if (guard) {
+            const int ok = (isfinite(norm) && isfinite(gs)) ? 1 : 0;
+            guard[0] = ok;
+            guard[1] = guard[1] + ok;
+            guard[2] = guard[2] + (1 - ok);
+        }
     }
 }
 
@@ -148,20 +129,16 @@ __device__ __forceinline__ void opt_update(float& p, float g, float& m, float& v
     p = p - e.step_size * (m / denom);
 }
 
-__global__ __launch_bounds__(OPT_THREADS) void k_adam_step(const OptChunk c, const float* __restrict__ clip_coef, int decoupled)
+// The elements [lo, hi) of one tensor, both step kernels' loop.  e: the scalars only.  SCALED: the gradient is multiplied by gs first
+// (the guarded step; gs == 1 leaves g's bits).  Everything here is wave-uniform but i.
+template <bool SCALED>
+__device__ __forceinline__ void opt_step_slice(float* p_, const float* g_, float* m_, float* v_, long long lo, long long hi, const OptEntry& e,
+                                               float coef, float gs, int decoupled)
 {
-    const int b = blockIdx.x;
-    if (b >= c.n_wg) return;
-    const int ei = opt_find_entry(c, b);
-    const OptEntry& e = c.e[ei];
-    float* __restrict__ p = e.p;
-    const float* __restrict__ g = e.g;
-    float* __restrict__ m = e.m;
-    float* __restrict__ v = e.v;
-    const long long n = e.n;
-    const long long lo = (long long)(b - e.wg0) * OPT_STEP_SLICE;
-    const long long hi = lo + OPT_STEP_SLICE < n ? lo + OPT_STEP_SLICE : n;
-    const float coef = clip_coef ? clip_coef[0] : 1.0f;
+    float* __restrict__ p = p_;
+    const float* __restrict__ g = g_;
+    float* __restrict__ m = m_;
+    float* __restrict__ v = v_;
     const bool dec = decoupled != 0;
     const bool vec = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0;      // (per tensor: wave-uniform)
     for (long long i = lo + 4 * (long long)threadIdx.x; i < hi; i += 4 * OPT_THREADS) {
@@ -169,10 +146,10 @@ __global__ __launch_bounds__(OPT_THREADS) void k_adam_step(const OptChunk c, con
             float4 P = *reinterpret_cast<const float4*>(p + i), M = *reinterpret_cast<const float4*>(m + i);
             float4 V = *reinterpret_cast<const float4*>(v + i);
             const float4 G = *reinterpret_cast<const float4*>(g + i);
-            opt_update(P.x, G.x, M.x, V.x, coef, e, dec);
-            opt_update(P.y, G.y, M.y, V.y, coef, e, dec);
-            opt_update(P.z, G.z, M.z, V.z, coef, e, dec);
-            opt_update(P.w, G.w, M.w, V.w, coef, e, dec);
+            opt_update(P.x, SCALED ? G.x * gs : G.x, M.x, V.x, coef, e, dec);
+            opt_update(P.y, SCALED ? G.y * gs : G.y, M.y, V.y, coef, e, dec);
+            opt_update(P.z, SCALED ? G.z * gs : G.z, M.z, V.z, coef, e, dec);
+            opt_update(P.w, SCALED ? G.w * gs : G.w, M.w, V.w, coef, e, dec);
             *reinterpret_cast<float4*>(p + i) = P;
             *reinterpret_cast<float4*>(m + i) = M;
             *reinterpret_cast<float4*>(v + i) = V;
@@ -181,7 +158,7 @@ __global__ __launch_bounds__(OPT_THREADS) void k_adam_step(const OptChunk c, con
             for (int k = 0; k < 4; k++) {
                 if (i + k < hi) {
                     float P = p[i + k], M = m[i + k], V = v[i + k];
-                    opt_update(P, g[i + k], M, V, coef, e, dec);
+                    opt_update(P, SCALED ? g[i + k] * gs : g[i + k], M, V, coef, e, dec);
                     p[i + k] = P; m[i + k] = M; v[i + k] = V;
                 }
             }
@@ -189,44 +166,17 @@ __global__ __launch_bounds__(OPT_THREADS) void k_adam_step(const OptChunk c, con
     }
 }
 
-// Walks the caller's tensors, `launch`-ing one full chunk after another.  slice: elements per workgroup; need_state: p, m, v are used.
-template <typename Launch>
-int opt_for_each_chunk(const regtr_optim_tensor_t* t, int n_tensors, int slice, bool need_state, Launch launch)
+__global__ __launch_bounds__(OPT_THREADS) void k_adam_step(const OptChunk c, const float* __restrict__ clip_coef, int decoupled)
 {
-    if (n_tensors < 0 || (n_tensors > 0 && !t)) return RG_ERR_ARG;
-    for (int i = 0; i < n_tensors; i++) {
-        if (t[i].n < 0 || t[i].n >= (1ll << 40)) return RG_ERR_ARG;
-        if (t[i].n > 0 && (!t[i].g || (need_state && (!t[i].p || !t[i].m || !t[i].v)))) return RG_ERR_ARG;
-        if ((uintptr_t)t[i].g & 3) return RG_ERR_ARG;
-        if (need_state && (((uintptr_t)t[i].p | (uintptr_t)t[i].m | (uintptr_t)t[i].v) & 3)) return RG_ERR_ARG;
-    }
-    OptChunk c;
-    c.n_entries = 0; c.n_wg = 0; c.part0 = 0;
-    for (int i = 0; i <= n_tensors; i++) {
-        const long long wgs = i < n_tensors ? (t[i].n + slice - 1) / slice : 0;
-        const bool flush = i == n_tensors || c.n_entries == OPT_CHUNK || (long long)c.n_wg + wgs > 0x7fffffffll;
-        if (flush && c.n_entries > 0) {
-            const int st = launch(c);
-            if (st != RG_OK) return st;
-            c.part0 += c.n_wg;
-            c.n_entries = 0; c.n_wg = 0;
-        }
-        if (i == n_tensors || wgs == 0) continue;                              // (an empty tensor: nothing to do)
-        OptEntry& e = c.e[c.n_entries++];
-        const double lr = t[i].lr, wd = t[i].weight_decay, b1 = t[i].beta1, b2 = t[i].beta2;
-        e.p = t[i].p; e.g = t[i].g; e.m = t[i].m; e.v = t[i].v; e.n = t[i].n;
-        e.decay = (float)(1.0 - lr * wd); e.wd = (float)wd;
-        e.b1 = (float)b1; e.omb1 = (float)(1.0 - b1); e.b2 = (float)b2; e.omb2 = (float)(1.0 - b2);
-        e.step_size = (float)(lr / t[i].bias_correction1); e.sqrt_bc2 = (float)t[i].sqrt_bias_correction2; e.eps = (float)t[i].eps;
-        e.wg0 = c.n_wg;
-        c.n_wg += (int)wgs;
-    }
-    return RG_OK;
+    const int b = blockIdx.x;
+    if (b >= c.n_wg) return;
+    const OptEntry& e = c.e[mt_find_entry(c, b)];
+    long long lo, hi;
+    mt_slice<OPT_STEP_SLICE>(b, e, lo, hi);
+    opt_step_slice<false>(e.p, e.g, e.m, e.v, lo, hi, e, clip_coef ? clip_coef[0] : 1.0f, 1.0f, decoupled);
 }
 
 // ---- the guarded step (skip_nonfinite): the decision to leave a step out is taken and obeyed on the device --------------------------------
-// The guard word, four int32 on the device: {ok, applied_steps, skipped_steps, reserved}.  ONE lane of ONE workgroup (thread 0 of
-// k_grad_norm_finish_guarded) writes it with ordinary stores; every other kernel only reads guard[0], once per workgroup.
 constexpr int OPT_GUARD_CHUNK = 40;       // tensors per guarded launch (regtr_optim_guarded_chunk_tensors): the entries carry float64 scalars
 
 struct OptGuardEntry {
@@ -241,11 +191,7 @@ struct OptGuardEntry {
 };
 static_assert(sizeof(OptGuardEntry) == 88, "OptGuardEntry layout");
 
-struct OptGuardChunk {
-    OptGuardEntry e[OPT_GUARD_CHUNK];
-    int n_entries;
-    int n_wg;
-};
+typedef MtChunk<OptGuardEntry, OPT_GUARD_CHUNK> OptGuardChunk;
 static_assert(sizeof(OptGuardChunk) <= 3856, "the guarded descriptor must not outgrow OptChunk: the 4 KiB kernel-argument segment");
 
 // beta^t for an integer t >= 0 by binary exponentiation (never the math library's pow: a numpy restatement reproduces this bit for bit).
@@ -285,31 +231,6 @@ __device__ __forceinline__ void opt_bias_scalars(double lr, double b1, double b2
     sqrt_bc2 = (float)sqrt(1.0 - opt_ipow(b2, ti));
 }
 
-__global__ __launch_bounds__(OPT_THREADS) void k_grad_norm_finish_guarded(const double* __restrict__ partials, long long n_partials,
-                                                                          float max_norm, const float* __restrict__ grad_scale,
-                                                                          float* __restrict__ out, int* __restrict__ guard)
-{
-    __shared__ double sh[OPT_THREADS / RG_WAVE];
-    double s = 0.0;
-    for (long long i = threadIdx.x; i < n_partials; i += OPT_THREADS) s += partials[i];
-    const double t = opt_block_sum(s, sh);
-    if (threadIdx.x == 0) {
-        const float gs = grad_scale ? grad_scale[0] : 1.0f;
-        const float norm = (float)sqrt(t) * gs;                                // (gs == 1: k_grad_norm_finish's bits)
-        float coef = 1.0f;
-        if (max_norm > 0.0f) {
-            const float c = max_norm / (norm + 1e-6f);
-            coef = c > 1.0f ? 1.0f : c;
-        }
-        const int ok = (isfinite(norm) && isfinite(gs)) ? 1 : 0;
-        out[0] = norm;
-        out[1] = coef;
-        guard[0] = ok;
-        guard[1] = guard[1] + ok;
-        guard[2] = guard[2] + (1 - ok);
-    }
-}
-
 // steps[e.step] += 1 for every tensor of the chunk (the empty ones too) when the guard says ok, and the tensor's two per-step scalars
 // from the advanced count into step_scalars[2 e.step ..]: one thread per entry, so the float64 power, divide and square root run once
 // per TENSOR (formed in k_adam_step_guarded they ran once per workgroup, ~2900 times a step: +34 us of kernel time, measured)
@@ -334,48 +255,16 @@ __global__ __launch_bounds__(OPT_THREADS) void k_adam_step_guarded(const OptGuar
     const int b = blockIdx.x;
     if (b >= c.n_wg) return;
     if (__builtin_amdgcn_readfirstlane(guard[0]) == 0) return;                // a skipped step: not one byte is written
-    const int ei = opt_find_entry(c, b);
-    const OptGuardEntry& ge = c.e[ei];
-    OptEntry e;                                                                // k_adam_step's scalars, in opt_for_each_chunk's order
+    const OptGuardEntry& ge = c.e[mt_find_entry(c, b)];
+    OptEntry e;                                                                // k_adam_step's scalars, in opt_walk's order
     e.decay = (float)(1.0 - ge.lr * ge.wd); e.wd = (float)ge.wd;
     e.b1 = (float)ge.b1; e.omb1 = (float)(1.0 - ge.b1); e.b2 = (float)ge.b2; e.omb2 = (float)(1.0 - ge.b2);
     e.eps = (float)ge.eps;
     e.step_size = step_scalars[2 * (long long)ge.step];                       // (k_adam_steps_advance left them, from the advanced count)
     e.sqrt_bc2 = step_scalars[2 * (long long)ge.step + 1];
-    float* __restrict__ p = ge.p;
-    const float* __restrict__ g = ge.g;
-    float* __restrict__ m = ge.m;
-    float* __restrict__ v = ge.v;
-    const long long n = ge.n;
-    const long long lo = (long long)(b - ge.wg0) * OPT_STEP_SLICE;
-    const long long hi = lo + OPT_STEP_SLICE < n ? lo + OPT_STEP_SLICE : n;
-    const float coef = clip_coef ? clip_coef[0] : 1.0f;
-    const float gs = grad_scale ? grad_scale[0] : 1.0f;
-    const bool dec = decoupled != 0;
-    const bool vec = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0;      // (per tensor: wave-uniform)
-    for (long long i = lo + 4 * (long long)threadIdx.x; i < hi; i += 4 * OPT_THREADS) {
-        if (vec && i + 4 <= hi) {
-            float4 P = *reinterpret_cast<const float4*>(p + i), M = *reinterpret_cast<const float4*>(m + i);
-            float4 V = *reinterpret_cast<const float4*>(v + i);
-            const float4 G = *reinterpret_cast<const float4*>(g + i);
-            opt_update(P.x, G.x * gs, M.x, V.x, coef, e, dec);                 // (gs == 1: g itself)
-            opt_update(P.y, G.y * gs, M.y, V.y, coef, e, dec);
-            opt_update(P.z, G.z * gs, M.z, V.z, coef, e, dec);
-            opt_update(P.w, G.w * gs, M.w, V.w, coef, e, dec);
-            *reinterpret_cast<float4*>(p + i) = P;
-            *reinterpret_cast<float4*>(m + i) = M;
-            *reinterpret_cast<float4*>(v + i) = V;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                if (i + k < hi) {
-                    float P = p[i + k], M = m[i + k], V = v[i + k];
-                    opt_update(P, g[i + k] * gs, M, V, coef, e, dec);
-                    p[i + k] = P; m[i + k] = M; v[i + k] = V;
-                }
-            }
-        }
-    }
+    long long lo, hi;
+    mt_slice<OPT_STEP_SLICE>(b, ge, lo, hi);
+    opt_step_slice<true>(ge.p, ge.g, ge.m, ge.v, lo, hi, e, clip_coef ? clip_coef[0] : 1.0f, grad_scale ? grad_scale[0] : 1.0f, decoupled);
 }
 
 __global__ __launch_bounds__(64) void k_adam_bias_scalars(double lr, double b1, double b2, const float* __restrict__ steps, int n,
@@ -383,6 +272,29 @@ __global__ __launch_bounds__(64) void k_adam_bias_scalars(double lr, double b1, 
 {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i < n) opt_bias_scalars(lr, b1, b2, steps[i], out[2 * i], out[2 * i + 1]);
+}
+
+// one tensor of either table: n in [0, 2^40), 4-byte aligned pointers, none of them NULL with elements to work on (state: p, m, v too)
+bool opt_tensor_ok(const float* p, const float* g, const float* m, const float* v, long long n, bool state)
+{
+    if (n < 0 || n >= (1ll << 40) || ((uintptr_t)g & 3) || (n > 0 && !g)) return false;
+    return !state || (!(((uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 3) && !(n > 0 && (!p || !m || !v)));
+}
+
+// the walk over a checked regtr_optim_tensor_t table, `slice` elements per workgroup; an empty tensor makes no entry
+template <typename Launch>
+int opt_walk(const regtr_optim_tensor_t* t, int n_tensors, int slice, Launch launch)
+{
+    return mt_walk<OptChunk>(
+        n_tensors, false, [&](int i) { return (t[i].n + slice - 1) / slice; },
+        [&](int i, OptEntry& e) {
+            const double lr = t[i].lr, wd = t[i].weight_decay, b1 = t[i].beta1, b2 = t[i].beta2;
+            e.p = t[i].p; e.g = t[i].g; e.m = t[i].m; e.v = t[i].v; e.n = t[i].n;
+            e.decay = (float)(1.0 - lr * wd); e.wd = (float)wd;
+            e.b1 = (float)b1; e.omb1 = (float)(1.0 - b1); e.b2 = (float)b2; e.omb2 = (float)(1.0 - b2);
+            e.step_size = (float)(lr / t[i].bias_correction1); e.sqrt_bc2 = (float)t[i].sqrt_bias_correction2; e.eps = (float)t[i].eps;
+        },
+        launch);
 }
 
 }  // namespace
@@ -398,11 +310,11 @@ int regtr_grad_sumsq(const regtr_optim_tensor_t* tensors, int n_tensors, double*
     if (n_tensors < 0 || n_partials < 0 || (n_tensors > 0 && !tensors)) return RG_ERR_ARG;
     long long need = 0;
     for (int i = 0; i < n_tensors; i++) {
-        if (tensors[i].n < 0 || tensors[i].n >= (1ll << 40)) return RG_ERR_ARG;
+        if (!opt_tensor_ok(nullptr, tensors[i].g, nullptr, nullptr, tensors[i].n, false)) return RG_ERR_ARG;
         need += (tensors[i].n + OPT_NORM_SLICE - 1) / OPT_NORM_SLICE;
     }
     if (need != n_partials || (need > 0 && !partials)) return RG_ERR_ARG;      // the caller sized the partials from the same lengths
-    return opt_for_each_chunk(tensors, n_tensors, OPT_NORM_SLICE, false, [&](const OptChunk& c) {
+    return opt_walk(tensors, n_tensors, OPT_NORM_SLICE, [&](const OptChunk& c) {
         k_grad_sumsq<<<c.n_wg, OPT_THREADS, 0, (hipStream_t)stream>>>(c, partials);
         RG_RETURN_IF_LAUNCH_FAILED();
         return RG_OK;
@@ -412,19 +324,21 @@ int regtr_grad_sumsq(const regtr_optim_tensor_t* tensors, int n_tensors, double*
 int regtr_grad_norm_finish(const double* partials, long long n_partials, float max_norm, float* norm_coef, void* stream)
 {
     if (n_partials < 0 || !norm_coef || (n_partials > 0 && !partials) || max_norm != max_norm) return RG_ERR_ARG;
-    k_grad_norm_finish<<<1, OPT_THREADS, 0, (hipStream_t)stream>>>(partials, n_partials, max_norm, norm_coef);
+    k_grad_norm_finish<<<1, OPT_THREADS, 0, (hipStream_t)stream>>>(partials, n_partials, max_norm, nullptr, norm_coef, nullptr);
     RG_RETURN_IF_LAUNCH_FAILED();
     return RG_OK;
 }
 
 int regtr_adam_step(const regtr_optim_tensor_t* tensors, int n_tensors, const float* clip_coef, int decoupled, void* stream)
 {
-    for (int i = 0; i < n_tensors && tensors; i++) {
+    if (n_tensors < 0 || (n_tensors > 0 && !tensors)) return RG_ERR_ARG;
+    for (int i = 0; i < n_tensors; i++) {
         const regtr_optim_tensor_t& t = tensors[i];
+        if (!opt_tensor_ok(t.p, t.g, t.m, t.v, t.n, true)) return RG_ERR_ARG;
         if (!(t.bias_correction1 > 0.0) || !(t.sqrt_bias_correction2 > 0.0) || !(t.eps >= 0.0) || t.lr != t.lr || t.weight_decay != t.weight_decay)
             return RG_ERR_ARG;
     }
-    return opt_for_each_chunk(tensors, n_tensors, OPT_STEP_SLICE, true, [&](const OptChunk& c) {
+    return opt_walk(tensors, n_tensors, OPT_STEP_SLICE, [&](const OptChunk& c) {
         k_adam_step<<<c.n_wg, OPT_THREADS, 0, (hipStream_t)stream>>>(c, clip_coef, decoupled);
         RG_RETURN_IF_LAUNCH_FAILED();
         return RG_OK;
@@ -438,7 +352,7 @@ int regtr_grad_norm_finish_guarded(const double* partials, long long n_partials,
 {
     if (n_partials < 0 || !norm_coef || !guard || (n_partials > 0 && !partials) || max_norm != max_norm) return RG_ERR_ARG;
     if (((uintptr_t)norm_coef | (uintptr_t)guard | (uintptr_t)grad_scale) & 3) return RG_ERR_ARG;
-    k_grad_norm_finish_guarded<<<1, OPT_THREADS, 0, (hipStream_t)stream>>>(partials, n_partials, max_norm, grad_scale, norm_coef, guard);
+    k_grad_norm_finish<<<1, OPT_THREADS, 0, (hipStream_t)stream>>>(partials, n_partials, max_norm, grad_scale, norm_coef, guard);
     RG_RETURN_IF_LAUNCH_FAILED();
     return RG_OK;
 }
@@ -449,18 +363,18 @@ int regtr_adam_step_guarded(const regtr_optim_guarded_tensor_t* t, int n_tensors
     if (n_tensors < 0 || n_steps < 0 || (n_tensors > 0 && (!t || !steps || !step_scalars || !guard))) return RG_ERR_ARG;
     if (((uintptr_t)steps | (uintptr_t)step_scalars | (uintptr_t)clip_coef | (uintptr_t)grad_scale | (uintptr_t)guard) & 3) return RG_ERR_ARG;
     for (int i = 0; i < n_tensors; i++) {
-        if (t[i].n < 0 || t[i].n >= (1ll << 40) || t[i].step_index < 0 || t[i].step_index >= n_steps) return RG_ERR_ARG;
-        if (t[i].n > 0 && (!t[i].g || !t[i].p || !t[i].m || !t[i].v)) return RG_ERR_ARG;
-        if (((uintptr_t)t[i].g | (uintptr_t)t[i].p | (uintptr_t)t[i].m | (uintptr_t)t[i].v) & 3) return RG_ERR_ARG;
+        if (!opt_tensor_ok(t[i].p, t[i].g, t[i].m, t[i].v, t[i].n, true) || t[i].step_index < 0 || t[i].step_index >= n_steps) return RG_ERR_ARG;
         if (!(t[i].eps >= 0.0) || t[i].lr != t[i].lr || t[i].weight_decay != t[i].weight_decay) return RG_ERR_ARG;
         if (!(t[i].beta1 >= 0.0 && t[i].beta1 < 1.0) || !(t[i].beta2 >= 0.0 && t[i].beta2 < 1.0)) return RG_ERR_ARG;
     }
-    OptGuardChunk c;
-    c.n_entries = 0; c.n_wg = 0;
-    for (int i = 0; i <= n_tensors; i++) {
-        const long long wgs = i < n_tensors ? (t[i].n + OPT_STEP_SLICE - 1) / OPT_STEP_SLICE : 0;
-        const bool flush = i == n_tensors || c.n_entries == OPT_GUARD_CHUNK || (long long)c.n_wg + wgs > 0x7fffffffll;
-        if (flush && c.n_entries > 0) {
+    return mt_walk<OptGuardChunk>(
+        n_tensors, true /* an empty tensor's count advances too */, [&](int i) { return (t[i].n + OPT_STEP_SLICE - 1) / OPT_STEP_SLICE; },
+        [&](int i, OptGuardEntry& e) {
+            e.p = t[i].p; e.g = t[i].g; e.m = t[i].m; e.v = t[i].v; e.n = t[i].n;
+            e.lr = t[i].lr; e.wd = t[i].weight_decay; e.b1 = t[i].beta1; e.b2 = t[i].beta2; e.eps = t[i].eps;
+            e.step = t[i].step_index;
+        },
+        [&](const OptGuardChunk& c) {
             // the counts first (an empty tensor's too), then the update reads them: two launches of one stream, in order
             k_adam_steps_advance<<<1, 64, 0, (hipStream_t)stream>>>(c, steps, step_scalars, guard);
             RG_RETURN_IF_LAUNCH_FAILED();
@@ -468,17 +382,8 @@ int regtr_adam_step_guarded(const regtr_optim_guarded_tensor_t* t, int n_tensors
                 k_adam_step_guarded<<<c.n_wg, OPT_THREADS, 0, (hipStream_t)stream>>>(c, step_scalars, clip_coef, grad_scale, guard, decoupled);
                 RG_RETURN_IF_LAUNCH_FAILED();
             }
-            c.n_entries = 0; c.n_wg = 0;
-        }
-        if (i == n_tensors) continue;
-        OptGuardEntry& e = c.e[c.n_entries++];
-        e.p = t[i].p; e.g = t[i].g; e.m = t[i].m; e.v = t[i].v; e.n = t[i].n;
-        e.lr = t[i].lr; e.wd = t[i].weight_decay; e.b1 = t[i].beta1; e.b2 = t[i].beta2; e.eps = t[i].eps;
-        e.step = t[i].step_index;
-        e.wg0 = c.n_wg;
-        c.n_wg += (int)wgs;
-    }
-    return RG_OK;
+            return RG_OK;
+        });
 }
 
 int regtr_adam_bias_scalars(double lr, double beta1, double beta2, const float* steps, int n, float* out, void* stream)

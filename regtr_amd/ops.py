@@ -2,6 +2,7 @@
 stream only; every arithmetic step runs in libregtr_hip.so.  Nothing here synchronises with the host, with one documented
 exception: `KdTree` (the reference-order parity mode) reads its row width back.  Every pointer handed to the library is checked
 for device, dtype and contiguity (_lib.ptr / iptr / bptr / dptr)."""
+import functools
 import math
 import operator
 
@@ -1323,10 +1324,23 @@ def pose_metrics(pred, gt):
     return (out, comp) if layered else (out[0], comp[0])
 
 
-# ------------------------------------------------------------------------------------------------ optimiser step (csrc/optim.hip)
-_OPTIM_DTYPE = None
+# ------------------------------------------------------------------------------------------------ optimiser step (csrc/optim.hip over csrc/multi_tensor.h)
 _T = torch.Tensor
 _dtype_of = operator.attrgetter('dtype')
+
+
+@functools.lru_cache(maxsize=None)
+def _table_dtype(name):
+    """numpy's layout of one row of a host table (include/regtr_hip.h): 'optim' regtr_optim_tensor_t, 'guarded'
+    regtr_optim_guarded_tensor_t, 'bucket' regtr_bucket_tensor_t -- built on first use (numpy is imported lazily)."""
+    import numpy as np
+    pgmvn = [(k, np.uint64) for k in 'pgmv'] + [('n', np.int64)]
+    fields, size = {'optim': (pgmvn + [('scalars', np.float64, (7,))], 96),
+                    'guarded': (pgmvn + [('hyper', np.float64, (5,)), ('step_index', np.int32)], 88),
+                    'bucket': ([('g', np.uint64), ('n', np.int64), ('offset', np.int64)], 24)}[name]
+    dtype = np.dtype(fields, align=True)
+    assert dtype.itemsize == size
+    return dtype
 
 
 def _optim_all_ok(lists):
@@ -1348,12 +1362,7 @@ def _optim_table(grads, params=None, exp_avgs=None, exp_avg_sqs=None, scalars=No
     the list of gradient tensors it points at (kept alive by the caller until the launches are enqueued).  Every tensor is checked HERE,
     with a Python exception: a GPU tensor on the launch device, float32; p, m, v contiguous; g of p's shape, m and v of p's element count
     (a non-contiguous g is made contiguous)."""
-    global _OPTIM_DTYPE
     import numpy as np
-    if _OPTIM_DTYPE is None:
-        _OPTIM_DTYPE = np.dtype([('p', np.uint64), ('g', np.uint64), ('m', np.uint64), ('v', np.uint64), ('n', np.int64),
-                                 ('scalars', np.float64, (7,))], align=True)
-        assert _OPTIM_DTYPE.itemsize == 96
     n = len(grads)
     state = params is not None
     if state and not (len(params) == len(exp_avgs) == len(exp_avg_sqs) == len(scalars) == n):
@@ -1366,7 +1375,7 @@ def _optim_table(grads, params=None, exp_avgs=None, exp_avg_sqs=None, scalars=No
     if not ok:
         _optim_explain(grads, params, exp_avgs, exp_avg_sqs, what)
     keep = grads if all(map(_T.is_contiguous, grads)) else [g if g.is_contiguous() else g.contiguous() for g in grads]
-    tab = np.zeros(n, dtype=_OPTIM_DTYPE)
+    tab = np.zeros(n, dtype=_table_dtype('optim'))
     tab['g'] = list(map(_T.data_ptr, keep))
     tab['n'] = list(map(_T.numel, keep))
     if state:
@@ -1413,14 +1422,13 @@ def optim_slices():
     return int(L.regtr_optim_norm_slice()), int(L.regtr_optim_step_slice()), int(L.regtr_optim_chunk_tensors())
 
 
-_optim_norm_slice = None
+@functools.lru_cache(maxsize=None)
+def _optim_norm_slice():
+    return int(_lib.lib().regtr_optim_norm_slice())
 
 
 def _sumsq(tab, keep):
-    global _optim_norm_slice
-    if _optim_norm_slice is None:
-        _optim_norm_slice = int(_lib.lib().regtr_optim_norm_slice())
-    sl = _optim_norm_slice
+    sl = _optim_norm_slice()
     n_part = int(((tab['n'] + (sl - 1)) // sl).sum())
     dev = keep[0].device if keep else torch.device('cuda', torch.cuda.current_device())
     partials = torch.empty(n_part, dtype=torch.float64, device=dev)
@@ -1445,6 +1453,10 @@ def grad_norm_finish(partials, max_norm):
     return out
 
 
+def _adam_step(tab, n, clip_coef, decoupled):
+    check(_lib.lib().regtr_adam_step(tab.ctypes.data if n else None, n, ptr(clip_coef), 1 if decoupled else 0, stream()), 'regtr_adam_step')
+
+
 def adam_step(params, grads, exp_avgs, exp_avg_sqs, scalars, clip_coef=None, decoupled=True):
     """torch's single-tensor AdamW (decoupled) / Adam step on every tensor in place (regtr_adam_step).  scalars: per tensor (lr,
     weight_decay, beta1, beta2, eps, bias_correction1 = 1 - beta1^t, sqrt(bias_correction2) = sqrt(1 - beta2^t)), host float64.
@@ -1456,8 +1468,7 @@ def adam_step(params, grads, exp_avgs, exp_avg_sqs, scalars, clip_coef=None, dec
     tab, keep = _optim_table(grads, params, exp_avgs, exp_avg_sqs, scalars, what='adam_step')
     if clip_coef is not None and clip_coef.numel() != 1:
         raise RuntimeError(f'adam_step: clip_coef must hold one float32, got {tuple(clip_coef.shape)}')
-    check(_lib.lib().regtr_adam_step(tab.ctypes.data if len(keep) else None, len(keep), ptr(clip_coef), 1 if decoupled else 0, stream()),
-          'regtr_adam_step')
+    _adam_step(tab, len(keep), clip_coef, decoupled)
 
 
 def clip_adam_step(params, grads, exp_avgs, exp_avg_sqs, scalars, max_norm, decoupled=True):
@@ -1465,15 +1476,11 @@ def clip_adam_step(params, grads, exp_avgs, exp_avg_sqs, scalars, max_norm, deco
     (checked once) -> the (2,) float32 device tensor [total_norm before clipping, clip_coef].  What FusedAdamW.step runs."""
     tab, keep = _optim_table(grads, params, exp_avgs, exp_avg_sqs, scalars, what='clip_adam_step')
     norm_coef = grad_norm_finish(_sumsq(tab, keep), max_norm)
-    check(_lib.lib().regtr_adam_step(tab.ctypes.data if len(keep) else None, len(keep), ptr(norm_coef[1:]), 1 if decoupled else 0, stream()),
-          'regtr_adam_step')
+    _adam_step(tab, len(keep), norm_coef[1:], decoupled)
     return norm_coef
 
 
 # ------------------------------------------------------------------------------------------------ the guarded step (skip_nonfinite)
-_OPTIM_GUARDED_DTYPE = None
-
-
 def optim_guarded_chunk():
     """Tensors per launch of adam_step_guarded -- tests straddle it."""
     return int(_lib.lib().regtr_optim_guarded_chunk_tensors())
@@ -1507,14 +1514,9 @@ def grad_norm_finish_guarded(partials, max_norm, guard, grad_scale=None):
 
 
 def _guarded_table(tab, hypers, step_index):
-    global _OPTIM_GUARDED_DTYPE
     import numpy as np
-    if _OPTIM_GUARDED_DTYPE is None:
-        _OPTIM_GUARDED_DTYPE = np.dtype([('p', np.uint64), ('g', np.uint64), ('m', np.uint64), ('v', np.uint64), ('n', np.int64),
-                                         ('hyper', np.float64, (5,)), ('step_index', np.int32)], align=True)
-        assert _OPTIM_GUARDED_DTYPE.itemsize == 88
     n = len(tab)
-    gtab = np.zeros(n, dtype=_OPTIM_GUARDED_DTYPE)
+    gtab = np.zeros(n, dtype=_table_dtype('guarded'))
     for k in ('p', 'g', 'm', 'v', 'n'):
         gtab[k] = tab[k]
     if n:
@@ -1601,9 +1603,6 @@ def grad_finite_flag(grads, guard):
 
 
 # ------------------------------------------------------------------------------------------------ gradient bucket (csrc/grad_bucket.hip)
-_BUCKET_DTYPE = None
-
-
 def grad_pack_slice():
     """Elements per workgroup of grad_pack -- tests straddle it."""
     return int(_lib.lib().regtr_grad_pack_slice())
@@ -1619,11 +1618,7 @@ def grad_pack(grads, offsets, bucket, scale, accumulate, sizes=None, flag=None, 
     flag (a guard word, (4,) int32 on the device; None: the unguarded launch above): regtr_grad_pack_guarded -- flag[0] != 0 the same
     arithmetic, flag[0] == 0 zeros under assign and nothing under accumulate; n_good (a 1-element float32 device tensor outside every
     segment, or None) then receives (accumulate ? n_good : 0) + (flag[0] != 0), unscaled."""
-    global _BUCKET_DTYPE
     import numpy as np
-    if _BUCKET_DTYPE is None:
-        _BUCKET_DTYPE = np.dtype([('g', np.uint64), ('n', np.int64), ('offset', np.int64)], align=True)
-        assert _BUCKET_DTYPE.itemsize == 24
     n = len(grads)
     if len(offsets) != n or (sizes is not None and len(sizes) != n):
         raise RuntimeError('grad_pack: grads, offsets (and sizes) must have one entry per tensor')
@@ -1634,7 +1629,7 @@ def grad_pack(grads, offsets, bucket, scale, accumulate, sizes=None, flag=None, 
         if have and not _optim_all_ok((have,)):
             _optim_explain(have, None, None, None, 'grad_pack')
         keep = [g if g is None or g.is_contiguous() else g.contiguous() for g in grads]
-        tab = np.zeros(n, dtype=_BUCKET_DTYPE)
+        tab = np.zeros(n, dtype=_table_dtype('bucket'))
         if n:
             if sizes is None and len(have) != n:
                 raise RuntimeError('grad_pack: a None gradient needs its length in sizes')

@@ -1,4 +1,4 @@
-"""numpy restatement of the guarded optimiser step (FusedAdamW(skip_nonfinite=True); csrc/optim.hip's k_grad_norm_finish_guarded,
+"""numpy restatement of the guarded optimiser step (FusedAdamW(skip_nonfinite=True); csrc/optim.hip's k_grad_norm_finish under a guard,
 k_adam_steps_advance, k_adam_step_guarded) and of the guarded bucket's flag, on top of tests/optim_ref.py, whose float64 update and
 one-step float32 bound it imports unchanged.
 
