@@ -69,6 +69,10 @@
  *   regtr_segment_mean        the modified Chamfer distance (nearest neighbours, per-cloud means)   benchmark/benchmark_modelnet.py:69-76
  *   regtr_pose_metrics        se3_compare; the RPMNet / DCP pose metrics   utils/se3_torch.py:93-105, benchmark/benchmark_modelnet.py:51-67
  *   regtr_gather_segments     (no reference counterpart) packs the cached per-cloud tokens of the pairs of one RegTR.register call
+ *   regtr_icp_step            (no reference counterpart) one point-to-point ICP iteration on the raw clouds: fused transform + nearest
+ *                             match + float64 moments, then the per-pair Kabsch solve, fitness / inlier_rmse and the stop rule
+ *   regtr_icp_ws_bytes /
+ *   regtr_icp_chunk           (no reference counterpart) its workspace size and chunking
  */
 #ifndef REGTR_HIP_H
 #define REGTR_HIP_H
@@ -991,6 +995,47 @@ int regtr_grad_pack(const regtr_bucket_tensor_t* tensors, int n_tensors, float* 
  * n_good that is not 4-byte aligned. */
 int regtr_grad_pack_guarded(const regtr_bucket_tensor_t* tensors, int n_tensors, float* bucket, long long n_bucket, float scale,
                             int accumulate, const int* flag, float* n_good, void* stream);
+
+/* ---- ICP pose refinement and registration fitness (regtr_amd/refine.py; csrc/icp.hip) -------------------------------------------------
+ * Point-to-point ICP on the full-resolution clouds and Open3D-style fitness / inlier_rmse of a pose.  New entry points only: no
+ * existing signature changes, REGTR_ABI_VERSION stays as it is. */
+
+/* Host only: source rows per workgroup of regtr_icp_step's accumulate pass (a cloud of n rows has ceil(n / chunk) chunks). */
+int regtr_icp_chunk(void);
+
+/* Bytes of regtr_icp_step's workspace: 17 doubles per chunk slot, ceil(max_src_len / chunk) slots per pair.  0 for a negative count. */
+size_t regtr_icp_ws_bytes(int n_pairs, int max_src_len);
+
+/* ONE iteration of point-to-point ICP over packed pairs: an accumulate launch and a solve launch, nothing waits for the host.
+ *   src_xyz [n_src, 3] with src_off [n_pairs + 1], tgt_off [n_pairs + 1] over n_tgt target rows: source cloud b searches target cloud b.
+ *   grid_ws: a cell grid built ONCE by regtr_cellgrid_build over the targets (n_clouds = n_pairs, ns_cap = n_tgt) with
+ *   grid_radius * (1 + 1e-6) >= max_dist, and serving every iteration.  max_src_len >= every source cloud's length (rows of a cloud
+ *   beyond it are not visited).  pose [n_pairs, 12] float32 (3x4 row-major) is read and written in place.
+ * Accumulate: every source row p of a pair that is not done is transformed, y = ((r0 x + r1 y) + r2 z) + t in float32 rounded per
+ * operation (regtr_se3_transform's bits), and matched to the nearest target row q of its pair with d2 < max_dist^2 -- d2 in float64 on
+ * the widened coordinates, ties to the lower index: regtr_nearest_in_radius's rule, and its index bit for bit.  Matched rows add to the
+ * float64 moments n, sum d2, sum p, sum q, sum p q^T with p the ORIGINAL source point; the sums run in a fixed order without atomics
+ * (bit-reproducible).  idx [n_src] (optional): the match, -1 when the ball is empty; d2 [n_src] (optional): its float64 d2, +inf when
+ * empty.
+ * Solve, per pair: fitness = n / n_src_b (0 for an empty source cloud), inlier_rmse = sqrt(sum d2 / n) (0 when n == 0), written with n
+ * to stats [n_pairs, 3] (float64).  The pair is DONE -- done[b] = 1, its pose, stats, iters_run and idx / d2 rows never written again by
+ * later calls with iter > 0 -- when iter > 0 and |fitness - previous| < rel_fitness and |inlier_rmse - previous| < rel_rmse (the
+ * previous call's stats), when n < 3, when the covariance fixes no rotation (min (lam_i + lam_j) <= 2^-23 lam_0, the test of
+ * regtr_weighted_procrustes_bwd), or when its pose holds a non-finite entry.  Otherwise pose = the fit of the matches (cov = sum p q^T /
+ * n - pbar qbar^T, R with the reflection rule of regtr_weighted_procrustes, t = qbar - R pbar, float64 rounded to float32) -- the
+ * absolute pose, nothing is composed -- and iters_run[b] = iter + 1.
+ *   iter: the iteration's number.  iter == 0 reads neither done nor the previous stats and writes done, iters_run and every row of idx /
+ *   d2; the caller passes 0, 1, 2, ... over the same arrays.  stats_only != 0: the pass writes stats (and idx / d2) of the pairs that
+ *   are not done and leaves pose alone -- after the last iteration it gives the stats of the returned pose; with iter == 0 it is
+ *   evaluate_registration.
+ * n_pairs == 0 or n_src == 0: REGTR_OK, nothing launched or written.  Refused (REGTR_ERR_ARG, nothing launched): a negative count or
+ * iter, n_pairs > 65535 (more clouds than a launch over the grid supports), max_src_len < 1 or > n_src, NULL src_xyz / offsets / grid_ws
+ * / pose / stats / iters_run / done / ws, max_dist or grid_radius not > 0, a grid built for a smaller radius.  REGTR_ERR_WORKSPACE:
+ * grid_ws_bytes below regtr_cellgrid_ws_bytes(n_tgt, n_pairs) or ws_bytes below regtr_icp_ws_bytes(n_pairs, max_src_len). */
+int regtr_icp_step(const float* src_xyz, const int* src_off, int n_src, int max_src_len, const int* tgt_off, int n_tgt, int n_pairs,
+                   double max_dist, float grid_radius, const void* grid_ws, size_t grid_ws_bytes, float* pose, int iter, int stats_only,
+                   double rel_fitness, double rel_rmse, double* stats, int* iters_run, int* done, int* idx, double* d2, void* ws,
+                   size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -169,6 +169,10 @@ SIGNATURES = {
     'regtr_grad_norm_finish_guarded': (_I, [_P, _c.c_longlong, _F, _P, _P, _P, _P]),
     'regtr_adam_step_guarded': (_I, [_P, _I, _P, _P, _c.c_longlong, _P, _P, _P, _I, _P]),
     'regtr_adam_bias_scalars': (_I, [_c.c_double, _c.c_double, _c.c_double, _P, _I, _P, _P]),
+    'regtr_icp_chunk': (_I, []),
+    'regtr_icp_ws_bytes': (_Z, [_I, _I]),
+    'regtr_icp_step': (_I, [_P, _P, _I, _I, _P, _I, _I, _c.c_double, _F, _P, _Z, _P, _I, _I, _c.c_double, _c.c_double, _P, _P, _P, _P, _P,
+                            _P, _Z, _P]),
 }
 
 COMPOSITE = ('regtr_encoder_fwd', 'regtr_cross_encoder_fwd')      # bound through a GIL-releasing handle (see _load)

@@ -1031,7 +1031,7 @@ def train_loop(model, batches, steps, first_step=0, train_backbone=True, validat
 
 
 # ------------------------------------------------------------------------------------------------------ the test loop
-def run_test(model, pairs, batch, device, logger=None, max_pairs=None, num_workers=0, loader_pool=None, losses=False):
+def run_test(model, pairs, batch, device, logger=None, max_pairs=None, num_workers=0, loader_pool=None, losses=False, refine=None):
     """Runs every pair of `pairs` (this rank's shard) through the model, B at a time.  loader_pool: a LoaderPool over `pairs` (loader
     processes forked by the caller, e.g. before the GPU was initialised); else num_workers > 0: a pool forked here for this pass;
     0: one loader thread (Prefetcher).
@@ -1041,6 +1041,10 @@ def run_test(model, pairs, batch, device, logger=None, max_pairs=None, num_worke
     losses: also RegTR.compute_loss(per_pair=True) of every pair (3DMatch-style pair sources: GT pose per pair, level-0 masks from
     overlap.compute_overlap_masks at cfg.overlap_radius); the means over all pairs of all ranks (one extra all-reduce) are returned in
     timing['losses'].  Without it the launches and outputs are those of a plain run.
+    refine: None, or {'max_dist', 'iters'}: every batch's last-layer pose is polished on the batch's raw clouds by RegTR.refine_pose
+    (point-to-point ICP, regtr_amd/refine.py) on the stream of its forward, one model or replicas alike; the REFINED poses are returned
+    and timing['refine'] holds the means over all pairs of all ranks of fitness and inlier_rmse before and after.  None: no launch and
+    no output of a plain run changes.
     Returns, on every rank, (poses (n_total, 3, 4) float32 numpy ordered by pair id, pair ids, timing dict)."""
     import contextlib
     import itertools
@@ -1062,7 +1066,9 @@ def run_test(model, pairs, batch, device, logger=None, max_pairs=None, num_worke
     R = len(models)
     streams = [torch.cuda.Stream(device) for _ in range(R)] if (cuda and R > 1) else [None] * R
     it, turn, counter = iter(loader), threading.Lock(), itertools.count()
-    done, errs, fwd_ms, loss_done = [], [], [], []
+    done, errs, fwd_ms, loss_done, refine_done = [], [], [], [], []
+    if refine is not None and set(refine) != {'max_dist', 'iters'}:
+        raise ValueError(f"run_test(refine=...): a dict with exactly 'max_dist' and 'iters' expected, got {sorted(refine)}")
     if losses:
         if any(m.cfg.get('dataset', '3dmatch') != '3dmatch' for m in models):
             raise NotImplementedError('run_test(losses=True): ModelNet losses are not implemented (3DMatch-style pair sources only)')
@@ -1093,6 +1099,12 @@ def run_test(model, pairs, batch, device, logger=None, max_pairs=None, num_worke
                         lo = models[r].compute_loss(out, {'kpconv_meta': fb['kpconv_meta'], 'pose': pose, 'src_overlap': sm,
                                                           'tgt_overlap': tm}, per_pair=True)
                         loss_done.append((k, list(lo), torch.stack([v_.to(torch.float64) for v_ in lo.values()])))     # (keys, B)
+                    if refine is not None:
+                        from . import refine as refine_
+                        before = refine_.evaluate_registration(b['src_xyz'], b['tgt_xyz'], out['pose'][-1], refine['max_dist'])
+                        res = models[r].refine_pose(fb, out['pose'][-1], max_dist=refine['max_dist'], iters=refine['iters'])
+                        refine_done.append((k, torch.stack([before[0], before[1], res.fitness, res.inlier_rmse])))      # (4, B) float64
+                        out = {'pose': res.pose[None]}
                     done.append((k, out['pose'][-1], b['ids'] if 'ids' in b else [i_['idx'] for i_ in b['items']]))      # (B, 3, 4), stays on the device
         except BaseException as e:      # noqa: BLE001  (re-raised on the caller)
             errs.append(e)
@@ -1129,6 +1141,16 @@ def run_test(model, pairs, batch, device, logger=None, max_pairs=None, num_worke
             dist.all_reduce(red)                   # per-term sums and the pair count of every rank
         red = red.cpu().numpy()
         loss_means = {k_: float(red[j] / red[-1]) if red[-1] > 0 else float('nan') for j, k_ in enumerate(keys)}
+    refine_means = None
+    if refine is not None:
+        refine_done.sort(key=lambda d: d[0])
+        per = torch.cat([d[1] for d in refine_done], dim=1) if refine_done else torch.zeros((4, 0), dtype=torch.float64, device=device)
+        red = torch.cat([per.sum(dim=1), torch.tensor([float(per.shape[1])], dtype=torch.float64).to(device, non_blocking=True)])
+        if world > 1:
+            dist.all_reduce(red)
+        red = red.cpu().numpy()
+        refine_means = {k_: float(red[j] / red[-1]) if red[-1] > 0 else float('nan')
+                        for j, k_ in enumerate(('fitness_before', 'inlier_rmse_before', 'fitness_after', 'inlier_rmse_after'))}
     if device.type == 'cuda':
         torch.cuda.synchronize(device)
     elapsed = time.perf_counter() - t0
@@ -1144,6 +1166,8 @@ def run_test(model, pairs, batch, device, logger=None, max_pairs=None, num_worke
     timing = {'elapsed_s': elapsed, 'pairs': n, 'world': world, 'loader': getattr(loader_pool, 'last_timing', None), 'forward_ms': fwd_ms}
     if losses:
         timing['losses'] = loss_means
+    if refine is not None:
+        timing['refine'] = refine_means
     return poses_np, all_ids.cpu().numpy(), timing
 
 
@@ -1191,7 +1215,7 @@ def plan_windows(pair_keys, batch, max_bank_clouds):
                'src': [at[s] for s, _ in win], 'tgt': [at[t] for _, t in win]}
 
 
-def run_test_shared(model, pairs, batch, device, logger=None, max_pairs=None, max_bank_clouds=1024, losses=False):
+def run_test_shared(model, pairs, batch, device, logger=None, max_pairs=None, max_bank_clouds=1024, losses=False, refine=None):
     """run_test over a pair source that names its fragments (pairs.fragment_keys(i) -> (src_key, tgt_key), pairs.load_fragment(key) ->
     (n, 3) float32: ThreeDMatchPairs, SyntheticScenePairs), with every fragment's backbone run ONCE for as long as it stays in a bank of
     at most max_bank_clouds clouds: per window of `batch` pairs (plan_windows) the missing fragments are loaded and encoded in one
@@ -1200,8 +1224,11 @@ def run_test_shared(model, pairs, batch, device, logger=None, max_pairs=None, ma
     window runs (as Prefetcher does for pairs; the LoaderPool processes are not used).  Under a process group every rank takes pairs i %
     world as run_test does and encodes the fragments of its own shard.  Returns what run_test returns, through gather_poses; timing
     additionally carries clouds_encoded, distinct_fragments and pair_slots (= 2 x pairs) of this rank.
-    Refused: a list of replicas, losses=True."""
+    Refused: a list of replicas, losses=True, refine (ICP reads the raw clouds, which a bank need not hold)."""
     import torch.distributed as dist
+    if refine is not None:
+        raise NotImplementedError('run_test_shared: refine is not implemented on the shared path: ICP reads the raw clouds of a pair, and a '
+                                  'cloud bank need not hold them (use run_test)')
     if isinstance(model, (list, tuple)):
         raise NotImplementedError('run_test_shared: replicas are not implemented on the shared path (one model, one stream)')
     if losses:

@@ -60,6 +60,11 @@ parser.add_argument('--max_pairs', type=int, default=None)
 parser.add_argument('--losses', action='store_true',
                     help='also compute the reference\'s test losses (RegTR.compute_loss per pair on GT overlap masks) and log a [Losses] line; '
                          '3DMatch-style pair sources only')
+parser.add_argument('--refine', choices=('icp',), default=None,
+                    help='polish every predicted pose on the full-resolution clouds before it is written (regtr_amd.refine.icp: point-to-point '
+                         'ICP on the device, on the forward\'s stream); est.log then holds the refined poses.  Not with --share_backbone')
+parser.add_argument('--refine_dist', type=float, default=None, help='--refine: correspondence distance (default 2 x cfg.first_subsampling_dl)')
+parser.add_argument('--refine_iters', type=int, default=30, help='--refine: ICP iterations at most (default 30)')
 parser.add_argument('--share_backbone', action='store_true',
                     help='encode every fragment once and register all its pairs against the cached result (RegTR.encode_clouds / register, '
                          'harness.run_test_shared): one model, one loader thread; not with --losses or --replicas')
@@ -158,6 +163,9 @@ def main():
 
     if opt.share_backbone and (opt.losses or opt.replicas > 1):
         logger.error('--share_backbone runs one model without the test losses: drop --losses / --replicas')
+        sys.exit(-4)
+    if opt.share_backbone and opt.refine:
+        logger.error('--refine needs the raw clouds, which a cloud bank need not hold: drop --share_backbone')
         sys.exit(-4)
     if opt.fragments and (opt.synthetic <= 0 or opt.materialize or opt.fragments < 2 or cfg.dataset != '3dmatch'):
         logger.error('--fragments F (F >= 2) goes with --synthetic N on a 3dmatch config, without --materialize')
@@ -261,6 +269,9 @@ def main():
             torch.cuda.synchronize(device)
             del wc, wbank
     t_run = time.perf_counter()
+    refine = None
+    if opt.refine:
+        refine = {'max_dist': opt.refine_dist if opt.refine_dist is not None else 2 * cfg.first_subsampling_dl, 'iters': opt.refine_iters}
     if opt.share_backbone:
         poses, ids, timing = harness.run_test_shared(model, pairs, opt.batch, device, logger, opt.max_pairs, max_bank_clouds=opt.max_bank_clouds)
         logger.info(f'[Shared backbone] clouds_encoded / pair_slots = {timing["clouds_encoded"]} / {timing["pair_slots"]} = '
@@ -268,7 +279,11 @@ def main():
                     f'{opt.max_bank_clouds} clouds; this rank)')
     else:
         poses, ids, timing = harness.run_test(models if len(models) > 1 else model, pairs, opt.batch, device, logger, opt.max_pairs, loader_pool=pool,
-                                             losses=opt.losses)
+                                             losses=opt.losses, refine=refine)
+        if refine is not None:
+            rf = timing['refine']
+            logger.info(f'[Refine] icp, max_dist {refine["max_dist"]:g}, at most {refine["iters"]} iterations: fitness {rf["fitness_before"]:.4f} -> '
+                        f'{rf["fitness_after"]:.4f}, inlier_rmse {rf["inlier_rmse_before"]:.5f} -> {rf["inlier_rmse_after"]:.5f} (means over {len(ids)} pairs)')
     if pool is not None:
         logger.info(f'loader: {timing["loader"]}; forward ms (host clock, incl. the end-of-forward status wait): {timing["forward_ms"]}')
         pool.close()
