@@ -569,7 +569,7 @@ class KPFEncoder(nn.Module):
         lq = last.layer_ind + (1 if 'strided' in last.block_name else 0)
         out_dim = last.KPConv.out_channels if isinstance(last, SimpleBlock) else last.unary2.out_dim
         out = torch.empty((meta['points'][lq].shape[0], out_dim), dtype=torch.float32, device=x.device)
-        ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+        ws = ops._ws(nb, x.device)
         _lib.check(L.regtr_encoder_fwd(blocks, nb_blocks, levels, n_levels, n_clouds, start, stop, _lib.ptr(x), _lib.ptr(out), f16, 0.1, 1e-5,
                                        _lib.bptr(ws), nb, ctx.status_ptr(), _lib.stream()), 'regtr_encoder_fwd')
         return out

@@ -13,7 +13,13 @@ from ._lib import bptr, check, dptr, iptr, ptr, raw, stream
 
 
 def _ws(nbytes, device):
+    """Every workspace a launcher is handed comes from here (tests replace this one function to control what a workspace holds)."""
     return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+
+
+def _ws_as(numel, dtype, device):
+    """Typed scratch of `numel` elements: a view of a _ws byte buffer."""
+    return _ws(int(numel) * dtype.itemsize, device).view(dtype)
 
 
 # ------------------------------------------------------------------------------------------------ preprocessing
@@ -255,7 +261,7 @@ def gemm(a, b, bias=None, row_div=None, residual=None, relu=False, out=None, a_s
         if R:
             s_off = want_stats[0]
             n_clouds = s_off.numel() - 1
-            partial = torch.empty((((M + R - 1) // R + n_clouds) * N, 2), dtype=torch.float64, device=a.device)
+            partial = _ws_as(((M + R - 1) // R + n_clouds) * N * 2, torch.float64, a.device)
         seg_rows = s_off if R else a_seg_off                    # the cloud table of the rows, when the launch needs one
         ti = None
         if seg_rows is not None and (a_seg_off is None or s_off is None or a_seg_off is s_off):
@@ -325,7 +331,7 @@ def gemm_stream(a, sw, seg_off, a_stats=None, a_slope=0.1, want_stats=False, eps
     ti = tile_segments(seg_off, M, R)
     partial = None
     if want_stats:
-        partial = torch.empty((((M + R - 1) // R + n_clouds) * N, 2), dtype=torch.float64, device=a.device)
+        partial = _ws_as(((M + R - 1) // R + n_clouds) * N * 2, torch.float64, a.device)
     out = torch.empty((M, N), dtype=torch.float32, device=a.device)
     check(L.regtr_gemm_stream(raw(a), a.stride(0) if M > 1 else K, bptr(sw.planes), ptr(out), N, M, N, K, ptr(a_stats), a_slope,
                               iptr(seg_off), n_clouds, iptr(ti), dptr(partial), stream()), 'regtr_gemm_stream')
@@ -359,7 +365,7 @@ def _block_tail(x1, x1_stats, row_div, f, w1_kn, w2_kn, seg_off, max_len, slope,
     K2, N = (f.shape[1] if f is not None else 0), w1_kn.shape[1]
     n_clouds = seg_off.numel() - 1
     nb = L.regtr_block_tail_ws_bytes(n_clouds, int(max_len), N, K1, K2)
-    ws = torch.empty(nb, dtype=torch.uint8, device=x1.device)       # not the shared scratch: sized per call, used across four launches
+    ws = _ws(nb, x1.device)       # sized per call, used across four launches
     ti = tile_segments(seg_off, M, 256)
     y = torch.empty((M, N), dtype=torch.float32, device=x1.device)
     st = torch.empty((2 if K2 else 1, n_clouds, N, 2), dtype=torch.float32, device=x1.device) if want_stats else None
@@ -1431,7 +1437,7 @@ def _sumsq(tab, keep):
     sl = _optim_norm_slice()
     n_part = int(((tab['n'] + (sl - 1)) // sl).sum())
     dev = keep[0].device if keep else torch.device('cuda', torch.cuda.current_device())
-    partials = torch.empty(n_part, dtype=torch.float64, device=dev)
+    partials = _ws_as(n_part, torch.float64, dev)
     check(_lib.lib().regtr_grad_sumsq(tab.ctypes.data if len(keep) else None, len(keep), dptr(partials) if n_part else None, n_part, stream()),
           'regtr_grad_sumsq')
     return partials

@@ -102,7 +102,7 @@ def _icp_fused(src, s_off, s_len, tgt, t_off, grid, r32, pose, max_dist, iters, 
     done = new(B, dtype=torch.int32, device=dev)
     idx = torch.empty(n_src, dtype=torch.int32, device=dev) if return_idx else None
     nb = L.regtr_icp_ws_bytes(B, max_len)
-    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
+    ws = ops._ws(max(nb, 1), dev)
     for k in range(iters + 1):
         check(L.regtr_icp_step(ptr(src) if n_src else None, iptr(s_off), n_src, max_len, iptr(t_off), tgt.shape[0], B, max_dist, r32,
                                bptr(grid.ws), grid.nbytes, ptr(pose), k, int(k == iters), rel_fitness, rel_rmse, dptr(stats),

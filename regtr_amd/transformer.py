@@ -219,7 +219,7 @@ class TransformerCrossEncoder(nn.Module):
             f16, planes = False, (3 if ctx.force_x3 else max(int(l0.gemm_planes), 3 if l0.attn_precision == 3 else 1))
             table, eps = self._param_table(False)
         nb = L.regtr_cross_encoder_ws_bytes(n, D, F)
-        ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+        ws = ops._ws(nb, x.device)
         g = b = None
         feps = 0.0
         if self.norm is not None:
