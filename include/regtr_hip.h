@@ -274,6 +274,14 @@ int regtr_gemm_stream_tile_rows(void);
 int regtr_gemm_stream(const float* A, int lda, const void* planes, float* C, int ldc, int M, int N, int K,
                       const float* a_stats, float a_slope, const int* seg_off, int n_seg, const void* tile_info,
                       double* stat_partial, void* stream);
+/* The same call with its launch form named (tests and tools/stream_bench.py; regtr_gemm_stream is form 0): 0 the measured choice per
+ * (K, N); 1 one workgroup per (256-row tile, column block); 2 one workgroup per 256-row tile that loads and splits its rows once and walks
+ * all column blocks (taken wherever there are two or more).  C and stat_partial hold the same bits in every form.  A new entry point
+ * only: no existing signature changes, REGTR_ABI_VERSION stays as it is. */
+int regtr_gemm_stream_form(const float* A, int lda, const void* planes, float* C, int ldc, int M, int N, int K,
+                           const float* a_stats, float a_slope, const int* seg_off, int n_seg, const void* tile_info,
+                           double* stat_partial, int form, void* stream);
+int regtr_gemm_stream_walks_columns(int N, int K, int form);   /* 1: that form launches the column-walking kernel for (N, K); host only */
 /* Linear -> InstanceNorm [+ Linear -> InstanceNorm of a second input] -> LeakyReLU in one pass over the NARROW inputs
  * (csrc/block_tail.hip):  Y = LeakyReLU_slope( InstanceNorm(A1' W1) [+ InstanceNorm(A2 W2)] ).  The per-cloud statistics of a product
  * come from the K x K second moments of its input (float64), so no product is ever written.  Two served forms

@@ -91,6 +91,8 @@ SIGNATURES = {
     'regtr_block_tail_ws_bytes': (_Z, [_I, _I, _I, _I, _I]),
     'regtr_block_tail': (_I, [_P, _I, _P, _F, _P, _P, _I, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _F, _F, _P, _I, _P, _Z, _P, _P]),
     'regtr_gemm_stream': (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _F, _P, _I, _P, _P, _P]),
+    'regtr_gemm_stream_walks_columns': (_I, [_I, _I, _I]),
+    'regtr_gemm_stream_form': (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _F, _P, _I, _P, _P, _I, _P]),
     'regtr_gemm_x3_stat_tile_rows': (_I, [_I, _I, _I]),
     'regtr_instnorm_finalize_tiles': (_I, [_P, _P, _I, _I, _I, _F, _P, _P]),
     'regtr_add_f32': (_I, [_P, _P, _Z, _P, _P]),

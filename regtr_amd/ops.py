@@ -333,8 +333,9 @@ def gemm_stream(a, sw, seg_off, a_stats=None, a_slope=0.1, want_stats=False, eps
     if want_stats:
         partial = _ws_as(((M + R - 1) // R + n_clouds) * N * 2, torch.float64, a.device)
     out = torch.empty((M, N), dtype=torch.float32, device=a.device)
-    check(L.regtr_gemm_stream(raw(a), a.stride(0) if M > 1 else K, bptr(sw.planes), ptr(out), N, M, N, K, ptr(a_stats), a_slope,
-                              iptr(seg_off), n_clouds, iptr(ti), dptr(partial), stream()), 'regtr_gemm_stream')
+    form = 0 if strip_columns is None else (2 if strip_columns else 1)
+    check(L.regtr_gemm_stream_form(raw(a), a.stride(0) if M > 1 else K, bptr(sw.planes), ptr(out), N, M, N, K, ptr(a_stats), a_slope,
+                                   iptr(seg_off), n_clouds, iptr(ti), dptr(partial), form, stream()), 'regtr_gemm_stream_form')
     if not want_stats:
         return out
     stats = torch.empty((n_clouds, N, 2), dtype=torch.float32, device=a.device)
@@ -419,6 +420,9 @@ SMALL_REGIME_ROWS = 131072
 # Routing switches: plain module attributes, never read from the environment.  Tests and measure.py assign them to take the other path as the reference.
 use_stream_gemm = True      # one-shot strip kernel for the shallow levels' Linears
 use_block_tail = True       # resnet-block tail / first block from input moments (csrc/block_tail.hip)
+# launch form of the strip GEMM's wide outputs (two or more column blocks): None = the measured choice per (K, N) compiled into
+# csrc/gemm_stream.hip; True = one workgroup per row tile walks all column blocks; False = one workgroup per column block.  Same bits either way.
+strip_columns = None
 PRENORM_MIN_ROWS = 65536        # a LEVEL with fewer rows than this (of a large batch): the extra normalise pass costs more than the gather saves
 prenorm_gather = True       # unary1's IN + LReLU applied before the gather (packed support records)
 # unary2's folded InstanceNorm + LeakyReLU operand is applied by a separate in-place pass instead where the fold would route to the tiled kernel
