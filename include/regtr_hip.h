@@ -73,6 +73,9 @@
  *                             match + float64 moments, then the per-pair Kabsch solve, fitness / inlier_rmse and the stop rule
  *   regtr_icp_ws_bytes /
  *   regtr_icp_chunk           (no reference counterpart) its workspace size and chunking
+ *   regtr_estimate_normals    (no reference counterpart) per-point surface normals from the exact integer moments of the radius neighbourhood
+ *   regtr_icp_plane_step      (no reference counterpart) one point-to-plane ICP iteration: regtr_icp_step's match, the 6x6 normal
+ *                             equations in float64, the LDL^T solve and the update of a float64 master pose
  */
 #ifndef REGTR_HIP_H
 #define REGTR_HIP_H
@@ -1044,6 +1047,45 @@ int regtr_icp_step(const float* src_xyz, const int* src_off, int n_src, int max_
                    double max_dist, float grid_radius, const void* grid_ws, size_t grid_ws_bytes, float* pose, int iter, int stats_only,
                    double rel_fitness, double rel_rmse, double* stats, int* iters_run, int* done, int* idx, double* d2, void* ws,
                    size_t ws_bytes, void* stream);
+
+/* ---- surface normals and point-to-plane ICP (regtr_amd/refine.py; csrc/icp_plane.hip) -----------------------------------------------
+ * New entry points only: no existing signature changes, REGTR_ABI_VERSION stays as it is.  Neither has a workspace or a size query: the
+ * arrays below are the caller's, with the stated shapes. */
+
+/* Surface normals of packed clouds: xyz [n, 3] float32 with seg_off [n_clouds + 1]; grid_ws a cell grid built by regtr_cellgrid_build over
+ * the SAME rows (ns_cap = n) with grid_radius * (1 + 1e-6) >= radius.  Per point p the points q of its own cloud with float64
+ * d2 = (dx dx + dy dy) + dz dz < radius^2 on the widened coordinates (p itself included) add dq = rint((q - p) 2^s), s the largest
+ * integer with radius 2^s <= 2^20, to int64 sums: moments [n, 10] (optional) = n | sum dq (3) | sum dq dq^T (xx xy xz yy yz zz).  The
+ * sums are exact, so they do not depend on the order in which the grid lists a cell's points: the outputs are bit-reproducible.
+ * In float64 then m = S1 / n, C_ab = S2_ab / n - m_a m_b, and the eigen-decomposition of C by the one-sided Jacobi SVD of
+ * regtr_weighted_procrustes (l2 >= l1 >= l0).  valid [n] int32 = (n >= 3 and l1 > 2^-40 l2); normals [n, 3] float32 = the unit
+ * eigenvector of l0 rounded to float32 (its sign is unspecified), exactly 0 where valid is 0.
+ * n == 0: REGTR_OK, nothing launched.  Refused (REGTR_ERR_ARG, nothing launched): n < 0, n_clouds < 1, radius or grid_radius not > 0,
+ * a grid built for a smaller radius, NULL seg_off / grid_ws, NULL xyz / normals / valid with n > 0, a pointer that is not aligned to its
+ * element (grid_ws: 16 bytes).  REGTR_ERR_WORKSPACE: grid_ws_bytes below regtr_cellgrid_ws_bytes(n, n_clouds). */
+int regtr_estimate_normals(const float* xyz, const int* seg_off, int n, int n_clouds, double radius, float grid_radius, const void* grid_ws,
+                           size_t grid_ws_bytes, float* normals, int* valid, long long* moments, void* stream);
+
+/* ONE iteration of point-to-plane ICP over packed pairs, two launches as regtr_icp_step and with its arguments where the names agree
+ * (the same chunking regtr_icp_chunk(), float32 transform and match rule: idx, n_match, fitness and inlier_rmse are regtr_icp_step's
+ * bits for the same pose).  tgt_normals [n_tgt, 3] float32 and tgt_valid [n_tgt] int32: regtr_estimate_normals' outputs for the targets.
+ * Accumulate: a match whose target has a valid normal nrm adds, in float64 with y the transformed source point, r = nrm . (y - q) and
+ * J = [y x nrm, nrm] to  partial [n_pairs, ceil(max_src_len / chunk), 30] float64 = n_match | sum d2 | n_sys | sum J^T J (the 21 upper
+ * entries by rows) | sum J^T r (6), per chunk and in a fixed order; other matches count for n_match and sum d2 only.  Every slot the
+ * solve reads was written by this call's accumulate.
+ * Solve, per pair: stats [n_pairs, 3] as regtr_icp_step.  The pair is DONE by regtr_icp_step's relative rule and for a non-finite pose,
+ * and also when n_sys < 6, or when the LDL^T (float64, no pivoting) of J^T J scaled to unit diagonal meets a pivot <= 2^-23 (one wall
+ * fixes no pose).  Otherwise (J^T J) x = -J^T r, dT = (Rz(x2) Ry(x1) Rx(x0), x[3:6]) and pose64 <- dT pose64 on the float64 master pose
+ * pose64 [n_pairs, 12]; pose [n_pairs, 12] float32 = its rounding, iters_run = iter + 1.  iter == 0 writes pose64 = pose before
+ * anything else, so the caller need not initialise it.  Rows are always transformed with the float32 pose: the stats are those of the
+ * returned pose.  A done pair's pose, pose64, stats, iters_run and idx rows are never written again.  stats_only as regtr_icp_step.
+ * n_src == 0: REGTR_OK, nothing launched.  Refused (REGTR_ERR_ARG, nothing launched): what regtr_icp_step refuses, n_pairs < 1, NULL
+ * pose64 / partial, NULL tgt_normals / tgt_valid with n_tgt > 0, a pointer that is not aligned to its element (grid_ws: 16 bytes).
+ * REGTR_ERR_WORKSPACE: grid_ws_bytes below regtr_cellgrid_ws_bytes(n_tgt, n_pairs). */
+int regtr_icp_plane_step(const float* src_xyz, const int* src_off, int n_src, int max_src_len, const float* tgt_normals, const int* tgt_valid,
+                         const int* tgt_off, int n_tgt, int n_pairs, double max_dist, float grid_radius, const void* grid_ws,
+                         size_t grid_ws_bytes, float* pose, double* pose64, int iter, int stats_only, double rel_fitness, double rel_rmse,
+                         double* stats, int* iters_run, int* done, int* idx, double* partial, void* stream);
 
 #ifdef __cplusplus
 }

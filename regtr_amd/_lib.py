@@ -175,6 +175,9 @@ SIGNATURES = {
     'regtr_icp_ws_bytes': (_Z, [_I, _I]),
     'regtr_icp_step': (_I, [_P, _P, _I, _I, _P, _I, _I, _c.c_double, _F, _P, _Z, _P, _I, _I, _c.c_double, _c.c_double, _P, _P, _P, _P, _P,
                             _P, _Z, _P]),
+    'regtr_estimate_normals': (_I, [_P, _P, _I, _I, _c.c_double, _F, _P, _Z, _P, _P, _P, _P]),
+    'regtr_icp_plane_step': (_I, [_P, _P, _I, _I, _P, _P, _P, _I, _I, _c.c_double, _F, _P, _Z, _P, _P, _I, _I, _c.c_double, _c.c_double,
+                                  _P, _P, _P, _P, _P, _P]),
 }
 
 COMPOSITE = ('regtr_encoder_fwd', 'regtr_cross_encoder_fwd')      # bound through a GIL-releasing handle (see _load)

@@ -17,10 +17,10 @@ VARIANT = os.environ.get('REGTR_VARIANT', '')
 VARIANT_FLAGS = os.environ.get('REGTR_VARIANT_FLAGS', '').split()
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 ARCH = 'gfx950'
-SOURCES = ['preprocess.hip', 'kpconv.hip', 'kpconv_bwd.hip', 'gemm.hip', 'gemm_x3.hip', 'gemm_stream.hip', 'block_tail.hip', 'norm.hip', 'posemb_mlp.hip', 'norm_pool_bwd.hip', 'attention.hip', 'attention_bwd.hip', 'layer_bwd.hip', 'head_bwd.hip', 'cross_encoder.hip', 'encoder.hip', 'procrustes.hip', 'losses.hip', 'circle_loss.hip', 'augment.hip', 'augment_modelnet.hip', 'metrics.hip', 'optim.hip', 'cloud_bank.hip', 'grad_bucket.hip', 'icp.hip']
+SOURCES = ['preprocess.hip', 'kpconv.hip', 'kpconv_bwd.hip', 'gemm.hip', 'gemm_x3.hip', 'gemm_stream.hip', 'block_tail.hip', 'norm.hip', 'posemb_mlp.hip', 'norm_pool_bwd.hip', 'attention.hip', 'attention_bwd.hip', 'layer_bwd.hip', 'head_bwd.hip', 'cross_encoder.hip', 'encoder.hip', 'procrustes.hip', 'losses.hip', 'circle_loss.hip', 'augment.hip', 'augment_modelnet.hip', 'metrics.hip', 'optim.hip', 'cloud_bank.hip', 'grad_bucket.hip', 'icp.hip', 'icp_plane.hip']
 # bit-level parity of the float32 distance / voxel arithmetic with the reference's SSE2 build needs no contraction
 # kpconv.hip: SLP-packed f32 VALU (v_pk_*) beside MFMAs costs more than it saves and blocks v_add_f32_dpp fusion
-EXTRA = {'preprocess.hip': ['-ffp-contract=off'], 'losses.hip': ['-ffp-contract=off'], 'circle_loss.hip': ['-ffp-contract=off'], 'augment.hip': ['-ffp-contract=off'], 'augment_modelnet.hip': ['-ffp-contract=off'], 'metrics.hip': ['-ffp-contract=off'], 'optim.hip': ['-ffp-contract=off'], 'grad_bucket.hip': ['-ffp-contract=off'], 'icp.hip': ['-ffp-contract=off'], 'ref_order.hip': ['-ffp-contract=off'], 'kpconv.hip': ['-fno-slp-vectorize']}
+EXTRA = {'preprocess.hip': ['-ffp-contract=off'], 'losses.hip': ['-ffp-contract=off'], 'circle_loss.hip': ['-ffp-contract=off'], 'augment.hip': ['-ffp-contract=off'], 'augment_modelnet.hip': ['-ffp-contract=off'], 'metrics.hip': ['-ffp-contract=off'], 'optim.hip': ['-ffp-contract=off'], 'grad_bucket.hip': ['-ffp-contract=off'], 'icp.hip': ['-ffp-contract=off'], 'icp_plane.hip': ['-ffp-contract=off'], 'ref_order.hip': ['-ffp-contract=off'], 'kpconv.hip': ['-fno-slp-vectorize']}
 COMMON = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-Wno-unused-result',
           '-I' + os.path.join(os.path.dirname(HERE), 'include')]
 

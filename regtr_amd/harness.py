@@ -1041,8 +1041,8 @@ def run_test(model, pairs, batch, device, logger=None, max_pairs=None, num_worke
     losses: also RegTR.compute_loss(per_pair=True) of every pair (3DMatch-style pair sources: GT pose per pair, level-0 masks from
     overlap.compute_overlap_masks at cfg.overlap_radius); the means over all pairs of all ranks (one extra all-reduce) are returned in
     timing['losses'].  Without it the launches and outputs are those of a plain run.
-    refine: None, or {'max_dist', 'iters'}: every batch's last-layer pose is polished on the batch's raw clouds by RegTR.refine_pose
-    (point-to-point ICP, regtr_amd/refine.py) on the stream of its forward, one model or replicas alike; the REFINED poses are returned
+    refine: None, or {'max_dist', 'iters'[, 'method', 'normal_radius']}: every batch's last-layer pose is polished on the batch's raw
+    clouds by RegTR.refine_pose (ICP, regtr_amd/refine.py; point to point unless method says 'point_to_plane') on the stream of its forward, one model or replicas alike; the REFINED poses are returned
     and timing['refine'] holds the means over all pairs of all ranks of fitness and inlier_rmse before and after.  None: no launch and
     no output of a plain run changes.
     Returns, on every rank, (poses (n_total, 3, 4) float32 numpy ordered by pair id, pair ids, timing dict)."""
@@ -1067,8 +1067,8 @@ def run_test(model, pairs, batch, device, logger=None, max_pairs=None, num_worke
     streams = [torch.cuda.Stream(device) for _ in range(R)] if (cuda and R > 1) else [None] * R
     it, turn, counter = iter(loader), threading.Lock(), itertools.count()
     done, errs, fwd_ms, loss_done, refine_done = [], [], [], [], []
-    if refine is not None and set(refine) != {'max_dist', 'iters'}:
-        raise ValueError(f"run_test(refine=...): a dict with exactly 'max_dist' and 'iters' expected, got {sorted(refine)}")
+    if refine is not None and not {'max_dist', 'iters'} <= set(refine) <= {'max_dist', 'iters', 'method', 'normal_radius'}:
+        raise ValueError(f"run_test(refine=...): a dict with 'max_dist' and 'iters' (and at most 'method', 'normal_radius') expected, got {sorted(refine)}")
     if losses:
         if any(m.cfg.get('dataset', '3dmatch') != '3dmatch' for m in models):
             raise NotImplementedError('run_test(losses=True): ModelNet losses are not implemented (3DMatch-style pair sources only)')
@@ -1102,7 +1102,8 @@ def run_test(model, pairs, batch, device, logger=None, max_pairs=None, num_worke
                     if refine is not None:
                         from . import refine as refine_
                         before = refine_.evaluate_registration(b['src_xyz'], b['tgt_xyz'], out['pose'][-1], refine['max_dist'])
-                        res = models[r].refine_pose(fb, out['pose'][-1], max_dist=refine['max_dist'], iters=refine['iters'])
+                        res = models[r].refine_pose(fb, out['pose'][-1], max_dist=refine['max_dist'], iters=refine['iters'],
+                                                    **{k_: refine[k_] for k_ in ('method', 'normal_radius') if k_ in refine})
                         refine_done.append((k, torch.stack([before[0], before[1], res.fitness, res.inlier_rmse])))      # (4, B) float64
                         out = {'pose': res.pose[None]}
                     done.append((k, out['pose'][-1], b['ids'] if 'ids' in b else [i_['idx'] for i_ in b['items']]))      # (B, 3, 4), stays on the device

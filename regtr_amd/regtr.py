@@ -951,15 +951,20 @@ class RegTR(nn.Module):
         return {'rot_err_deg': err['rot_err_deg'].to(torch.float32), 'trans_err': err['trans_err'].to(torch.float32)}
 
     @torch.no_grad()
-    def refine_pose(self, batch, pose, max_dist=None, iters=30):
+    def refine_pose(self, batch, pose, max_dist=None, iters=30, method='point_to_point', normal_radius=None):
         """Polishes `pose` ((B, 3, 4) or (B, 4, 4), e.g. forward's pred['pose'][-1]) on the batch's full-resolution clouds
-        batch['src_xyz'] / batch['tgt_xyz'] by point-to-point ICP (regtr_amd/refine.py: icp; no reference counterpart).  max_dist: the
-        correspondence distance, by default twice the first subsampling cell.  Returns refine.ICPResult (pose, fitness, inlier_rmse,
-        n_inliers, iters_run), device tensors; enqueued on the current stream, no host wait."""
+        batch['src_xyz'] / batch['tgt_xyz'] by ICP (regtr_amd/refine.py: icp; no reference counterpart).  max_dist: the correspondence
+        distance, by default twice the first subsampling cell.  method: 'point_to_point' (default) or 'point_to_plane', which estimates
+        the targets' normals with normal_radius (default twice the first subsampling cell).  Returns refine.ICPResult (pose, fitness,
+        inlier_rmse, n_inliers, iters_run), device tensors; enqueued on the current stream, no host wait."""
         from . import refine
         if max_dist is None:
             max_dist = 2 * self.cfg.first_subsampling_dl
-        return refine.icp(batch['src_xyz'], batch['tgt_xyz'], pose, max_dist, iters=iters)
+        if method == 'point_to_point' and normal_radius is None:
+            return refine.icp(batch['src_xyz'], batch['tgt_xyz'], pose, max_dist, iters=iters)
+        if normal_radius is None:
+            normal_radius = 2 * self.cfg.first_subsampling_dl
+        return refine.icp(batch['src_xyz'], batch['tgt_xyz'], pose, max_dist, iters=iters, method=method, normal_radius=normal_radius)
 
     def validation_step(self, batch, batch_idx=None):
         """generic_reg_model.py:82-91: forward (no gradients), compute_loss, compute_metrics -> (losses, metrics).  Reads no parameter's

@@ -60,11 +60,14 @@ parser.add_argument('--max_pairs', type=int, default=None)
 parser.add_argument('--losses', action='store_true',
                     help='also compute the reference\'s test losses (RegTR.compute_loss per pair on GT overlap masks) and log a [Losses] line; '
                          '3DMatch-style pair sources only')
-parser.add_argument('--refine', choices=('icp',), default=None,
-                    help='polish every predicted pose on the full-resolution clouds before it is written (regtr_amd.refine.icp: point-to-point '
-                         'ICP on the device, on the forward\'s stream); est.log then holds the refined poses.  Not with --share_backbone')
+parser.add_argument('--refine', choices=('icp', 'icp_plane'), default=None,
+                    help='polish every predicted pose on the full-resolution clouds before it is written (regtr_amd.refine.icp on the device, on '
+                         'the forward\'s stream: icp point to point, icp_plane point to plane with target normals estimated on the device); '
+                         'est.log then holds the refined poses.  Not with --share_backbone')
 parser.add_argument('--refine_dist', type=float, default=None, help='--refine: correspondence distance (default 2 x cfg.first_subsampling_dl)')
 parser.add_argument('--refine_iters', type=int, default=30, help='--refine: ICP iterations at most (default 30)')
+parser.add_argument('--refine_normal_radius', type=float, default=None,
+                    help='--refine icp_plane: radius of the normal estimation (default 2 x cfg.first_subsampling_dl)')
 parser.add_argument('--share_backbone', action='store_true',
                     help='encode every fragment once and register all its pairs against the cached result (RegTR.encode_clouds / register, '
                          'harness.run_test_shared): one model, one loader thread; not with --losses or --replicas')
@@ -272,6 +275,8 @@ def main():
     refine = None
     if opt.refine:
         refine = {'max_dist': opt.refine_dist if opt.refine_dist is not None else 2 * cfg.first_subsampling_dl, 'iters': opt.refine_iters}
+        if opt.refine == 'icp_plane':
+            refine.update(method='point_to_plane', normal_radius=opt.refine_normal_radius)
     if opt.share_backbone:
         poses, ids, timing = harness.run_test_shared(model, pairs, opt.batch, device, logger, opt.max_pairs, max_bank_clouds=opt.max_bank_clouds)
         logger.info(f'[Shared backbone] clouds_encoded / pair_slots = {timing["clouds_encoded"]} / {timing["pair_slots"]} = '
@@ -282,7 +287,7 @@ def main():
                                              losses=opt.losses, refine=refine)
         if refine is not None:
             rf = timing['refine']
-            logger.info(f'[Refine] icp, max_dist {refine["max_dist"]:g}, at most {refine["iters"]} iterations: fitness {rf["fitness_before"]:.4f} -> '
+            logger.info(f'[Refine] {opt.refine}, max_dist {refine["max_dist"]:g}, at most {refine["iters"]} iterations: fitness {rf["fitness_before"]:.4f} -> '
                         f'{rf["fitness_after"]:.4f}, inlier_rmse {rf["inlier_rmse_before"]:.5f} -> {rf["inlier_rmse_after"]:.5f} (means over {len(ids)} pairs)')
     if pool is not None:
         logger.info(f'loader: {timing["loader"]}; forward ms (host clock, incl. the end-of-forward status wait): {timing["forward_ms"]}')
